@@ -19,8 +19,21 @@ consensus draws / the whole sampling wall time, adaptation included (data upload
 `accuracy` compares the consensus with the full-data posterior (MAP + inverse Hessian from
 the GPU gradient, tools/laplace.py) and with the data-generating parameters.
 
-After the headline, the same process (every rank of an N-rank run) times the other BASELINE
-configurations: configs[1] (8 schools x 4096 chains, rank 0: a one-GPU config), configs[2]
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what `value` needs: data ->
+sampler -> W untimed steps -> K timed steps -> the line (metric, value, ms_per_step, roofline
+of the timed window).  Its chains are still in Stan's adaptation: a step costs one sweep of
+the data whatever the phase, and every chain evaluates one gradient per step.  Everything
+else on this page -- the Stan warmup run to its end before the timed steps, the ESS phase,
+the combine, accuracy, the CPU baselines and the other configurations -- runs with --full.
+--dump-outputs DIR (either kind of run) writes what the sampler holds after the last timed
+step as DIR/<name>.npy (float64): per chain the transitions completed, step size and inverse
+metric, the unconstrained draw of every transition completed so far (zero where a chain has
+not got there; the first transitions that fit DUMP_BYTES), and the run counters.  Data, seeds and
+step counts are fixed by the arguments, so two builds given the same arguments can be compared
+array for array.
+
+With --full, after the headline, the same process (every rank of an N-rank run) times the
+other BASELINE configurations: configs[1] (8 schools x 4096 chains, rank 0: a one-GPU config), configs[2]
 (linear N=1e7 d=50, 8 shards over the N ranks, the reference sampler's settings), configs[3]
 at the driver API's default chains=1, and configs[4] (full-data logistic d=1000, 64 chains,
 rows split over the N ranks with a per-leapfrog gradient all-reduce).  Each is a compact
@@ -28,9 +41,9 @@ sub-record; the line's keys are explained in DESIGN.md section 4 ("bench line ke
 headline ESS/s, min ESS and accuracy come LAST in the line (a driver that keeps the tail of
 stdout keeps them).
 
-Usage: python bench.py [--gpus N --steps K --warmup W].  --gpus N > 1 without a launcher starts N
-rank processes itself (one per GPU, RCCL) before any GPU call; under a
-launcher (WORLD_SIZE set) --gpus must equal the world size or the run is refused.
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].
+--gpus N > 1 without a launcher starts N rank processes itself (one per GPU, RCCL) before any
+GPU call; under a launcher (WORLD_SIZE set) --gpus must equal the world size or the run is refused.
 """
 import argparse
 import datetime
@@ -63,9 +76,15 @@ def parse(argv=None):
     p.add_argument("--launch-check", action="store_true",
                    help="start the ranks, build the process group, report world size / backend / rank devices and "
                         "exit: the launcher path without sampling (CPU: STARK_DIST_BACKEND=gloo)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: the Stan warmup before the timed steps, the ESS "
+                        "phase, combine, accuracy, CPU baselines and the other BASELINE configurations (minutes)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the sampler holds after the last of them as DIR/<name>.npy "
+                        "(float64; at most DUMP_BYTES in all)")
     p.add_argument("--throughput-only", action="store_true",
                    help="time the K steps (sampler still in adaptation) and print the line: no ESS phase, accuracy, "
-                        "CPU baseline or sub-records")
+                        "CPU baseline or sub-records.  What a run without --full does; with --full, overrides it")
     p.add_argument("--deadline-s", type=float, default=500.0,
                    help="wall-time budget of the whole run: an optional phase (second criterion, sub-records) whose "
                         "expected cost would cross it is skipped and the line says so")
@@ -129,7 +148,39 @@ def parse(argv=None):
                         "the phase times to this path")
     p.add_argument("--detail-json", default=None,
                    help="rank 0 also writes the uncompacted records (every sub-object of the line, in full) here")
-    return p.parse_args(argv)
+    a = p.parse_args(argv)
+    if not a.full and (a.dump_draws or a.ess_budget_s is not None or a.second_criterion != "none"):
+        p.error("--dump-draws, --ess-budget-s and --second-criterion belong to the ESS phase: add --full")
+    # a run without --full is the throughput-only run, its sampler keeping the draws of the
+    # warmup transitions it times (what --dump-outputs writes)
+    a.save_warmup = not a.full
+    a.throughput_only = a.throughput_only or not a.full
+    return a
+
+
+DUMP_BYTES = 60e6   # --dump-outputs: bound of the files written, all arrays together
+
+
+def dump_outputs(path, sampler, info, first, rank, world):
+    """What the caller of the timed sampler.run() holds after its last step, as float64 .npy
+    files under `path`: iterations (transitions completed per chain, shard-major), stepsize and
+    inv_metric (per chain), unconstrained (chains x T x D: the draw of transition first + j of
+    every chain that has completed it, zero otherwise; T = the most any chain has completed,
+    cut to what fits DUMP_BYTES) and counters (COUNTERS, whole run so far)."""
+    os.makedirs(path, exist_ok=True)
+    its = sampler.iterations()
+    eps, im = sampler.adaptation()
+    ud = np.concatenate([sampler.unconstrained(s) for s in range(sampler.model.nshards)])
+    done = np.clip(its - first, 0, ud.shape[1])
+    T = int(min(done.max(), DUMP_BYTES // (8 * ud.shape[0] * ud.shape[2]) - 1))
+    ud = np.where(np.arange(T)[None, :, None] < done[:, None, None], ud[:, :T], 0.0)
+    out = {"iterations": its.astype(np.float64), "stepsize": eps, "inv_metric": im, "unconstrained": ud,
+           "counters": np.array([float(info[k]) for k in COUNTERS])}
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + (".npy" if world == 1 else f".rank{rank}.npy")), arr)
+
+
+COUNTERS = ("grad_evals", "leapfrogs", "steps", "sweeps", "shard_sweeps", "divergent", "errors")
 
 
 def cpu_baseline(d, rows_per_shard, shards, seconds, family="logistic"):
@@ -505,7 +556,8 @@ def consensus_job(a, R, ctx, left, cpu_seconds=None):
     # cover the timed window and the fixed post-warmup draws of the ESS phase
     n_samp = W + K + ND + 1
     sampler = model.sampler(num_warmup=A, num_samples=n_samp, chains=a.chains, seed=a.seed + 1,
-                            shard_ids=shard_ids, stepsize_jitter=a.stepsize_jitter, nuts_criterion=a.nuts_criterion)
+                            shard_ids=shard_ids, stepsize_jitter=a.stepsize_jitter, nuts_criterion=a.nuts_criterion,
+                            save_warmup=a.save_warmup)
     tag = f"{a.family} d={a.d}"
     R.log(f"{tag}: {spr} shards x {rows_per_shard} rows per rank in {t_gen:.1f}s "
           f"({model.device_bytes() / 1e9:.1f} GB on this GPU)")
@@ -556,6 +608,8 @@ def consensus_job(a, R, ctx, left, cpu_seconds=None):
                       "chains_per_shard": a.chains, "num_warmup": A, "stepsize_jitter": a.stepsize_jitter,
                       "nuts_criterion": a.nuts_criterion, "parallelism": f"shard-dp{world}"},
            "timed_window_monotonic_ns": [w0, w1]}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, sampler, i1, 0 if a.save_warmup else A, rank, world)
     if a.throughput_only:
         # the timed window only (the sampler still adapting: a step costs one sweep whatever the phase)
         rec["config"]["workload"] = f"bayesian {a.family} regression, {a.shards} subposterior shards, throughput only"
@@ -839,8 +893,8 @@ def compact_fulldata(rec):
 
 def sub_args(a, **kw):
     d = dict(vars(a))
-    d.update(dict(second_criterion="none", dump_draws=None, ess_budget_s=None, shard_offset=0,
-                  throughput_only=False, no_accuracy=False))
+    d.update(dict(second_criterion="none", dump_draws=None, dump_outputs=None, ess_budget_s=None, shard_offset=0,
+                  throughput_only=False, save_warmup=False, no_accuracy=False))
     d.update(kw)
     return argparse.Namespace(**d)
 

@@ -23,8 +23,8 @@ def test_gpus_2_spawns_two_ranks():
     """--launch-check walks the run's record schedule with the same collectives and skip
     decisions the run takes: at --gpus 2 configs[2], configs[3] chains=1 and configs[4] run on
     BOTH ranks (configs[2] 8 shards as 4 + 4, configs[4] rows per GPU x 2), configs[1] on rank 0."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--launch-check"], capture_output=True, text=True,
-                       timeout=180, env=_env(STARK_DIST_BACKEND="gloo"))
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--launch-check"], capture_output=True,
+                       text=True, timeout=180, env=_env(STARK_DIST_BACKEND="gloo"))
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["world_size"] == 2 and line["dist_backend"] == "gloo"
@@ -150,14 +150,67 @@ def test_check_world():
     assert "WORLD_SIZE=4" in bench.check_world(8, {"WORLD_SIZE": "4"})
 
 
+def test_plain_run_is_the_throughput_run_and_full_is_opt_in(capsys):
+    """Without --full the bench times the headline steps only; the ESS-phase options need --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not a.full and a.throughput_only and a.save_warmup and a.steps == 7 and a.warmup == 3
+    assert a.dump_outputs is None
+    f = bench.parse(["--full", "--dump-outputs", "d"])
+    assert f.full and not f.throughput_only and not f.save_warmup and f.dump_outputs == "d"
+    assert bench.parse(["--full", "--throughput-only"]).throughput_only
+    for extra in (["--dump-draws", "x.npz"], ["--ess-budget-s", "5"], ["--second-criterion", "stan2.19"]):
+        with pytest.raises(SystemExit):
+            bench.parse(extra)
+        assert "--full" in capsys.readouterr().err
+        bench.parse(["--full", *extra])
+    # the sub-records of a --full run never write the headline's dumps
+    s = bench.sub_args(f, chains=1)
+    assert s.dump_outputs is None and not s.save_warmup and s.chains == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dump_outputs(tmp_path):
+    """A plain run: --steps sets the timed steps, the line holds the headline keys and none of
+    the --full records, and --dump-outputs writes the sampler's state after the last timed step
+    as float64 arrays (two shards x 4 chains, d = 10: D = 11 unconstrained coordinates)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "40", "--warmup", "8", "--rows", "4e4",
+                        "--shards", "2", "--d", "10", "--chains", "4", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=120, env=_env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 40 and line["warmup"] == 8 and line["n_gpus"] == 1
+    assert line["unit"] == "gradient evals/sec" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0
+    # every chain evaluates one gradient per step: value = chains * steps / time
+    assert abs(line["value"] - 8 * 40 / (40 * line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+    assert not {"ess_per_sec", "cpu_baseline", "other_configs", "configs1_schools", "accuracy"} & set(line)
+    arrs = {f.name[:-4]: np.load(f) for f in out.iterdir()}
+    assert set(arrs) == {"iterations", "stepsize", "inv_metric", "unconstrained", "counters"}
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64e6
+    its, ud = arrs["iterations"], arrs["unconstrained"]
+    assert its.shape == (8,) and arrs["stepsize"].shape == (8,) and arrs["inv_metric"].shape == (8, 11)
+    assert dict(zip(bench.COUNTERS, arrs["counters"]))["steps"] == 48          # W + K steps, no more
+    assert its.max() >= 1 and ud.shape == (8, int(its.max()), 11)
+    for c in range(8):      # a draw for every completed transition, zero beyond
+        n = int(its[c])
+        assert np.all(np.any(ud[c, :n] != 0, axis=1)) and not ud[c, n:].any()
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(500)
 def test_gpus_2_gloo_rehearsal_reproduces_one_rank_consensus():
     """`bench.py --gpus 2` on one GPU (gloo rehearsal: both ranks share the device, one shard
     each) gives the 1-rank run's consensus bit for bit: shard RNG streams and the chunk-order
     reduction do not depend on placement, and the all-gather keys the shards by global id."""
-    args = ["--rows", "4e5", "--shards", "2", "--d", "10", "--adapt-iters", "60", "--ess-draws", "60", "--steps", "20",
-            "--warmup", "5", "--no-cpu-baseline", "--no-schools", "--no-accuracy",
+    args = ["--full", "--rows", "4e5", "--shards", "2", "--d", "10", "--adapt-iters", "60", "--ess-draws", "60",
+            "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-schools", "--no-accuracy",
             # the other configs at rehearsal sizes: configs[2] 8 x 5e3 rows, configs[4] 2e4 rows per rank
             "--cfg2-rows", "4e4", "--cfg2-adapt", "100", "--cfg2-draws", "60", "--cfg4-rows-per-gpu", "2e4",
             "--cfg4-steps", "4"]

@@ -4,7 +4,7 @@ d = 100, 8 shards x 16 chains) under the reference's sampler settings (pystan 2 
 criterion, stepsize_jitter 0, iter = 2000: 1000 warmup + 1000 draws), where one 8-shard launch
 on one GPU does not fit a gpurun call.
 
-Each shard k ran as `bench.py --rows 1.25e7 --shards 1 --shard-offset k --dump-draws ...`: the
+Each shard k ran as `bench.py --full --rows 1.25e7 --shards 1 --shard-offset k --dump-draws ...`: the
 rows and RNG keys of shard k of the 8-shard job, alone on one GPU -- what rank k of the 8-GPU
 job runs (one shard per GPU, no data-path collective).  This script combines the
 dumps as the job's consensus would (engine.consensus(separate_lp=True), restated here in numpy:

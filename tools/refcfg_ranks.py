@@ -6,7 +6,7 @@ The 8-GPU job (logistic N = 1e8, d = 100, one 1.25e7-row shard x 16 chains per G
 data-path collective) under pystan 2's settings -- Stan 2.19.1's NUTS criterion, stepsize_jitter
 0, iter = 2000: 1000 warmup + 1000 draws per chain (stark/stark.py:48, 60-63) -- has ranks that
 take longer than one gpurun call.  Here rank k (shard k's rows and RNG keys, exactly what
-`bench.py --rows 1.25e7 --shards 1 --shard-offset k` samples) runs on this GPU under a wall
+`bench.py --full --rows 1.25e7 --shards 1 --shard-offset k` samples) runs on this GPU under a wall
 budget; when the budget runs out the sampler state is saved (engine.Sampler.save_state: every
 chain's position, momentum, tree stack, adaptation and RNG counters, the draws so far) together
 with the sampling time spent, and the next call loads it and continues -- bit for bit the run

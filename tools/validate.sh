@@ -27,7 +27,7 @@ cp "$O/sweep_pmc.json" profiles/sweep_pmc.json
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -d "$O/pmc_sq" -o pmc --output-format csv -- python3 tools/sweep_run.py --chains 16 --steps 6 > "$O/pmc_sq.log" 2>&1 || exit 9
 python3 tools/pmc_arms.py "$O/pmc_sq/pmc_counter_collection.csv" --json "$O/sweep16_pmc.json" > "$O/pmc_sq_summary.txt" 2>&1
 rm -rf "$O/pmc_fetch" "$O/pmc_write" "$O/pmc_sq"
-timeout -k 10 800 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run -- python3 bench.py "$@" > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 800 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run -- python3 bench.py --full "$@" > "$O/bench.json" 2> "$O/bench.err"
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit 10
 python3 tools/rocpd_summary.py window "$O/prof/run_results.db" --kernel k_sweep16 --bench-json "$O/bench.json" --json "$O/window.json"
 python3 tools/rocpd_summary.py stats "$O/prof/run_results.db" > "$O/kernel_stats.csv" 2>&1; head -8 "$O/kernel_stats.csv"
