@@ -10,6 +10,8 @@
  *   stk_model_create_synthetic  SURVEY.md 8d synthetic shards (bench; no host rows)
  *   stk_log_density_grad        Stan log_prob<propto=true,jacobian=true> + gradient, the
  *                               unit of work inside stark/stark.py:48 `sm.sampling`
+ *   stk_log_density_grad_shards the same for every shard at once, launched as a sampling run
+ *                               launches it (parity hook)
  *   stk_sample / stk_sampler_*  stark/stark.py:48-56  `sm.sampling(data, **kw)` +
  *                               `fit.extract()` -> P x S matrix, for every local partition
  *                               (stark/stark.py:65 mapPartitions(_mcmc(...)))
@@ -159,6 +161,10 @@ STK_API int stk_model_device_bytes(const stk_model* m, int64_t* bytes);
 
 /* ---- log density + gradient at C points of one shard (parity hook) ---- */
 STK_API int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, double* lp, double* grad);
+/* lp and gradient of EVERY shard at C points each, through the grouped launches of a
+ * sampling run (parity hook).  q: [nshards][C][D], lp: [nshards][C], grad: [nshards][C][D]
+ * (grad may be NULL).  Regressions only; C must be a chain count the sampler takes. */
+STK_API int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double* lp, double* grad);
 
 /* ---- sampling: stark/stark.py:43-56 for every shard of the model ---- */
 STK_API int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out);

@@ -85,6 +85,7 @@ SIGNATURES = [
     ("stk_model_copy_data", ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     ("stk_model_device_bytes", ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),
     ("stk_log_density_grad", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _vp, _vp]),
+    ("stk_log_density_grad_shards", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp]),
     ("stk_sampler_create", ctypes.c_int, [_vp, ctypes.POINTER(Config), _pp]),
     ("stk_sampler_run", ctypes.c_int, [_vp, _i32, _i64]),
     ("stk_sampler_info", ctypes.c_int, [_vp, ctypes.POINTER(RunInfo)]),

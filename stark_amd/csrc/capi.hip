@@ -116,6 +116,36 @@ struct stk_model {
   int64_t bytes = 0;
 };
 
+// The grouped sweep launches of a regression model at C chains per shard: consecutive shards of
+// equal n share one launch of nsh * G blocks; every shard's partial sums lie Gs = max G chunks
+// apart.  One construction for the sampler and the multi-shard parity hook.
+struct SweepGroup { int shard0, nsh, T, LD, G; size_t lds; };
+struct SweepPlan {
+  std::vector<SweepGroup> groups;
+  int Gs = 1;
+  int64_t nmax = 0;
+  size_t partial_bytes = 0;   // [nshards][Gs][C][d + 2] doubles
+  size_t ws_bytes = 0;        // v5 workspace for every shard (0 for the other variants)
+};
+static SweepPlan sweep_plan(const stk_model* m, int C) {
+  SweepPlan p;
+  for (int sh = 0; sh < m->nshards;) {
+    SweepGroup gr{};
+    gr.shard0 = sh;
+    stk_sweep_geometry(m->sh[sh].n, m->d, &gr.T, &gr.LD, &gr.G, &gr.lds, C);
+    int e = sh + 1;
+    while (e < m->nshards && m->sh[e].n == m->sh[sh].n) ++e;
+    gr.nsh = e - sh;
+    p.Gs = std::max(p.Gs, gr.G);
+    p.groups.push_back(gr);
+    sh = e;
+  }
+  for (int sh = 0; sh < m->nshards; ++sh) p.nmax = std::max<int64_t>(p.nmax, m->sh[sh].n);
+  p.partial_bytes = sizeof(double) * (size_t)m->nshards * p.Gs * C * (m->d + 2);
+  p.ws_bytes = stk_sweep_ws_bytes(p.nmax, m->d, C, m->nshards);
+  return p;
+}
+
 struct stk_sampler {
   stk_model* m = nullptr;
   stk_config cfg{};
@@ -132,8 +162,7 @@ struct stk_sampler {
   stk_allreduce_fn ar_fn = nullptr;   // full-data mode: rank-sum of [grad | lp] after every reduce
   void* ar_user = nullptr;
   int Gs = 1;
-  struct Group { int shard0, nsh, T, LD, G; size_t lds; };
-  std::vector<Group> groups;
+  std::vector<SweepGroup> groups;
   std::vector<hipEvent_t> ev;
   std::vector<int> iv_host;
   std::vector<unsigned long long> cnt_host;
@@ -512,6 +541,49 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
   return STK_OK;
 }
 
+// Every shard at C points each through the sampler's grouped launches (sweep_plan): the parity
+// hook for multi-shard grids, shard0 > 0 and a partial-sum stride Gs above a group's own G.
+int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
+  ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_shards: bad arguments");
+  ARG_CHECK(m->family == STK_LOGREG || m->family == STK_LINREG, "stk_log_density_grad_shards: regression families only");
+  ARG_CHECK(stk_sweep_supported(C, m->d), "chains per shard must be 1, 2, 4, 8, 16 (d <= 128) or 64 for regressions");
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const ShardDev* shd = m->sh_dev.as<ShardDev>();
+  const int D = m->Dmax;                       // one d for every shard of a regression model
+  const int Dp = (m->Dmax + 7) / 8 * 8;
+  const size_t rows = (size_t)m->nshards * C;
+  const SweepPlan plan = sweep_plan(m, C);
+  SweepWs ws{};
+  if (plan.ws_bytes) {
+    RC(ctx->scratch[4].ensure(plan.ws_bytes));
+    ws = stk_sweep_ws(ctx->scratch[4].p, plan.nmax, m->d, m->nshards);
+  }
+  RC(ctx->scratch[0].ensure(sizeof(double) * rows * Dp));
+  RC(ctx->scratch[1].ensure(sizeof(double) * rows));
+  RC(ctx->scratch[2].ensure(sizeof(double) * rows * Dp));
+  RC(ctx->scratch[3].ensure(plan.partial_bytes));
+  double* qb = ctx->scratch[0].as<double>();
+  double* lpb = ctx->scratch[1].as<double>();
+  double* gb = ctx->scratch[2].as<double>();
+  double* part = ctx->scratch[3].as<double>();
+  STK_HIP_CHECK(hipMemcpy2DAsync(qb, sizeof(double) * Dp, q, sizeof(double) * D, sizeof(double) * D, rows,
+                                 hipMemcpyDefault, st));
+  for (const auto& gr : plan.groups)
+    STK_HIP_CHECK(stk_launch_sweep(m->family, shd, gr.shard0, gr.nsh, m->sh[gr.shard0].n, m->d, gr.T, gr.LD, gr.G, plan.Gs,
+                                   gr.lds, qb, C, Dp, part, nullptr, 0, nullptr, st, plan.ws_bytes ? &ws : nullptr));
+  for (const auto& gr : plan.groups)
+    STK_HIP_CHECK(stk_launch_sweep_reduce(m->family, shd, gr.shard0, gr.nsh, m->d, gr.G, plan.Gs, qb, C, Dp, part,
+                                          nullptr, 0, lpb, gb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(lp, lpb, sizeof(double) * rows, hipMemcpyDefault, st));
+  if (grad)
+    STK_HIP_CHECK(hipMemcpy2DAsync(grad, sizeof(double) * D, gb, sizeof(double) * Dp, sizeof(double) * D, rows,
+                                   hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
 // ---------------------------------------------------------------- sampler
 static int sbuf(stk_sampler* s, size_t bytes, void** p) {
   s->bufs.emplace_back();
@@ -662,26 +734,13 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
   }
   if (rc == STK_OK && m->family != STK_SCHOOLS) {
     // sweep geometry, grouped by consecutive shards of equal n
-    int gmax = 1;
-    for (int sh = 0; sh < m->nshards;) {
-      stk_sampler::Group gr{};
-      gr.shard0 = sh;
-      stk_sweep_geometry(m->sh[sh].n, m->d, &gr.T, &gr.LD, &gr.G, &gr.lds, cfg->chains);
-      int e = sh + 1;
-      while (e < m->nshards && m->sh[e].n == m->sh[sh].n) ++e;
-      gr.nsh = e - sh;
-      gmax = std::max(gmax, gr.G);
-      s->groups.push_back(gr);
-      sh = e;
-    }
-    s->Gs = gmax;
-    rc = s->partial.ensure(sizeof(double) * (size_t)m->nshards * gmax * cfg->chains * (m->d + 2));
-    int64_t nmax = 0;
-    for (int sh = 0; sh < m->nshards; ++sh) nmax = std::max<int64_t>(nmax, m->sh[sh].n);
-    const size_t wsb = stk_sweep_ws_bytes(nmax, m->d, cfg->chains, m->nshards);
-    if (rc == STK_OK && wsb) {
-      rc = s->ws.ensure(wsb);
-      if (rc == STK_OK) s->sws = stk_sweep_ws(s->ws.p, nmax, m->d, m->nshards);
+    SweepPlan plan = sweep_plan(m, cfg->chains);
+    s->groups = std::move(plan.groups);
+    s->Gs = plan.Gs;
+    rc = s->partial.ensure(plan.partial_bytes);
+    if (rc == STK_OK && plan.ws_bytes) {
+      rc = s->ws.ensure(plan.ws_bytes);
+      if (rc == STK_OK) s->sws = stk_sweep_ws(s->ws.p, plan.nmax, m->d, m->nshards);
     }
     if (rc == STK_OK) rc = s->ran.ensure(sizeof(int) * 64);
   }

@@ -266,6 +266,18 @@ class Model:
         check(_lib.load().stk_log_density_grad(self._h, shard, q.ctypes.data, C, lp.ctypes.data, g.ctypes.data))
         return lp, g
 
+    def log_density_grad_shards(self, q):
+        """lp and grad lp of every shard at C points each (q: nshards x C x D), through the grouped
+        sweep launches of a sampling run (see stk_log_density_grad_shards); regressions only."""
+        q = np.ascontiguousarray(q, np.float64)
+        if q.ndim != 3 or q.shape[0] != self.nshards or q.shape[2] != self.D[0]:
+            raise ValueError(f"q must be [nshards = {self.nshards}, C, D = {self.D[0]}], got {q.shape}")
+        C = q.shape[1]
+        lp = np.empty(q.shape[:2])
+        g = np.empty(q.shape)
+        check(_lib.load().stk_log_density_grad_shards(self._h, q.ctypes.data, C, lp.ctypes.data, g.ctypes.data))
+        return lp, g
+
     def set_prior(self, alpha=None, beta=None):
         """normal(0, s) priors on alpha and beta (regressions); None or 0: flat."""
         check(_lib.load().stk_model_set_prior(self._h, float(alpha or 0.0), float(beta or 0.0)))

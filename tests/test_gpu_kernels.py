@@ -136,6 +136,32 @@ def test_synthetic_generator_matches_oracle(ctx, orc, d):
     X = orc.gen_x(seed, 0, 500, d)
     np.testing.assert_array_equal(got["x"], X)
     np.testing.assert_allclose(got["y"], orc.gen_y_linear(seed, 0, X, 0.0, beta), rtol=1e-13, atol=1e-13)
+    if d == 1:
+        return
+    # global 64-bit row indices (the bench's shards sit at offsets of 1e8 rows and more): the low
+    # word carries into the high one inside shard 0 of the first offset; the second has a high word > 1
+    rows, nsh = 300, 2
+    for row_offset in (2 ** 32 - 100, 2 ** 40 + 3):
+        m = engine.Model.synthetic(ctx, "logistic", nsh, rows, d, data_seed=seed, row_offset=row_offset)
+        for s in range(nsh):
+            got = m.copy_data(s)
+            X = orc.gen_x(seed, row_offset + s * rows, rows, d)
+            np.testing.assert_array_equal(got["x"], X)     # bit-exact
+            y, margin = orc.gen_y_logistic(seed, row_offset + s * rows, X, 0.0, beta)
+            diff = got["y"] != y
+            assert np.all(margin[diff] < 1e-12)
+        m.close()
+    # linear with an intercept and a noise scale, across the 32-bit carry
+    row_offset = 2 ** 32 - 100
+    ml = engine.Model.synthetic(ctx, "linear", nsh, rows, d, data_seed=seed, row_offset=row_offset, alpha=-0.7,
+                                noise_sigma=2.5)
+    for s in range(nsh):
+        got = ml.copy_data(s)
+        X = orc.gen_x(seed, row_offset + s * rows, rows, d)
+        np.testing.assert_array_equal(got["x"], X)
+        np.testing.assert_allclose(got["y"], orc.gen_y_linear(seed, row_offset + s * rows, X, -0.7, beta, 2.5),
+                                   rtol=1e-13, atol=1e-13)
+    ml.close()
 
 
 # ---------------------------------------------------------------- combine

@@ -105,6 +105,133 @@ def test_oracle_density_fd(orc, family):
     np.testing.assert_allclose(g, fd, rtol=1e-6, atol=1e-6 * max(1.0, np.abs(g).max()))
 
 
+def _ld_schools(y, sigma, q):
+    """stark_amd/models/schools.stan in long double: non-centred, tau = exp(u) with Jacobian + u.
+    Returns (lp, grad, sum |terms| of lp, sum |terms| of every gradient component)."""
+    L = np.longdouble
+    y, sigma, q = y.astype(L), sigma.astype(L), q.astype(L)
+    mu, u, eta = q[0], q[1], q[2:]
+    tau = np.exp(u)
+    z = (y - (mu + tau * eta)) / sigma
+    r = z / sigma
+    lp = (-eta * eta / 2 - z * z / 2).sum() + u
+    g = np.concatenate([[r.sum(), tau * (r * eta).sum() + 1], -eta + tau * r])
+    alp = (eta * eta / 2).sum() + (z * z / 2).sum() + abs(u)
+    ag = np.concatenate([[np.abs(r).sum(), (tau * np.abs(r * eta)).sum() + 1], np.abs(eta) + tau * np.abs(r)])
+    return lp, g, alp, ag
+
+
+def _ld_logistic(X, y, q):
+    """stark_amd/models/logistic.stan in long double with Stan 2.19's bernoulli_logit cut-offs:
+    with t = (2y - 1) eta, the term is -exp(-t) above 20, t below -20, -log1p(exp(-t)) between."""
+    L = np.longdouble
+    X, q = X.astype(L), q.astype(L)
+    sgn = (2 * y - 1).astype(L)
+    t = sgn * (q[0] + X @ q[1:])
+    e = np.exp(-t)
+    lt = np.where(t > 20, -e, np.where(t < -20, t, -np.log1p(e)))
+    de = sgn * np.where(t > 20, e, np.where(t < -20, L(1), e / (e + 1)))
+    lp = lt.sum()
+    g = np.concatenate([[de.sum()], X.T @ de])
+    ag = np.concatenate([[np.abs(de).sum()], np.abs(X).T @ np.abs(de)])
+    return lp, g, np.abs(lt).sum(), ag
+
+
+def _ld_linear(X, y, q):
+    """stark_amd/models/linear.stan in long double: sigma = exp(u), lp = -ss/2 - N u + u."""
+    L = np.longdouble
+    X, y, q = X.astype(L), y.astype(L), q.astype(L)
+    n, d = X.shape
+    u = q[d + 1]
+    inv_s = np.exp(-u)
+    z = (y - (q[0] + X @ q[1:d + 1])) * inv_s
+    ss = (z * z).sum()
+    dm = z * inv_s
+    lp = -ss / 2 - n * u + u
+    g = np.concatenate([[dm.sum()], X.T @ dm, [-L(n) + ss + 1]])
+    ag = np.concatenate([[np.abs(dm).sum()], np.abs(X).T @ np.abs(dm), [L(n) + ss + 1]])
+    return lp, g, ss / 2 + n * abs(u) + abs(u), ag
+
+
+@pytest.mark.parametrize("family", ["schools", "logistic", "linear"])
+def test_oracle_density_matches_extended_precision(orc, family):
+    """The oracle's three densities and gradients against their restatement in long double (64-bit
+    mantissa).  The bar is derived: a sequential fp64 sum of n terms errs by at most
+    n 2^-53 sum |term_i| to first order, and every term carries a few roundings of its own (the
+    d-term dot product of eta, exp, log1p, the products): |oracle - ld| <= 4 (n + d) 2^-53 sum
+    |terms|, the sums of absolute terms taken in long double per lp and per gradient component.
+    On the same inputs that bound is to lie below 1e-11 max(|value|, 1), so the GPU tests' 1e-10
+    bar against the oracle has a factor 10 of room above the oracle's own error.
+
+    A worst-case bound relative to the value says something only where the sum does not cancel
+    (sum |terms| / |value| is what it scales with; the GPU tests floor their gradient bar for
+    the same reason), so the regression points are chosen away from the mode: see the comments
+    at the inputs.
+
+    Measured (x86-64): the oracle's error is at most 0.10 of the bound (schools) and 3.0e-3 of it
+    (regressions), i.e. at most 3.6e-4 of 1e-11 max(|value|, 1) everywhere.  The bound is at most
+    0.091 of 1e-11 max(|value|, 1) for every lp, 0.022 for the schools gradient, 0.10 for the
+    logistic gradient and 0.72 for the linear one."""
+    if np.finfo(np.longdouble).eps >= 2.0 ** -53:
+        pytest.skip("np.longdouble is no wider than fp64 on this platform")
+    rng = np.random.default_rng(8)
+    cases = []          # (name, oracle model, n + d, long-double restatement, q)
+    if family == "schools":
+        for J, y, sigma in ((8, orc.SCHOOLS_Y, orc.SCHOOLS_SIGMA), (70, rng.normal(0, 10, 70), rng.uniform(5, 20, 70))):
+            om = orc.Model(orc.FAM_SCHOOLS, y=y, sigma=sigma)
+            for k in range(3):
+                cases.append((f"J={J} q{k}", om, J, lambda q, y=y, sigma=sigma: _ld_schools(y, sigma, q),
+                              rng.normal(0, 1, om.D)))
+    else:
+        # linear: every coefficient 0.3 away from the generating one, so that no gradient component is
+        # the cancelling sum it is near the mode (there sum |terms| exceeds |value| without limit)
+        n, d = 2000, 40
+        X = rng.uniform(-1.7, 1.7, (n, d))
+        beta = rng.normal(0, 1 / np.sqrt(d), d)
+        away = beta + 0.3 * np.where(np.arange(d) % 2 == 0, 1.0, -1.0)
+        if family == "logistic":
+            # The residual y - p saturates, so over centred columns no point keeps all 41 gradient
+            # components from cancelling (sum |x_ij de_i| stays >= 29 |sum x_ij de_i| for some j at
+            # n = 2000, d = 40, and the worst-case bound, linear in n, then exceeds 1e-11 |g_j|).
+            # Non-negative columns and an intercept that is too high make every component a sum of
+            # mostly one sign: the bound is about the arithmetic, not about cancellation.
+            X = np.abs(X)
+            eta = X @ beta
+            eta[: n // 50] *= 80.0
+            y = (rng.uniform(size=n) < 1 / (1 + np.exp(-eta))).astype(np.int32)
+            om = orc.Model(orc.FAM_LOGREG, X=X, y=y)
+            # the first point keeps every row between the cut-offs; the second puts the y = 1 rows
+            # above +20 and the y = 0 rows below -20
+            qs = [("alpha+3", np.concatenate([[3.0], beta])), ("alpha+100, 40 beta", np.concatenate([[100.0], 40 * beta]))]
+            t = (2 * y - 1) * (3.0 + X @ beta)
+            assert np.all(np.abs(t) < 20)
+            t = (2 * y - 1) * (100.0 + X @ (40 * beta))
+            assert (t > 20).sum() > 100 and (t < -20).sum() > 100
+            cases += [(name, om, n + d, lambda q: _ld_logistic(X, y, q), q) for name, q in qs]
+        else:
+            y = 0.3 + X @ beta + rng.normal(size=n)
+            om = orc.Model(orc.FAM_LINREG, X=X, y=y)
+            for u in (-6.0, 0.0, 6.0):
+                cases.append((f"log sigma={u}", om, n + d, lambda q: _ld_linear(X, y, q),
+                              np.concatenate([[0.8], away, [u]])))
+    res = []
+    for name, om, nd, ld, q in cases:
+        lp, g = om.lpgrad(q)
+        rlp, rg, alp, ag = ld(q)
+        got = np.concatenate([[lp], g]).astype(np.longdouble)
+        ref = np.concatenate([[rlp], rg])
+        bound = 4 * nd * np.longdouble(2.0) ** -53 * np.concatenate([[alp], ag])
+        room = 1e-11 * np.maximum(np.abs(ref), 1)
+        res.append((name, np.abs(got - ref), bound, room))
+        print(f"{family} {name}: max err/bound = {float((res[-1][1] / bound).max()):.3g}, "
+              f"err/(1e-11 max(|v|, 1)) = {float((res[-1][1] / room).max()):.3g}, "
+              f"bound/(1e-11 max(|v|, 1)) = lp {float(bound[0] / room[0]):.3g}, grad {float((bound[1:] / room[1:]).max()):.3g}")
+    for name, err, bound, room in res:
+        assert np.all(err <= bound), (name, float((err / bound).max()))
+    for name, err, bound, room in res:
+        assert np.all(bound < room), (name, float((bound / room).max()), int(np.argmax(bound / room)))
+
+
 def test_oracle_generator_shapes(orc):
     X = orc.gen_x(7, 0, 50, 9)
     assert X.shape == (50, 9) and np.all(np.abs(X) < np.sqrt(3))
