@@ -82,14 +82,19 @@ typedef struct {
   int32_t num_warmup;
   int32_t num_samples;
   int32_t chains;            /* chains per shard */
-  int32_t max_depth;
+  int32_t max_depth;         /* 1..30.  8 schools: the fused kernel holds a chain's 17 vectors and
+                                max_depth x 4 (stan2.19) or x 7 (stan2.23) stack vectors of
+                                Dp = roundup8(J + 2) doubles in LDS; a config whose image exceeds the
+                                CU's 160 KiB (only J >= 79 can: e.g. J = 126, stan2.23, max_depth >= 20)
+                                is refused with STK_E_ARG by stk_sampler_create */
   double adapt_delta, adapt_gamma, adapt_kappa, adapt_t0;
   double stepsize;           /* initial nominal step size */
   double init_radius;        /* inits ~ U(-R, R) on the unconstrained scale */
   int32_t adapt_init_buffer, adapt_term_buffer, adapt_window;
   int32_t adapt_engaged;
   uint64_t seed;
-  const double* init;        /* NULL, or nshards * chains * D unconstrained inits */
+  const double* init;        /* NULL, or nshards * chains * D unconstrained inits (shard-major,
+                                every chain of a shard at that shard's own D, no padding) */
   const double* inv_metric;  /* NULL (unit), or D initial diagonal inverse metric */
   int32_t skip_init_stepsize;/* test hook: do not run base_hmc::init_stepsize */
   int32_t iter_offset;       /* test hook: RNG iteration index of the first transition */

@@ -15,6 +15,7 @@ using namespace stk;
 
 // ---- kernels' launchers (other translation units)
 int stk_nch_for(int Dmax);
+size_t stk_fused_lds_bytes(const NutsArgs& A, int nch);
 hipError_t stk_launch_nuts_init(const NutsArgs& A, const double* init, const double* inv_metric, double stepsize,
                                 double init_radius, hipStream_t st);
 hipError_t stk_launch_nuts_step(const NutsArgs& A, int nch, int step_id, int pause_at, hipStream_t st);
@@ -623,8 +624,20 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
   STK_HIP_CHECK(hipSetDevice(ctx->device));
   const int nch = stk_nch_for(m->Dmax);
   ARG_CHECK(nch > 0, "dimension %d too large (max 1024)", m->Dmax);
-  if (m->family == STK_SCHOOLS) ARG_CHECK(nch <= 2, "8-schools supports J <= 126");
-  else ARG_CHECK(stk_sweep_supported(cfg->chains, m->d), "chains per shard must be 1, 2, 4, 8, 16 (d <= 128) or 64 for regressions");
+  if (m->family == STK_SCHOOLS) {
+    ARG_CHECK(nch <= 2, "8-schools supports J <= 126");
+    // the fused kernel keeps a chain's vectors and its max_depth-deep tree stack in LDS
+    NutsArgs G{};
+    G.Dp = (m->Dmax + 7) / 8 * 8;
+    G.max_depth = cfg->max_depth;
+    G.uturn_ext = cfg->nuts_criterion;
+    G.cpw_cap = cfg->chains_per_wave;
+    const size_t lds = stk_fused_lds_bytes(G, nch);
+    ARG_CHECK(lds <= BIG_LDS_BYTES,
+              "8-schools with J = %d at max_depth %d (nuts_criterion %d) needs %zu bytes of LDS per workgroup, the limit is %zu: "
+              "lower max_depth",
+              m->Dmax - 2, cfg->max_depth, cfg->nuts_criterion, lds, BIG_LDS_BYTES);
+  } else ARG_CHECK(stk_sweep_supported(cfg->chains, m->d), "chains per shard must be 1, 2, 4, 8, 16 (d <= 128) or 64 for regressions");
   stk_sampler* s = new stk_sampler();
   s->m = m;
   m->refs++;
@@ -690,8 +703,10 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
   double* init_dev = nullptr;
   double* im_dev = nullptr;
   if (rc == STK_OK && cfg->init) {
-    // init is nshards * chains * D with per-shard D; repack to Dmax stride per chain
-    std::vector<double> h((size_t)nchains * m->Dmax, 0.0);
+    // init is nshards * chains * D with per-shard D; k_nuts_init reads init[gid * Dp + e], one
+    // stride for every chain (a stride of the chain's own D lets a short shard's chains land on
+    // the elements of a longer shard before it)
+    std::vector<double> packed((size_t)nchains * Dp, 0.0);
     std::vector<double> tmp;
     size_t off = 0;
     for (int sh = 0; sh < m->nshards; ++sh) {
@@ -699,15 +714,9 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
       for (int c = 0; c < cfg->chains; ++c) {
         tmp.resize(D);
         if (hipMemcpy(tmp.data(), cfg->init + off, sizeof(double) * D, hipMemcpyDefault) != hipSuccess) rc = STK_E_ARG;
-        memcpy(&h[(size_t)(sh * cfg->chains + c) * m->Dmax], tmp.data(), sizeof(double) * D);
+        memcpy(&packed[(size_t)(sh * cfg->chains + c) * Dp], tmp.data(), sizeof(double) * D);
         off += D;
       }
-    }
-    // k_nuts_init reads init[gid * D(shard)] -- store each chain at gid * D_shard
-    std::vector<double> packed((size_t)nchains * m->Dmax, 0.0);
-    for (int gid = 0; gid < nchains; ++gid) {
-      const int D = m->sh[gid / cfg->chains].D;
-      memcpy(&packed[(size_t)gid * D], &h[(size_t)gid * m->Dmax], sizeof(double) * D);
     }
     if (rc == STK_OK && (rc = sbuf(s, sizeof(double) * packed.size(), &p)) == STK_OK) {
       init_dev = (double*)p;

@@ -129,6 +129,8 @@ __host__ __device__ inline uint32_t rng_stream(const NutsArgs& A, int gid) {
   return (uint32_t)((A.shard_ids ? A.shard_ids[s] : s) * A.C + gid % A.C);
 }
 
+constexpr size_t BIG_LDS_BYTES = 160 * 1024;   // the LDS of one gfx950 CU
+
 // Raise a kernel's dynamic-LDS limit to the CU's 160 KiB.  The attribute is per device, so it
 // is set once per (current device, kernel); a failure is returned to the launch that needed it.
 inline hipError_t allow_big_lds(const void* kern) {
@@ -139,7 +141,7 @@ inline hipError_t allow_big_lds(const void* kern) {
   static std::set<std::pair<int, const void*>> done;
   std::lock_guard<std::mutex> lock(mu);
   if (done.count({dev, kern})) return hipSuccess;
-  e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BIG_LDS_BYTES);
   if (e == hipSuccess) done.insert({dev, kern});
   return e;
 }

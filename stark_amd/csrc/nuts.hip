@@ -1081,7 +1081,7 @@ __global__ __launch_bounds__(64) void k_nuts_init(NutsArgs A, const double* init
   for (int e = lane; e < A.Dp; e += WAVE) {
     double q0 = 0.0, imv = 1.0;
     if (e < D) {
-      q0 = init ? init[(size_t)gid * D + e]
+      q0 = init ? init[(size_t)gid * A.Dp + e]
                 : -init_radius + 2.0 * init_radius * uniform_at(A.seed, rng_stream(A, gid), 0u, (uint32_t)e, TAG_INIT);
       if (inv_metric) imv = inv_metric[e];
     }
@@ -1265,14 +1265,19 @@ static hipError_t launch_step_t(const NutsArgs& A, int step_id, int pause_at, hi
   hipLaunchKernelGGL(k_nuts_step<NCH>, dim3(A.nchains), dim3(64), 0, st, A, step_id, pause_at);
   return hipGetLastError();
 }
+// Dynamic LDS of one k_nuts_fused_schools workgroup: cpw chain images (vectors unless zp, tree
+// stack, scalars, uniform window) and the exp / log1p table.
+static size_t fused_lds_image(const NutsArgs& A, int cpw, bool zp) {
+  const int seg = WAVE / cpw;
+  size_t per = (zp ? 0 : (size_t)V_COUNT * A.Dp) +   // ZP: the vectors are in registers (NutsChain::RV)
+               (size_t)A.max_depth * stack_vecs(A) * A.Dp + (size_t)A.max_depth * SS_COUNT +
+               S_COUNT + (I_COUNT + 1) / 2 + 2 * seg;  // + the chain's uniform window
+  per += per & 1;                                        // keep the table after the chains 16-B aligned
+  return sizeof(double) * (cpw * per + MT_N);
+}
 template <int NCH, int CPW, int MINW = 1, int UT = 0, bool ZP = false>
 static hipError_t launch_fused_zp(const NutsArgs& A, int pause_at, int max_steps, hipStream_t st) {
-  constexpr int SEG = WAVE / CPW;
-  size_t per = (ZP ? 0 : (size_t)V_COUNT * A.Dp) +   // ZP: the vectors are in registers (NutsChain::RV)
-               (size_t)A.max_depth * stack_vecs(A) * A.Dp + (size_t)A.max_depth * SS_COUNT +
-               S_COUNT + (I_COUNT + 1) / 2 + 2 * SEG;  // + the chain's uniform window
-  per += per & 1;                                        // keep the table after the chains 16-B aligned
-  const size_t lds = sizeof(double) * (CPW * per + MT_N);
+  const size_t lds = fused_lds_image(A, CPW, ZP);
   if (lds > 64 * 1024) {
     // the attribute is per device (allow_big_lds keys it on the current one); a failure is
     // reported as such rather than as a generic launch failure
@@ -1283,7 +1288,7 @@ static hipError_t launch_fused_zp(const NutsArgs& A, int pause_at, int max_steps
   return hipGetLastError();
 }
 // The zero-padding form (NutsChain ZP) where a chain's segment spans its vectors: 4 chains per wave
-// at Dp = 16 (8 schools, J = 8..14).  It is instantiated in its own translation unit,
+// at Dp = 16 (8 schools, J = 7..14).  It is instantiated in its own translation unit,
 // nuts_fused4.hip (this file with STK_NUTS_FUSED4_TU), so that it alone is built with LLVM's
 // iterative ILP scheduler (Makefile): that experimental scheduler gains it 2-3 % but has crashed
 // the compiler on other instantiations of this file.
@@ -1313,6 +1318,13 @@ static int fused_cpw(const NutsArgs& A) {
   int c = A.Dp <= 16 ? 4 : (A.Dp <= 32 ? 2 : 1);
   if (A.cpw_cap > 0) c = std::min(c, A.cpw_cap);
   return c;
+}
+
+// The image stk_launch_nuts_fused will ask for with these arguments (the sampler refuses a config
+// whose image exceeds STK_FUSED_LDS_MAX, the CU's LDS, before anything is launched).
+size_t stk_fused_lds_bytes(const NutsArgs& A, int nch) {
+  const int cpw = nch == 1 ? fused_cpw(A) : 1;
+  return fused_lds_image(A, cpw, nch == 1 && cpw == 4 && A.Dp == WAVE / 4);
 }
 
 int stk_nch_for(int Dmax) {
