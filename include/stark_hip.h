@@ -16,6 +16,8 @@
  *                               `fit.extract()` -> P x S matrix, for every local partition
  *                               (stark/stark.py:65 mapPartitions(_mcmc(...)))
  *   stk_transition              one Stan NUTS transition (parity hook, no adaptation)
+ *   stk_transition_dense        the same under a full D x D inverse metric (Stan's dense_e);
+ *                               stk_config.metric selects diag_e / dense_e / unit_e for a run
  *   stk_consensus_products      stark/stark.py:7-21   consensus_avg(J) reducer body
  *   stk_consensus_solve         stark/stark.py:66-70  inv(sum W) . sum W theta
  *   stk_consensus               stark/stark.py:66-70  reduce + solve over all shards
@@ -113,6 +115,17 @@ typedef struct {
   int32_t chains_per_wave;   /* 8-schools fused kernel: chains packed per 64-lane wave, 0 (default) =
                                 the most that fit (4 for D <= 16, 2 for D <= 32, else 1); 1 or 2 cap
                                 it (test hook: the packing changes no bit of the draws) */
+  int32_t metric;            /* Stan's metric: 0 (default) diag_e, 1 dense_e, 2 unit_e.
+                                dense_e: every chain adapts a full D x D inverse metric in the diag_e
+                                windows (covar_adaptation: Welford covariance, regularised as
+                                (n/(n+5)) cov + 1e-3 (5/(n+5)) I) and draws p = L^-T u, M^-1 = L L^T;
+                                regression families only (D <= 1024), refused for 8 schools.  A chain
+                                whose new metric is not positive definite stops like a step-size error
+                                (counted in stk_run_info.errors).
+                                unit_e: the metric stays I (inv_metric is ignored), only the step size
+                                adapts; every family */
+  const double* inv_metric_dense; /* dense_e: NULL (identity), or the D x D row-major symmetric
+                                positive definite initial inverse metric (else STK_E_ARG) */
 } stk_config;
 
 typedef struct {
@@ -184,7 +197,12 @@ STK_API int stk_sampler_draws(stk_sampler* s, int shard, double* out, double* st
 /* Unconstrained draws of one shard: out[chains][num_samples][D], or
  * out[chains][num_warmup + num_samples][D] when cfg.save_warmup is set. */
 STK_API int stk_sampler_draws_unconstrained(stk_sampler* s, int shard, double* out);
+/* Every chain's nominal step size (nshards * chains) and diagonal inverse metric
+ * ([nshards * chains][Dmax]; all ones under unit_e).  Either pointer may be NULL. */
 STK_API int stk_sampler_adaptation(stk_sampler* s, double* stepsize, double* inv_metric);
+/* The same for a dense_e sampler: inv_metric is [nshards * chains][D][D] row-major, every matrix
+ * symmetric to the bit.  STK_E_ARG for another metric. */
+STK_API int stk_sampler_adaptation_dense(stk_sampler* s, double* stepsize, double* inv_metric);
 /* Transitions completed so far by every chain (nshards * chains, shard-major). */
 STK_API int stk_sampler_iterations(stk_sampler* s, int32_t* iters);
 STK_API int stk_sampler_destroy(stk_sampler* s);
@@ -199,7 +217,9 @@ STK_API int stk_sampler_destroy(stk_sampler* s);
  * stk_sampler_state_bytes gives the size of the blob; stk_sampler_load_state refuses a blob
  * of another geometry / config (STK_E_ARG) before writing anything.  The data rows themselves
  * are not hashed (that would read the whole shard): loading into a model of the same geometry
- * built from other data is the caller's error and is not detected. */
+ * built from other data is the caller's error and is not detected.  A dense_e sampler's state also
+ * carries every chain's M^-1, its Cholesky factor and the window's Welford M2, and the config check
+ * includes the metric: a diag_e blob is refused by a dense_e sampler and the reverse. */
 STK_API int stk_sampler_state_bytes(stk_sampler* s, int64_t* bytes);
 STK_API int stk_sampler_save_state(stk_sampler* s, void* buf, int64_t bytes);
 STK_API int stk_sampler_load_state(stk_sampler* s, const void* buf, int64_t bytes);
@@ -224,6 +244,12 @@ STK_API int stk_sample(stk_model* m, const stk_config* cfg, double* draws, doubl
  * adaptation, RNG iteration index `iteration`: the unit of the GPU/CPU twin check. */
 STK_API int stk_transition(stk_model* m, int shard, double* q, int32_t C, uint64_t seed, int32_t iteration,
                            double eps, const double* inv_metric, int32_t max_depth, double* lp, double* stats);
+
+/* stk_transition under a dense metric: inv_metric is D x D row-major, symmetric positive definite
+ * (STK_E_ARG otherwise); momenta are p = L^-T u with M^-1 = L L^T and u the normals stk_transition
+ * draws for the same (seed, chain, iteration).  Regression families. */
+STK_API int stk_transition_dense(stk_model* m, int shard, double* q, int32_t C, uint64_t seed, int32_t iteration,
+                                 double eps, const double* inv_metric, int32_t max_depth, double* lp, double* stats);
 
 /* ---- consensus combine: stark/stark.py:7-21, 66-70 ---- */
 /* draws: nshards x P x S, out: P x S (host or device memory; device buffers are read and

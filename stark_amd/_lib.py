@@ -48,7 +48,8 @@ class Config(ctypes.Structure):
                 ("skip_init_stepsize", ctypes.c_int32), ("iter_offset", ctypes.c_int32),
                 ("save_warmup", ctypes.c_int32), ("shard_ids", ctypes.c_void_p),
                 ("stepsize_jitter", ctypes.c_double), ("nuts_criterion", ctypes.c_int32),
-                ("chains_per_wave", ctypes.c_int32)]
+                ("chains_per_wave", ctypes.c_int32), ("metric", ctypes.c_int32),
+                ("inv_metric_dense", ctypes.c_void_p)]
 
 
 class RunInfo(ctypes.Structure):
@@ -92,6 +93,7 @@ SIGNATURES = [
     ("stk_sampler_draws", ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     ("stk_sampler_draws_unconstrained", ctypes.c_int, [_vp, ctypes.c_int, _vp]),
     ("stk_sampler_adaptation", ctypes.c_int, [_vp, _vp, _vp]),
+    ("stk_sampler_adaptation_dense", ctypes.c_int, [_vp, _vp, _vp]),
     ("stk_sampler_iterations", ctypes.c_int, [_vp, _vp]),
     ("stk_sampler_destroy", ctypes.c_int, [_vp]),
     ("stk_sampler_state_bytes", ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),
@@ -101,6 +103,7 @@ SIGNATURES = [
     ("stk_sampler_set_allreduce", ctypes.c_int, [_vp, _vp, _vp, _vp]),
     ("stk_sample", ctypes.c_int, [_vp, ctypes.POINTER(Config), _vp, _vp, ctypes.POINTER(RunInfo)]),
     ("stk_transition", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _u64, _i32, _dbl, _vp, _i32, _vp, _vp]),
+    ("stk_transition_dense", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _u64, _i32, _dbl, _vp, _i32, _vp, _vp]),
     ("stk_consensus_products", ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     ("stk_consensus_solve", ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
     ("stk_consensus", ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),

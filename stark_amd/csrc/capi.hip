@@ -20,6 +20,8 @@ hipError_t stk_launch_nuts_init(const NutsArgs& A, const double* init, const dou
                                 double init_radius, hipStream_t st);
 hipError_t stk_launch_nuts_step(const NutsArgs& A, int nch, int step_id, int pause_at, hipStream_t st);
 hipError_t stk_launch_nuts_fused(const NutsArgs& A, int nch, int pause_at, int max_steps, hipStream_t st);
+hipError_t stk_launch_dense_init(const NutsArgs& A, const double* minv0, const double* chol0, hipStream_t st);
+hipError_t stk_launch_nuts_step_dense(const NutsArgs& A, int nch, int step_id, int pause_at, hipStream_t st);
 hipError_t stk_launch_schools_lpgrad(const ShardDev* shards, int shard, int nch, const double* q, int C, int Dp,
                                      double* lp, double* g, hipStream_t st);
 void stk_sweep_geometry(int64_t n, int d, int* T, int* LD, int* G, size_t* lds_bytes, int C);
@@ -586,6 +588,43 @@ int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double
 }
 
 // ---------------------------------------------------------------- sampler
+// dense_e: the caller's D x D initial inverse metric, checked and factored once on the host.
+// minv / chol come back [Dp][Dp] with zero padding (chol lower, M^-1 = L L^T).
+static int dense_metric_host(const double* src, int D, int Dp, std::vector<double>* minv, std::vector<double>* chol) {
+  std::vector<double> a((size_t)D * D);
+  if (hipMemcpy(a.data(), src, sizeof(double) * a.size(), hipMemcpyDefault) != hipSuccess) {
+    stk_set_error("inv_metric_dense: cannot read %d x %d doubles", D, D);
+    return STK_E_ARG;
+  }
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) {
+      const double x = a[(size_t)i * D + j], y = a[(size_t)j * D + i];
+      ARG_CHECK(std::isfinite(x), "inv_metric_dense[%d][%d] is not finite", i, j);
+      ARG_CHECK(std::fabs(x - y) <= 1e-12 * std::max(std::fabs(x), std::fabs(y)),
+                "inv_metric_dense is not symmetric: [%d][%d] = %.17g, [%d][%d] = %.17g", i, j, x, j, i, y);
+    }
+  minv->assign((size_t)Dp * Dp, 0.0);
+  chol->assign((size_t)Dp * Dp, 0.0);
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j <= i; ++j) {   // the lower triangle, mirrored: symmetric to the bit
+      (*minv)[(size_t)i * Dp + j] = (*minv)[(size_t)j * Dp + i] = a[(size_t)i * D + j];
+      (*chol)[(size_t)i * Dp + j] = a[(size_t)i * D + j];
+    }
+  double* L = chol->data();
+  for (int k = 0; k < D; ++k) {
+    const double piv = L[(size_t)k * Dp + k];
+    ARG_CHECK(piv > 0.0, "inv_metric_dense is not positive definite (pivot %d = %g)", k, piv);
+    const double d = std::sqrt(piv);
+    L[(size_t)k * Dp + k] = d;
+    for (int i = k + 1; i < D; ++i) L[(size_t)i * Dp + k] /= d;
+    for (int i = k + 1; i < D; ++i) {
+      const double ci = L[(size_t)i * Dp + k];
+      for (int j = k + 1; j <= i; ++j) L[(size_t)i * Dp + j] -= ci * L[(size_t)j * Dp + k];
+    }
+  }
+  return STK_OK;
+}
+
 static int sbuf(stk_sampler* s, size_t bytes, void** p) {
   s->bufs.emplace_back();
   RC(s->bufs.back().ensure(bytes));
@@ -620,10 +659,18 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
   ARG_CHECK(cfg->nuts_criterion == 0 || cfg->nuts_criterion == 1, "nuts_criterion must be 0 (Stan 2.19) or 1 (Stan >= 2.23)");
   ARG_CHECK(cfg->chains_per_wave >= 0 && cfg->chains_per_wave <= 4 && cfg->chains_per_wave != 3,
             "chains_per_wave must be 0, 1, 2 or 4");
+  ARG_CHECK(cfg->metric >= 0 && cfg->metric <= 2, "metric must be 0 (diag_e), 1 (dense_e) or 2 (unit_e)");
+  ARG_CHECK(cfg->metric != 1 || m->family != STK_SCHOOLS,
+            "metric dense_e is for the regression families (linear, logistic): the fused 8-schools kernel "
+            "has no dense form; use diag_e or unit_e");
   stk_ctx* ctx = m->ctx;
   STK_HIP_CHECK(hipSetDevice(ctx->device));
   const int nch = stk_nch_for(m->Dmax);
   ARG_CHECK(nch > 0, "dimension %d too large (max 1024)", m->Dmax);
+  const bool dense = cfg->metric == 1;
+  std::vector<double> minv_host, chol_host;
+  if (dense && cfg->inv_metric_dense)
+    RC(dense_metric_host(cfg->inv_metric_dense, m->Dmax, (m->Dmax + 7) / 8 * 8, &minv_host, &chol_host));
   if (m->family == STK_SCHOOLS) {
     ARG_CHECK(nch <= 2, "8-schools supports J <= 126");
     // the fused kernel keeps a chain's vectors and its max_depth-deep tree stack in LDS
@@ -658,7 +705,8 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
   A.iter_offset = cfg->iter_offset;
   unsigned nw = (unsigned)cfg->num_warmup, ib = (unsigned)cfg->adapt_init_buffer, tb = (unsigned)cfg->adapt_term_buffer,
            bw = (unsigned)cfg->adapt_window;
-  A.var_on = A.adapt && nw >= 20;
+  A.var_on = A.adapt && nw >= 20 && cfg->metric != 2;   // unit_e: the step size alone adapts
+  A.metric = cfg->metric;
   if (A.var_on && ib + bw + tb > nw) {   // windowed_adaptation::set_window_params, 15%/75%/10%
     ib = (unsigned)(0.15 * nw);
     tb = (unsigned)(0.1 * nw);
@@ -699,7 +747,24 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
   A.ud_iters = A.total_iters - A.ud_first;
   ALLOC(udraws, double, (size_t)nchains * A.ud_iters * Dp);
   ALLOC(req_step, int, (size_t)m->nshards);
+  if (dense) {
+    ALLOC(d_minv, double, (size_t)nchains * Dp * Dp);
+    ALLOC(d_chol, double, (size_t)nchains * Dp * Dp);
+    ALLOC(d_m2, double, (size_t)nchains * Dp * Dp);
+  }
 #undef ALLOC
+  double* minv_dev = nullptr;
+  double* chol_dev = nullptr;
+  if (rc == STK_OK && !minv_host.empty()) {
+    const size_t mb = sizeof(double) * Dp * Dp;
+    if ((rc = sbuf(s, 2 * mb, &p)) == STK_OK) {
+      minv_dev = (double*)p;
+      chol_dev = minv_dev + Dp * Dp;
+      if (hipMemcpy(minv_dev, minv_host.data(), mb, hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(chol_dev, chol_host.data(), mb, hipMemcpyHostToDevice) != hipSuccess)
+        rc = STK_E_HIP;
+    }
+  }
   double* init_dev = nullptr;
   double* im_dev = nullptr;
   if (rc == STK_OK && cfg->init) {
@@ -735,7 +800,7 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
     }
     if (rc == STK_E_ARG) stk_set_error("shard_ids: unreadable or negative");
   }
-  if (rc == STK_OK && cfg->inv_metric) {
+  if (rc == STK_OK && cfg->inv_metric && cfg->metric == 0) {
     if ((rc = sbuf(s, sizeof(double) * m->Dmax, &p)) == STK_OK) {
       im_dev = (double*)p;
       if (hipMemcpy(im_dev, cfg->inv_metric, sizeof(double) * m->Dmax, hipMemcpyDefault) != hipSuccess) rc = STK_E_HIP;
@@ -755,6 +820,7 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
   }
   if (rc == STK_OK) {
     hipError_t e = stk_launch_nuts_init(A, init_dev, im_dev, cfg->stepsize, cfg->init_radius, ctx->stream);
+    if (e == hipSuccess && dense) e = stk_launch_dense_init(A, minv_dev, chol_dev, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(A.draws, 0, sizeof(double) * (size_t)m->nshards * m->Pmax * A.S_total, ctx->stream);
     // a zeroed tree stack: the fused kernel's zero-padding form relies on +0 in every padding slot
     if (e == hipSuccess)
@@ -829,7 +895,8 @@ static int run_split_batch(stk_sampler* s, int nsteps, int pause_at) {
         return STK_E_STATE;
       }
     }
-    STK_HIP_CHECK(stk_launch_nuts_step(A, s->nch, step_id, pause_at, st));
+    if (A.metric == 1) STK_HIP_CHECK(stk_launch_nuts_step_dense(A, s->nch, step_id, pause_at, st));
+    else STK_HIP_CHECK(stk_launch_nuts_step(A, s->nch, step_id, pause_at, st));
     s->step++;
     s->steps++;
   }
@@ -993,6 +1060,24 @@ int stk_sampler_adaptation(stk_sampler* s, double* stepsize, double* inv_metric)
   return STK_OK;
 }
 
+int stk_sampler_adaptation_dense(stk_sampler* s, double* stepsize, double* inv_metric) {
+  ARG_CHECK(s, "NULL sampler");
+  ARG_CHECK(s->A.metric == 1, "stk_sampler_adaptation_dense: the sampler's metric is not dense_e");
+  stk_ctx* ctx = s->m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  const int n = s->A.nchains;
+  const size_t D = (size_t)s->m->Dmax, Dp = (size_t)s->A.Dp;
+  if (stepsize)
+    STK_HIP_CHECK(hipMemcpy2DAsync(stepsize, sizeof(double), s->A.sc + S_NOMEPS, sizeof(double) * S_COUNT,
+                                   sizeof(double), n, hipMemcpyDefault, ctx->stream));
+  if (inv_metric)
+    for (int c = 0; c < n; ++c)
+      STK_HIP_CHECK(hipMemcpy2DAsync(inv_metric + (size_t)c * D * D, sizeof(double) * D, s->A.d_minv + (size_t)c * Dp * Dp,
+                                     sizeof(double) * Dp, sizeof(double) * D, D, hipMemcpyDefault, ctx->stream));
+  STK_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return STK_OK;
+}
+
 int stk_sampler_iterations(stk_sampler* s, int32_t* iters) {
   ARG_CHECK(s && iters, "stk_sampler_iterations: bad arguments");
   stk_ctx* ctx = s->m->ctx;
@@ -1029,7 +1114,7 @@ std::vector<Seg> state_segments(const stk_sampler* s) {
   const NutsArgs& A = s->A;
   const size_t n = (size_t)A.nchains, Dp = (size_t)A.Dp, md = (size_t)A.max_depth;
   const size_t nsh = (size_t)s->m->nshards, S = (size_t)A.S_total;
-  return {{A.vec, sizeof(double) * n * V_COUNT * Dp},
+  std::vector<Seg> segs = {{A.vec, sizeof(double) * n * V_COUNT * Dp},
           {A.stk, sizeof(double) * n * md * SV_COUNT * Dp},
           {A.sc, sizeof(double) * n * S_COUNT},
           {A.stks, sizeof(double) * n * md * SS_COUNT},
@@ -1041,6 +1126,9 @@ std::vector<Seg> state_segments(const stk_sampler* s) {
           {A.stats, sizeof(double) * nsh * S * N_STATS},
           {A.udraws, sizeof(double) * n * (size_t)A.ud_iters * Dp},
           {A.req_step, sizeof(int) * nsh}};
+  if (A.metric == 1)   // dense_e: the chains' matrices (M^-1, its factor, the window's M2)
+    for (double* mat : {A.d_minv, A.d_chol, A.d_m2}) segs.push_back({mat, sizeof(double) * n * Dp * Dp});
+  return segs;
 }
 
 struct Fnv {
@@ -1063,6 +1151,7 @@ int state_geometry(const stk_sampler* s, uint64_t* out) {
   f.add(A.init_buffer), f.add(A.term_buffer), f.add(A.base_window);
   f.add(A.delta), f.add(A.gamma), f.add(A.kappa), f.add(A.t0), f.add(A.seed), f.add(A.jitter);
   f.add(A.uturn_ext), f.add(A.cpw_cap), f.add(A.ud_first), f.add(A.ud_iters), f.add(s->nch);
+  if (A.metric) f.add(A.metric);   // diag_e blobs keep the hash they always had
   std::vector<int32_t> ids(m->nshards);
   for (int i = 0; i < m->nshards; ++i) ids[i] = i;
   if (A.shard_ids)
@@ -1118,6 +1207,13 @@ int stk_sampler_load_state(stk_sampler* s, const void* buf, int64_t bytes) {
   ARG_CHECK(s && buf, "stk_sampler_load_state: bad arguments");
   int64_t need = 0;
   RC(stk_sampler_state_bytes(s, &need));
+  if (bytes >= (int64_t)sizeof(StateHeader)) {   // another metric: said so, before the sizes are compared
+    StateHeader h0;
+    memcpy(&h0, buf, sizeof(h0));
+    ARG_CHECK(memcmp(h0.magic, kStateMagic, 8) || h0.nsegs == state_segments(s).size(),
+              "stk_sampler_load_state: the state was saved with another metric (%u segments, this sampler has %zu)",
+              h0.nsegs, state_segments(s).size());
+  }
   ARG_CHECK(bytes == need, "stk_sampler_load_state: blob of %lld bytes, this sampler's state has %lld",
             (long long)bytes, (long long)need);
   stk_ctx* ctx = s->m->ctx;
@@ -1165,8 +1261,9 @@ int stk_sample(stk_model* m, const stk_config* cfg, double* draws, double* stats
   return rc;
 }
 
-int stk_transition(stk_model* m, int shard, double* q, int32_t C, uint64_t seed, int32_t iteration, double eps,
-                   const double* inv_metric, int32_t max_depth, double* lp, double* stats) {
+static int transition_impl(stk_model* m, int shard, double* q, int32_t C, uint64_t seed, int32_t iteration, double eps,
+                           const double* inv_metric, const double* inv_metric_dense, int32_t max_depth, double* lp,
+                           double* stats) {
   ARG_CHECK(m && q && C > 0 && shard >= 0 && shard < m->nshards, "stk_transition: bad arguments");
   const int D = m->sh[shard].D;
   stk_config cfg;
@@ -1180,6 +1277,10 @@ int stk_transition(stk_model* m, int shard, double* q, int32_t C, uint64_t seed,
   cfg.seed = seed;
   cfg.skip_init_stepsize = 1;
   cfg.iter_offset = iteration;
+  if (inv_metric_dense) {
+    cfg.metric = 1;
+    cfg.inv_metric_dense = inv_metric_dense;
+  }
   std::vector<double> qh((size_t)C * D);
   if (hipMemcpy(qh.data(), q, sizeof(double) * qh.size(), hipMemcpyDefault) != hipSuccess) {
     stk_set_error("stk_transition: cannot read q");
@@ -1217,6 +1318,17 @@ int stk_transition(stk_model* m, int shard, double* q, int32_t C, uint64_t seed,
   }
   stk_sampler_destroy(s);
   return rc;
+}
+
+int stk_transition(stk_model* m, int shard, double* q, int32_t C, uint64_t seed, int32_t iteration, double eps,
+                   const double* inv_metric, int32_t max_depth, double* lp, double* stats) {
+  return transition_impl(m, shard, q, C, seed, iteration, eps, inv_metric, nullptr, max_depth, lp, stats);
+}
+
+int stk_transition_dense(stk_model* m, int shard, double* q, int32_t C, uint64_t seed, int32_t iteration, double eps,
+                         const double* inv_metric, int32_t max_depth, double* lp, double* stats) {
+  ARG_CHECK(inv_metric, "stk_transition_dense: inv_metric (D x D) is NULL");
+  return transition_impl(m, shard, q, C, seed, iteration, eps, nullptr, inv_metric, max_depth, lp, stats);
 }
 
 // ---------------------------------------------------------------- consensus combine

@@ -116,6 +116,10 @@ struct NutsArgs {
   double jitter;         // stepsize_jitter (0: off)
   int uturn_ext;         // nuts_criterion: 1 = Stan >= 2.23 extra U-turn checks
   int cpw_cap;           // chains_per_wave cap of the fused 8-schools kernel (0: none)
+  int metric;            // 0 diag_e, 1 dense_e, 2 unit_e (stk_config.metric)
+  double* d_minv;        // dense_e: nchains * Dp * Dp   M^-1 (symmetric, stored in full)
+  double* d_chol;        // dense_e: nchains * Dp * Dp   L, M^-1 = L L^T (lower, rows contiguous)
+  double* d_m2;          // dense_e: nchains * Dp * Dp   Welford M2 of the current window
 };
 
 // Stack vectors per level in use: the Stan >= 2.23 junction checks need SV_PB / SV_PE / SV_PSE,

@@ -311,10 +311,252 @@ __device__ __forceinline__ void write_draw(const NutsArgs& A, const ShardDev& sh
   if (lane == 0) out[(size_t)(sh.P - 1) * S + col] = lp;
 }
 
+// ------------------------------------------------------------------ dense metric (dense_e)
+// Per-chain matrices of the dense instantiation (NutsChain DENSE), each [Dp][Dp] fp64 in global
+// memory and stored in full, and two LDS vectors of NCH * 64 doubles of the chain's wave.  All of
+// it is cold or per-leapfrog code of the dense kernels only (nuts_dense.hip); the diagonal
+// instantiations never reference it.
+struct DenseRefs {
+  double* minv = nullptr;   // M^-1, symmetric, zero padding
+  double* chol = nullptr;   // L (lower, rows contiguous) with M^-1 = L L^T
+  double* m2 = nullptr;     // Welford M2 of the current window
+  double* la = nullptr;     // LDS: input vector
+  double* lb = nullptr;     // LDS: output vector
+};
+// out = M^-1 pin: the lane owning element e = k 64 + lane sums M^-1[j Dp + e] pin[j] over j < Dp
+// (row j is contiguous over e, so a wave reads 512 consecutive bytes; column e of the symmetric
+// matrix) in four accumulators, j mod 4, combined in a fixed order -- the result depends on Dp
+// alone, not on the launch.  One wave per chain has nothing but its own loads to hide HBM latency
+// with: JB rows of KG chunks are loaded before their fmas, 8 to 32 independent loads in flight
+// (the plain j loop took 9.5 ms per step at D = 1001).  Lanes past D read column D - 1 and drop
+// the sum, so the loads need no exec mask.  pin holds zeros past D and the matrix zeros in its
+// padding; Dp is a multiple of 8.
+template <int NCH>
+__device__ __noinline__ void dense_matvec_cold(const double* M, const double* pin, double* out, int D, int Dp, int lane) {
+  constexpr int KG = NCH < 8 ? NCH : 8, JB = NCH < 8 ? 8 : 4;
+  typedef const __attribute__((address_space(3))) double* lds_cd;
+  const lds_cd pl = (lds_cd)pin;
+  const gptr_t<double> Mg = gp(M);
+  __syncthreads();
+#pragma unroll 1
+  for (int k0 = 0; k0 < NCH; k0 += KG) {
+    if (k0 * WAVE >= D) break;
+    double acc[KG][4];
+    int col[KG];
+#pragma unroll
+    for (int k = 0; k < KG; ++k) {
+      const int e = (k0 + k) * WAVE + lane;
+      col[k] = e < D ? e : D - 1;
+#pragma unroll
+      for (int a = 0; a < 4; ++a) acc[k][a] = 0.0;
+    }
+#pragma unroll 1
+    for (int j = 0; j < Dp; j += JB) {
+      double v[JB][KG], pj[JB];
+#pragma unroll
+      for (int b = 0; b < JB; ++b) {
+        pj[b] = pl[j + b];
+#pragma unroll
+        for (int k = 0; k < KG; ++k) v[b][k] = Mg[(size_t)(j + b) * Dp + col[k]];
+      }
+#pragma unroll
+      for (int b = 0; b < JB; ++b)
+#pragma unroll
+        for (int k = 0; k < KG; ++k) acc[k][b & 3] = fma(v[b][k], pj[b], acc[k][b & 3]);
+    }
+#pragma unroll
+    for (int k = 0; k < KG; ++k) {
+      const int e = (k0 + k) * WAVE + lane;
+      if (e < D) out[e] = (acc[k][0] + acc[k][1]) + (acc[k][2] + acc[k][3]);
+    }
+  }
+  __syncthreads();
+}
+// dense_e_metric::sample_p: L^T p = u by column-oriented back-substitution, in place in the LDS
+// vector u (zeros past D): once p[i] is known, L[i][j] p[i] leaves u[j] for every j < i (row i of L
+// is contiguous).  Blocked by 64 rows from the bottom, because a row-by-row loop pays one HBM
+// latency per row (about 1 us: 100 us per draw at D = 101, 2-3 ms at D = 1001):
+//   the diagonal block  lane l holds column b0 + l of rows b0 .. b0 + 63 in registers (64
+//                       independent row loads) and its own u; the 64 dependent steps are register
+//                       work, p[r] and L[r][r] broadcast by v_readlane;
+//   the panel           u[j] -= sum_r L[b0 + r][j] p[b0 + r] for the columns j < b0, 8 rows of up to
+//                       4 column chunks loaded before their fmas, rows in ascending order.
+__device__ __noinline__ void dense_backsolve_cold(const double* L, double* u, int D, int Dp, int lane) {
+  typedef __attribute__((address_space(3))) double* lds_d;
+  const lds_d ul = (lds_d)u;
+  const gptr_t<double> Lg = gp(L);
+  __syncthreads();
+#pragma unroll 1
+  for (int b0 = ((D - 1) / WAVE) * WAVE; b0 >= 0; b0 -= WAVE) {
+    const int nr = min(WAVE, D - b0);            // rows of this block (the bottom one may be short)
+    double t[WAVE];
+#pragma unroll
+    for (int r = 0; r < WAVE; ++r) {
+      const bool in = r < nr && lane <= r;       // the lower triangle, inside the matrix
+      const double v = Lg[in ? (size_t)(b0 + r) * Dp + b0 + lane : (size_t)0];
+      t[r] = in ? v : (lane == r ? 1.0 : 0.0);   // rows past D: p = u / 1 = 0
+    }
+    double x = ul[b0 + lane];
+#pragma unroll
+    for (int r = WAVE - 1; r >= 0; --r) {
+      const double pr = lane_d(x, r) / lane_d(t[r], r);
+      x = lane == r ? pr : (lane < r ? x - t[r] * pr : x);
+    }
+    ul[b0 + lane] = x;
+    __syncthreads();
+#pragma unroll 1
+    for (int c0 = 0; c0 < b0; c0 += 4 * WAVE) {
+      double a[4];
+      int col[4];
+      bool in[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int c = c0 + g * WAVE + lane;
+        in[g] = c < b0;
+        col[g] = in[g] ? c : 0;
+        a[g] = ul[col[g]];
+      }
+#pragma unroll 1
+      for (int r0 = 0; r0 < nr; r0 += 8) {
+        double v[8][4], pr[8];
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+          const bool rin = r0 + b < nr;
+          const int row = b0 + (rin ? r0 + b : 0);
+          pr[b] = rin ? ul[row] : 0.0;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) v[b][g] = Lg[(size_t)row * Dp + col[g]];
+        }
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) a[g] = fma(-v[b][g], pr[b], a[g]);
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        if (in[g]) ul[col[g]] = a[g];
+    }
+    __syncthreads();
+  }
+}
+// In-place Cholesky of the lower triangle of W (right-looking; the trailing update of row i runs
+// over its contiguous part (k, i]).  c: LDS scratch of Dp doubles.  One wave hides HBM latency only
+// with its own independent loads, so the column scaling takes 4 and the trailing update 8 rows per
+// pass, loads before stores.  Unblocked, it rereads the trailing matrix at every k (D^3 / 6 updates
+// of 16 B): 1.5 ms at D = 101, 0.5 s at D = 1001, a handful of times per run.
+// Returns nonzero on a non-positive or NaN pivot (wave-uniform: every lane reads the same pivot).
+__device__ __noinline__ int dense_cholesky_cold(double* W, double* c, int D, int Dp, int lane) {
+#pragma unroll 1
+  for (int k = 0; k < D; ++k) {
+    __syncthreads();
+    const double piv = W[(size_t)k * Dp + k];
+    if (!(piv > 0.0)) return 1;
+    const double d = sqrt(piv);
+    __syncthreads();
+    if (lane == 0) W[(size_t)k * Dp + k] = d;
+#pragma unroll 1
+    for (int i0 = k + 1 + lane; i0 < D; i0 += 4 * WAVE) {
+      double v[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int i = i0 + b * WAVE;
+        v[b] = W[(size_t)(i < D ? i : k) * Dp + k] / d;
+      }
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int i = i0 + b * WAVE;
+        if (i < D) {
+          W[(size_t)i * Dp + k] = v[b];
+          c[i] = v[b];
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int i0 = k + 1; i0 < D; i0 += 8) {
+#pragma unroll 1
+      for (int j = k + 1 + lane; j <= i0 + 7 && j < D; j += WAVE) {
+        const double cj = c[j];
+        double v[8];
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+          const int i = i0 + b;
+          v[b] = (i < D && j <= i) ? W[(size_t)i * Dp + j] : 0.0;
+        }
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+          const int i = i0 + b;
+          if (i < D && j <= i) W[(size_t)i * Dp + j] = v[b] - c[i] * cj;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  return 0;
+}
+// covar_adaptation::learn_covariance on the chain's wave.  in_window: the Welford update with the
+// draw qs (n = the count after this draw): delta = q - m, m += delta / n, M2 += (q - m) delta^T.
+// end_window: M^-1 = (n / (n + 5)) M2 / (n - 1) + 1e-3 (5 / (n + 5)) I, read from M2's lower
+// triangle so that it is symmetric to the bit; the estimator restarts; L is refactored.
+// Returns nonzero if the factorisation met a non-positive or NaN pivot.
+__device__ __noinline__ int dense_window_cold(const DenseRefs& dn, const double* qs, double* wm, int D, int Dp, int lane,
+                                              double n, bool in_window, bool end_window) {
+  if (in_window) {
+    __syncthreads();
+    for (int e = lane; e < D; e += WAVE) {
+      const double delta = qs[e] - wm[e];
+      const double m = wm[e] + delta / n;
+      wm[e] = m;
+      dn.la[e] = delta;
+      dn.lb[e] = qs[e] - m;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int i0 = 0; i0 < D; i0 += 8) {   // 8 rows per pass, loads before stores
+#pragma unroll 1
+      for (int j = lane; j < D; j += WAVE) {
+        const double dj = dn.la[j];
+        double v[8];
+#pragma unroll
+        for (int b = 0; b < 8; ++b) v[b] = dn.m2[(size_t)(i0 + b < D ? i0 + b : i0) * Dp + j];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+          if (i0 + b < D) dn.m2[(size_t)(i0 + b) * Dp + j] = v[b] + dn.lb[i0 + b] * dj;
+      }
+    }
+  }
+  if (!end_window) return 0;
+  __syncthreads();
+  const double w = n / (n + 5.0), reg = 1e-3 * (5.0 / (n + 5.0));
+  for (int i = 0; i < D; ++i) {
+    for (int j = lane; j < D; j += WAVE) {
+      const int hi = i > j ? i : j, lo = i > j ? j : i;
+      double v = dn.minv[(size_t)hi * Dp + lo];
+      if (n > 1) v = dn.m2[(size_t)hi * Dp + lo] / (n - 1.0);
+      v = w * v + (i == j ? reg : 0.0);
+      dn.chol[(size_t)i * Dp + j] = v;     // staged: minv's lower triangle is still being read
+    }
+  }
+  __syncthreads();
+  for (int i = 0; i < D; ++i) {
+    for (int j = lane; j < D; j += WAVE) {
+      const double v = dn.chol[(size_t)i * Dp + j];
+      dn.minv[(size_t)i * Dp + j] = v;
+      dn.m2[(size_t)i * Dp + j] = 0.0;
+      if (j > i) dn.chol[(size_t)i * Dp + j] = 0.0;
+    }
+  }
+  for (int e = lane; e < D; e += WAVE) wm[e] = 0.0;
+  return dense_cholesky_cold(dn.chol, dn.la, D, Dp, lane);
+}
+
 // ------------------------------------------------------------------ the chain
 // SEG: lanes per chain (64: one chain per wave; 16 / 32: 4 / 2 chains packed in a wave, each
 // in its own DPP row(s), D <= SEG).  `lane` is the lane's position inside its segment.
-template <int NCH, int SEG = WAVE, bool FM = false, int UT = -1, bool ZP = false>
+template <int NCH, int SEG = WAVE, bool FM = false, int UT = -1, bool ZP = false, bool DENSE = false>
+// DENSE: dense_e -- the metric is the chain's full M^-1 (DenseRefs) instead of the vector V_IM:
+// p_sharp = M^-1 p by dense_matvec_cold (psh, refreshed whenever p changes), momenta by
+// dense_backsolve_cold, the windows by dense_window_cold.  Split mode only (k_nuts_step).
 // UT: the U-turn criterion at compile time (0: Stan 2.19, 1: Stan >= 2.23's junction checks; -1: at
 // run time from A.uturn_ext) -- a run-time branch on it splits the merge loop's basic block
 // (every member is force-inlined: a non-inlined constructor or method receiving `this` puts
@@ -336,6 +578,9 @@ struct NutsChain {
   double s[S_COUNT];
   int iv[I_COUNT];
   double q[NCH], p[NCH], g[NCH], im[NCH];
+  DenseRefs dn{};                 // DENSE: the chain's matrices and LDS vectors
+  double psh[DENSE ? NCH : 1];    // DENSE: M^-1 p of the current p
+  bool dense_fail = false;        // DENSE: the window-end factorisation failed
   const double* mt = nullptr;     // FM: the fused kernel's exp / log1p table in LDS (else ocml)
   MtK mk{};                       // FM: its constants, VGPR-resident (mt_consts)
   __device__ __forceinline__ double ex(double x) const {
@@ -506,7 +751,7 @@ struct NutsChain {
     vld(V_Q, q);
     vld(V_P, p);
     vld(V_G, g);
-    vld(V_IM, im);
+    if constexpr (!DENSE) vld(V_IM, im);
   }
   __device__ __forceinline__ void flush_counts() {
     if (lane == 0 && (nleap | ndiv)) {
@@ -529,8 +774,24 @@ struct NutsChain {
     vst(V_G, g);
   }
 
+  // DENSE: psh = M^-1 p through the chain's LDS vectors (p zero past D)
+  __device__ __forceinline__ void sharp() {
+    if constexpr (DENSE) {
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) dn.la[k * SEG + lane] = ok(k) ? p[k] : 0.0;
+      dense_matvec_cold<NCH>(dn.minv, dn.la, dn.lb, D, A.Dp, lane);
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) psh[k] = ok(k) ? dn.lb[k * SEG + lane] : 0.0;
+    }
+  }
   __device__ __forceinline__ double kinetic(const double (&pp)[NCH]) const {   // diag_e_metric::tau
     double t = 0.0;
+    if constexpr (DENSE) {   // dense_e_metric::tau of the current p (pp is p: psh is its M^-1 p)
+#pragma unroll
+      for (int k = 0; k < NCH; ++k)
+        if (ok(k)) t += pp[k] * psh[k];
+      return 0.5 * seg_sum<SEG>(t);
+    }
 #pragma unroll
     for (int k = 0; k < NCH; ++k)
       if (okv(k)) t += pp[k] * im[k] * pp[k];
@@ -585,6 +846,18 @@ struct NutsChain {
     return u53((k & 1) ? r.b : r.a);
   }
   __device__ __forceinline__ void sample_momentum(uint32_t c1, uint32_t c2hi, uint32_t tag) {
+    if constexpr (DENSE) {   // the diagonal path's normals z (im = 1), then p = L^-T z
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) {
+        const int e = k * SEG + lane;
+        dn.la[e] = ok(k) ? momentum_cold(A.seed, rid, c1, c2hi, (uint32_t)e, tag, 1.0) : 0.0;
+      }
+      dense_backsolve_cold(dn.chol, dn.la, D, A.Dp, lane);
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) p[k] = ok(k) ? dn.la[k * SEG + lane] : 0.0;
+      sharp();
+      return;
+    }
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
       const int e = k * SEG + lane;
@@ -601,6 +874,14 @@ struct NutsChain {
   __device__ __forceinline__ void begin_leapfrog(double eps) {
     S(S_LFEPS) = eps;
     const double he = 0.5 * eps;
+    if constexpr (DENSE) {
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) p[k] -= he * g[k];
+      sharp();
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) q[k] += eps * psh[k];
+      return;
+    }
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
       p[k] -= he * g[k];
@@ -615,6 +896,7 @@ struct NutsChain {
       g[k] = -glp[k];
       p[k] -= he * g[k];
     }
+    sharp();
   }
 
   // ---- init_stepsize (base_hmc) as a probe sequence, one leapfrog per step
@@ -639,10 +921,25 @@ struct NutsChain {
     S(S_XBAR) = r.xbar;
     S(S_NOMEPS) = r.nomeps;
   }
+  // windowed_adaptation::compute_next_window, at the end of the window that closes with draw cnt
+  __device__ __forceinline__ void compute_next_window(unsigned cnt, unsigned nw) {
+    const unsigned last = nw - A.term_buffer - 1;
+    if ((unsigned)IV(I_WNEXT) != last) {
+      unsigned size = (unsigned)IV(I_WSIZE) * 2;
+      unsigned next = cnt + size;
+      if (next != last) {
+        const unsigned nb = next + 2 * size;
+        if (nb >= nw - A.term_buffer) next = last;
+      }
+      IV(I_WSIZE) = (int)size;
+      IV(I_WNEXT) = (int)next;
+    }
+  }
   __device__ __forceinline__ bool learn_variance() {
     const unsigned cnt = (unsigned)IV(I_WCNT);
     const unsigned nw = (unsigned)A.num_warmup;
     const bool in_window = (cnt >= A.init_buffer) && (cnt < nw - A.term_buffer) && (cnt != nw);
+    if constexpr (DENSE) return learn_covariance(cnt, nw, in_window);
     double wm[NCH], wm2[NCH];
     vld(V_WM, wm);
     vld(V_WM2, wm2);
@@ -659,18 +956,7 @@ struct NutsChain {
     }
     const bool end_window = (cnt == (unsigned)IV(I_WNEXT)) && (cnt != nw);
     if (end_window) {
-      // compute_next_window
-      const unsigned last = nw - A.term_buffer - 1;
-      if ((unsigned)IV(I_WNEXT) != last) {
-        unsigned size = (unsigned)IV(I_WSIZE) * 2;
-        unsigned next = cnt + size;
-        if (next != last) {
-          const unsigned nb = next + 2 * size;
-          if (nb >= nw - A.term_buffer) next = last;
-        }
-        IV(I_WSIZE) = (int)size;
-        IV(I_WNEXT) = (int)next;
-      }
+      compute_next_window(cnt, nw);
       const double n = S(S_WFN);
 #pragma unroll
       for (int k = 0; k < NCH; ++k) {
@@ -685,6 +971,18 @@ struct NutsChain {
     }
     vst(V_WM, wm);
     vst(V_WM2, wm2);
+    IV(I_WCNT) = (int)(cnt + 1);
+    return end_window;
+  }
+  // DENSE: covar_adaptation on the same window schedule; the matrices are updated in place by
+  // dense_window_cold (the Welford mean stays in V_WM)
+  __device__ __forceinline__ bool learn_covariance(unsigned cnt, unsigned nw, bool in_window) {
+    if (in_window) S(S_WFN) += 1.0;
+    const bool end_window = (cnt == (unsigned)IV(I_WNEXT)) && (cnt != nw);
+    if (end_window) compute_next_window(cnt, nw);
+    if (in_window || end_window)
+      dense_fail = dense_window_cold(dn, vp(V_QS), vp(V_WM), D, A.Dp, lane, S(S_WFN), in_window, end_window) != 0;
+    if (end_window) S(S_WFN) = 0.0;
     IV(I_WCNT) = (int)(cnt + 1);
     return end_window;
   }
@@ -719,7 +1017,10 @@ struct NutsChain {
     S(S_VB) = S(S_V);
     double ps[NCH];
 #pragma unroll
-    for (int k = 0; k < NCH; ++k) ps[k] = im[k] * p[k];
+    for (int k = 0; k < NCH; ++k) {
+      if constexpr (DENSE) ps[k] = psh[k];
+      else ps[k] = im[k] * p[k];
+    }
     vst(V_PSP, ps);
     vst(V_PSM, ps);
     vst(V_RHO, p);
@@ -773,6 +1074,12 @@ struct NutsChain {
       if (A.var_on) update = learn_variance();
     }
     IV(I_ITER) = it + 1;
+    if constexpr (DENSE) {
+      if (dense_fail) {   // the new metric is not positive definite: the chain stops, as on a step-size error
+        IV(I_MODE) = M_ERROR;
+        return false;
+      }
+    }
     if (update) {
       IV(I_SSREASON) = (A.adapt && it + 1 == A.num_warmup) ? 2 : 1;
       if (start_probe()) return true;
@@ -845,7 +1152,8 @@ struct NutsChain {
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
       c_rho[k] = p[k];
-      c_psb[k] = im[k] * p[k];
+      if constexpr (DENSE) c_psb[k] = psh[k];
+      else c_psb[k] = im[k] * p[k];
       c_pse[k] = c_psb[k];
       c_q[k] = q[k];
       c_g[k] = g[k];
@@ -1069,7 +1377,7 @@ struct NutsChain {
 };
 
 // ------------------------------------------------------------------ kernels
-#ifndef STK_NUTS_FUSED4_TU
+#if !defined(STK_NUTS_FUSED4_TU) && !defined(STK_NUTS_DENSE_TU)
 __global__ __launch_bounds__(64) void k_nuts_init(NutsArgs A, const double* init, const double* inv_metric,
                                                   double stepsize, double init_radius) {
   const int gid = blockIdx.x, lane = threadIdx.x;
@@ -1109,11 +1417,20 @@ __global__ __launch_bounds__(64) void k_nuts_init(NutsArgs A, const double* init
   }
 }
 
-#endif  // STK_NUTS_FUSED4_TU
-template <int NCH>
+#endif  // the main translation unit
+template <int NCH, bool DENSE = false>
 __global__ __launch_bounds__(64) void k_nuts_step(NutsArgs A, int step_id, int pause_at) {
   const int gid = blockIdx.x, lane = threadIdx.x;
-  NutsChain<NCH> ch(A, gid, lane);
+  NutsChain<NCH, WAVE, false, -1, false, DENSE> ch(A, gid, lane);
+  if constexpr (DENSE) {
+    __shared__ double dense_lds[2 * NCH * WAVE];
+    const size_t mat = (size_t)A.Dp * A.Dp;
+    ch.dn.minv = A.d_minv + (size_t)gid * mat;
+    ch.dn.chol = A.d_chol + (size_t)gid * mat;
+    ch.dn.m2 = A.d_m2 + (size_t)gid * mat;
+    ch.dn.la = dense_lds;
+    ch.dn.lb = dense_lds + NCH * WAVE;
+  }
   ch.load();
   const int mode = ch.IV(I_MODE);
   if (mode == M_DONE || mode == M_ERROR) return;
@@ -1255,10 +1572,51 @@ __global__ __launch_bounds__(64) void k_schools_lpgrad(const ShardDev* shards, i
   if (lane == 0) lp[c] = v;
 }
 
+#ifdef STK_NUTS_DENSE_TU
+// Every chain's M^-1 and L from one [Dp][Dp] pair (NULL: the identity), M2 zeroed.
+__global__ __launch_bounds__(256) void k_dense_init(NutsArgs A, const double* minv0, const double* chol0) {
+  const size_t mat = (size_t)A.Dp * A.Dp, total = (size_t)A.nchains * mat;
+  const int D = A.shards[0].D;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = i % mat;
+    const int r = (int)(e / A.Dp), c = (int)(e % A.Dp);
+    const double id = (r == c && r < D) ? 1.0 : 0.0;
+    A.d_minv[i] = minv0 ? minv0[e] : id;
+    A.d_chol[i] = chol0 ? chol0[e] : id;
+    A.d_m2[i] = 0.0;
+  }
+}
+#endif
+
 }  // namespace stk
 
 // ------------------------------------------------------------------ launchers
 using namespace stk;
+
+#ifdef STK_NUTS_DENSE_TU
+// The dense_e instantiations of k_nuts_step live in their own translation unit, nuts_dense.hip
+// (this file with STK_NUTS_DENSE_TU), so the diagonal instantiations compile as before.
+hipError_t stk_launch_dense_init(const NutsArgs& A, const double* minv0, const double* chol0, hipStream_t st) {
+  const size_t total = (size_t)A.nchains * A.Dp * A.Dp;
+  const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_dense_init, dim3(blocks), dim3(256), 0, st, A, minv0, chol0);
+  return hipGetLastError();
+}
+template <int NCH>
+static hipError_t launch_step_dense_t(const NutsArgs& A, int step_id, int pause_at, hipStream_t st) {
+  hipLaunchKernelGGL((k_nuts_step<NCH, true>), dim3(A.nchains), dim3(64), 0, st, A, step_id, pause_at);
+  return hipGetLastError();
+}
+hipError_t stk_launch_nuts_step_dense(const NutsArgs& A, int nch, int step_id, int pause_at, hipStream_t st) {
+  switch (nch) {
+    case 1: return launch_step_dense_t<1>(A, step_id, pause_at, st);
+    case 2: return launch_step_dense_t<2>(A, step_id, pause_at, st);
+    case 4: return launch_step_dense_t<4>(A, step_id, pause_at, st);
+    case 16: return launch_step_dense_t<16>(A, step_id, pause_at, st);
+  }
+  return hipErrorInvalidValue;
+}
+#else
 
 template <int NCH>
 static hipError_t launch_step_t(const NutsArgs& A, int step_id, int pause_at, hipStream_t st) {
@@ -1374,3 +1732,4 @@ hipError_t stk_launch_schools_lpgrad(const ShardDev* shards, int shard, int nch,
   return hipGetLastError();
 }
 #endif  // STK_NUTS_FUSED4_TU
+#endif  // STK_NUTS_DENSE_TU

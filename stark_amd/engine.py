@@ -36,6 +36,7 @@ def _shutdown():
                 pass
     _finalized = True
 FAMILY_NAMES = {v: k for k, v in FAMILIES.items()}
+METRICS = {"diag_e": 0, "dense_e": 1, "unit_e": 2}
 
 
 def _ptr(a):
@@ -122,11 +123,25 @@ def make_config(num_warmup=1000, num_samples=1000, chains=1, max_depth=10, adapt
                 adapt_kappa=0.75, adapt_t0=10.0, stepsize=1.0, init_radius=2.0, adapt_init_buffer=75,
                 adapt_term_buffer=50, adapt_window=25, adapt_engaged=True, seed=1234, init=None,
                 inv_metric=None, skip_init_stepsize=False, iter_offset=0, shard_ids=None,
-                save_warmup=False, stepsize_jitter=0.0, nuts_criterion="stan2.19", chains_per_wave=0):
+                save_warmup=False, stepsize_jitter=0.0, nuts_criterion="stan2.19", chains_per_wave=0,
+                metric="diag_e"):
     """Stan sampler settings (pystan 2 `sampling()` keywords + control block).
+    metric: "diag_e" (default; inv_metric is a vector of D), "dense_e" (regression families;
+    inv_metric is a symmetric positive definite D x D matrix) or "unit_e" (no inv_metric).
     nuts_criterion: "stan2.19" (the reference's pystan 2: one U-turn test per merged subtree)
     or "stan2.23" (plus the checks across subtree junctions of Stan >= 2.23)."""
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {sorted(METRICS)}, got {metric!r}")
+    if inv_metric is not None:
+        inv_metric = np.ascontiguousarray(inv_metric, np.float64)
+        if metric == "unit_e":
+            raise ValueError("metric='unit_e' takes no inv_metric")
+        if metric == "dense_e" and (inv_metric.ndim != 2 or inv_metric.shape[0] != inv_metric.shape[1]):
+            raise ValueError(f"metric='dense_e' needs a square 2-D inv_metric, got shape {inv_metric.shape}")
+        if metric == "diag_e" and inv_metric.ndim != 1:
+            raise ValueError(f"metric='diag_e' needs a 1-D inv_metric, got shape {inv_metric.shape}")
     c = _lib.default_config()
+    c.metric = METRICS[metric]
     c.num_warmup, c.num_samples, c.chains, c.max_depth = int(num_warmup), int(num_samples), int(chains), int(max_depth)
     c.adapt_delta, c.adapt_gamma, c.adapt_kappa, c.adapt_t0 = adapt_delta, adapt_gamma, adapt_kappa, adapt_t0
     c.stepsize, c.init_radius = stepsize, init_radius
@@ -145,9 +160,11 @@ def make_config(num_warmup=1000, num_samples=1000, chains=1, max_depth=10, adapt
         keep.append(init)
         c.init = init.ctypes.data
     if inv_metric is not None:
-        inv_metric = np.ascontiguousarray(inv_metric, np.float64)
         keep.append(inv_metric)
-        c.inv_metric = inv_metric.ctypes.data
+        if metric == "dense_e":
+            c.inv_metric_dense = inv_metric.ctypes.data
+        else:
+            c.inv_metric = inv_metric.ctypes.data
     if shard_ids is not None:
         shard_ids = np.ascontiguousarray(shard_ids, np.int32)
         keep.append(shard_ids)
@@ -296,12 +313,21 @@ class Model:
             s.close()
 
     def transition(self, shard, q, *, seed, iteration, eps, inv_metric=None, max_depth=10):
-        """One fixed-step NUTS transition per row of q (parity hook, see stk_transition)."""
+        """One fixed-step NUTS transition per row of q (parity hook, see stk_transition).
+        inv_metric: None (unit), a vector of D (diagonal) or a D x D matrix (dense, stk_transition_dense)."""
         q = np.array(np.atleast_2d(q), np.float64, copy=True, order="C")
         C = q.shape[0]
         lp = np.empty(C)
         st = np.empty((C, N_STATS))
         im = None if inv_metric is None else np.ascontiguousarray(inv_metric, np.float64)
+        D = self.D[shard]
+        if im is not None and im.shape not in ((D,), (D, D)):
+            raise ValueError(f"inv_metric has shape {im.shape}, shard {shard} needs ({D},) or ({D}, {D})")
+        if im is not None and im.ndim == 2:
+            check(_lib.load().stk_transition_dense(self._h, shard, q.ctypes.data, C, int(seed), int(iteration),
+                                                   float(eps), _ptr(im), int(max_depth), lp.ctypes.data,
+                                                   st.ctypes.data))
+            return q, lp, st
         check(_lib.load().stk_transition(self._h, shard, q.ctypes.data, C, int(seed), int(iteration), float(eps),
                                          _ptr(im), int(max_depth), lp.ctypes.data, st.ctypes.data))
         return q, lp, st
@@ -325,6 +351,13 @@ class Sampler:
         self.model = model
         self.cfg = cfg
         h = ctypes.c_void_p()
+        for name, im in (("inv_metric", cfg.inv_metric), ("inv_metric_dense", cfg.inv_metric_dense)):
+            if im:   # the C side reads max(D) (squared) doubles: a host array of another shape is refused here
+                D = max(model.D)
+                want = (D, D) if name == "inv_metric_dense" else (D,)
+                held = [a for a in getattr(cfg, "_keep", []) if a.ctypes.data == im]
+                if held and held[0].shape != want:
+                    raise ValueError(f"inv_metric has shape {held[0].shape}, the model needs {want}")
         check(_lib.load().stk_sampler_create(model._h, ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h
         self.total = cfg.num_warmup + cfg.num_samples
@@ -415,8 +448,14 @@ class Sampler:
         return out
 
     def adaptation(self):
+        """Every chain's step size and inverse metric: (nchains, D), or (nchains, D, D) under dense_e."""
         n = self.model.nshards * self.cfg.chains
         eps = np.empty(n)
+        if self.cfg.metric == METRICS["dense_e"]:
+            D = max(self.model.D)
+            im = np.zeros((n, D, D))
+            check(_lib.load().stk_sampler_adaptation_dense(self._h, eps.ctypes.data, im.ctypes.data))
+            return eps, im
         im = np.zeros((n, max(self.model.D)))
         check(_lib.load().stk_sampler_adaptation(self._h, eps.ctypes.data, im.ctypes.data))
         return eps, im

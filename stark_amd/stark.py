@@ -138,9 +138,10 @@ def sampling_config(family, datas, **kw):
     if seed is None:
         seed = int(np.random.SeedSequence().entropy) & 0x7FFFFFFF
     control = dict(kw.pop("control", None) or {})
-    if control.pop("metric", "diag_e") != "diag_e":
-        raise NotImplementedError("only metric='diag_e' (Stan's default) is supported")
-    cfg = dict(num_warmup=warmup, num_samples=it - warmup, chains=chains, seed=seed, thin=thin)
+    metric = control.pop("metric", "diag_e")
+    if metric not in engine.METRICS:
+        raise ValueError(f"control['metric'] must be one of {sorted(engine.METRICS)}, got {metric!r}")
+    cfg = dict(num_warmup=warmup, num_samples=it - warmup, chains=chains, seed=seed, thin=thin, metric=metric)
     for k, v in control.items():
         if k not in _CONTROL_KEYS:
             raise ValueError(f"unknown control key {k!r}")
@@ -239,6 +240,7 @@ class Stark:
         if thin > 1:   # last_run holds what the caller got: the thinned draws and their stats
             idx = thin_draws(np.arange(res.chains * res.num_samples)[None, :], res.chains, thin)[0]
             res = engine.SampleResult(draws, [st[idx] for st in res.stats], res.info, res.chains, len(idx) // res.chains)
+        res.info["metric"] = cfg["metric"]
         self.last_run = res
         if not permuted:
             return draws
