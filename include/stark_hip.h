@@ -203,6 +203,10 @@ STK_API int stk_sampler_adaptation(stk_sampler* s, double* stepsize, double* inv
 /* The same for a dense_e sampler: inv_metric is [nshards * chains][D][D] row-major, every matrix
  * symmetric to the bit.  STK_E_ARG for another metric. */
 STK_API int stk_sampler_adaptation_dense(stk_sampler* s, double* stepsize, double* inv_metric);
+/* A dense_e sampler's Cholesky factors, M^-1 = L L^T: chol is [nshards * chains][D][D] row-major, every
+ * L lower triangular (the upper triangle is zero).  Read-only: the factor the momenta are drawn with.
+ * STK_E_ARG for another metric. */
+STK_API int stk_sampler_metric_factor_dense(stk_sampler* s, double* chol);
 /* Transitions completed so far by every chain (nshards * chains, shard-major). */
 STK_API int stk_sampler_iterations(stk_sampler* s, int32_t* iters);
 STK_API int stk_sampler_destroy(stk_sampler* s);

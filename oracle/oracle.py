@@ -7,7 +7,10 @@ library instead of falling back here.
 
 Contents
   * ctypes bindings to ``oracle/_build/liboracle.so`` (``stark_oracle.c``): Philox, the
-    synthetic generator, the three log densities + gradients, the Stan 2.19 NUTS twin.
+    synthetic generator, the three log densities + gradients, the Stan 2.19 NUTS twin under a
+    diagonal, a dense (``inv_metric`` 2-D / ``metric="dense_e"``) or the unit metric.
+  * ``self_replay``: does the oracle replay its own transitions from starts moved by 1e-13
+    relative?  The precondition of every replay test at the project's bars.
   * ``consensus_avg_ref`` / ``consensus_combine_ref``: numpy restatement of the
     reference's combine (``stark/stark.py:7-21`` pairwise reducer and the driver solve
     ``stark/stark.py:66-70``), pinned against golden fixtures produced by importing the
@@ -70,6 +73,10 @@ def lib():
         L.orc_run_chain.restype = ctypes.c_long
         L.orc_transition.argtypes = [ctypes.c_void_p, u64, u32, u32, ci, ctypes.c_double, dp, dp, dp, dp, ci]
         L.orc_transition.restype = ctypes.c_long
+        L.orc_transition_dense.argtypes = [ctypes.c_void_p, u64, u32, u32, ci, ctypes.c_double, dp, dp, dp, dp, dp, ci]
+        L.orc_transition_dense.restype = ctypes.c_long
+        L.orc_cholesky.argtypes = [dp, ci, dp]
+        L.orc_cholesky.restype = ci
         L.orc_logreg_grad_loop.argtypes = [i64, ci, dp, i32p, dp, dp, ci]
         L.orc_logreg_grad_loop.restype = ctypes.c_double
         _lib = L
@@ -136,7 +143,19 @@ class _Cfg(ctypes.Structure):
                 ("t0", ctypes.c_double), ("stepsize", ctypes.c_double), ("init_radius", ctypes.c_double),
                 ("init_buffer", ctypes.c_int), ("term_buffer", ctypes.c_int), ("window", ctypes.c_int),
                 ("adapt_engaged", ctypes.c_int), ("seed", ctypes.c_uint64), ("stepsize_jitter", ctypes.c_double),
-                ("uturn_ext", ctypes.c_int)]
+                ("uturn_ext", ctypes.c_int), ("metric", ctypes.c_int), ("inv_metric_dense", ctypes.c_void_p)]
+
+
+METRICS = {"diag_e": 0, "dense_e": 1, "unit_e": 2}
+
+
+def cholesky(a):
+    """The oracle's own textbook Cholesky of a symmetric positive definite matrix (lower factor)."""
+    a = np.ascontiguousarray(a, np.float64)
+    out = np.empty_like(a)
+    if lib().orc_cholesky(_dp(a), a.shape[0], _dp(out)) < 0:
+        raise ValueError("oracle: the matrix is not positive definite")
+    return out
 
 
 class Model:
@@ -185,28 +204,51 @@ class Model:
     def run_chain(self, *, num_warmup=1000, num_samples=1000, max_depth=10, adapt_delta=0.8,
                   gamma=0.05, kappa=0.75, t0=10.0, stepsize=1.0, init_radius=2.0,
                   init_buffer=75, term_buffer=50, window=25, adapt_engaged=True, seed=1234,
-                  gid=0, init=None, stepsize_jitter=0.0, uturn_ext=False):
-        """uturn_ext: Stan >= 2.23's extra U-turn checks between subtrees (default: Stan 2.19)."""
+                  gid=0, init=None, stepsize_jitter=0.0, uturn_ext=False, metric="diag_e", inv_metric=None):
+        """uturn_ext: Stan >= 2.23's extra U-turn checks between subtrees (default: Stan 2.19).
+        metric: "diag_e", "dense_e" (covar_adaptation; inv_metric: None or the D x D initial M^-1; the
+        returned inv_metric is D x D) or "unit_e" (only the step size adapts)."""
+        dense = metric == "dense_e"
+        im0 = None
+        if inv_metric is not None:
+            if not dense:
+                raise ValueError("run_chain: inv_metric is the dense_e initial matrix")
+            im0 = np.ascontiguousarray(inv_metric, np.float64)
+            if im0.shape != (self.D, self.D):
+                raise ValueError(f"inv_metric has shape {im0.shape}, the model needs {(self.D, self.D)}")
         cfg = _Cfg(num_warmup, num_samples, max_depth, adapt_delta, gamma, kappa, t0, stepsize,
                    init_radius, init_buffer, term_buffer, window, int(adapt_engaged), seed, stepsize_jitter,
-                   int(bool(uturn_ext)))
+                   int(bool(uturn_ext)), METRICS[metric], im0.ctypes.data if im0 is not None else None)
         T = num_warmup + num_samples
         q = np.empty((T, self.D))
         lp = np.empty(T)
         st = np.empty((T, 6))
-        fin = np.empty(self.D + 1)
+        fin = np.empty(self.D * self.D + 1 if dense else self.D + 1)
         init_a = None if init is None else np.ascontiguousarray(init, np.float64)
         ng = lib().orc_run_chain(ctypes.byref(self._s), ctypes.byref(cfg), gid, _dp(init_a),
                                  _dp(q), _dp(lp), _dp(st), _dp(fin))
         if ng < 0:
-            raise RuntimeError("oracle: step size left (0, 1e7]")
-        return dict(q=q, lp=lp, stats=st, stepsize=fin[0], inv_metric=fin[1:], n_grad=ng)
+            raise RuntimeError("oracle: step size left (0, 1e7]" + (" or a metric is not positive definite" * dense))
+        im = fin[1:].reshape(self.D, self.D) if dense else fin[1:]
+        return dict(q=q, lp=lp, stats=st, stepsize=fin[0], inv_metric=im, n_grad=ng)
 
-    def transition(self, q, *, seed, gid, iteration, eps, inv_metric=None, max_depth=10, uturn_ext=False):
+    def transition(self, q, *, seed, gid, iteration, eps, inv_metric=None, max_depth=10, uturn_ext=False,
+                   factor=None):
+        """inv_metric: None (unit), a vector of D (diag_e) or a D x D matrix (dense_e, orc_transition_dense).
+        factor: cholesky(inv_metric), for many transitions under one dense metric (else factored per call)."""
         q = np.array(q, np.float64, copy=True)
         im = np.ones(self.D) if inv_metric is None else np.ascontiguousarray(inv_metric, np.float64)
         lp = ctypes.c_double()
         st = np.empty(6)
+        if im.ndim == 2:
+            if im.shape != (self.D, self.D):
+                raise ValueError(f"inv_metric has shape {im.shape}, the model needs {(self.D, self.D)}")
+            ch = None if factor is None else np.ascontiguousarray(factor, np.float64)
+            ng = lib().orc_transition_dense(ctypes.byref(self._s), seed, gid, iteration, max_depth, eps, _dp(im),
+                                            _dp(ch), _dp(q), ctypes.byref(lp), _dp(st), int(bool(uturn_ext)))
+            if ng < 0:
+                raise ValueError("oracle: inv_metric is not positive definite")
+            return q, lp.value, st, ng
         ng = lib().orc_transition(ctypes.byref(self._s), seed, gid, iteration, max_depth, eps,
                                   _dp(im), _dp(q), ctypes.byref(lp), _dp(st), int(bool(uturn_ext)))
         return q, lp.value, st, ng
@@ -338,3 +380,45 @@ def linreg_exact_moments(X, y):
     s2 = rss / nu
     cov = (nu / (nu - 2.0)) * s2 * np.linalg.inv(xtx)
     return mean, cov
+
+
+# ------------------------------------------------------------- replay bars and self-replay
+def over_bar(a, b, rtol, atol):
+    """Largest |a - b| / (atol + rtol |b|) (0 where equal to the bit, inf on a NaN)."""
+    a, b = np.atleast_1d(np.asarray(a, float)), np.atleast_1d(np.asarray(b, float))
+    with np.errstate(invalid="ignore"):
+        r = np.where(a == b, 0.0, np.abs(a - b) / (atol + rtol * np.abs(b)))
+    return float(np.where(np.isnan(r), np.inf, r).max())
+
+
+def replay_errors(got, want):
+    """(q, lp, stats) of one transition against the reference's: (discrete stats differ, the largest
+    error in units of the project's replay bars: q rtol 1e-8 / atol 1e-10, lp 1e-9 relative,
+    accept_stat and energy rtol 1e-9 / atol 1e-12)."""
+    q, lp, st = got[:3]
+    oq, olp, ost = want[:3]
+    flip = not np.array_equal(np.asarray(st)[2:5], np.asarray(ost)[2:5])
+    worst = max(over_bar(q, oq, 1e-8, 1e-10), over_bar(lp, olp, 0.0, 1e-9 * max(1.0, abs(olp))),
+                over_bar(np.asarray(st)[[0, 5]], np.asarray(ost)[[0, 5]], 1e-9, 1e-12))
+    return flip, worst
+
+
+def self_replay(model, starts, want=None, rel=1e-13, **kw):
+    """Does the oracle replay ITSELF?  Every transition of `starts` (a list of (q0, gid, iteration, eps))
+    is run again from q0 (1 + rel r), r = +-1 per coordinate (fixed generator), and compared with the
+    unperturbed one (`want`, computed here if None) in units of the replay bars.  A replay test of
+    another implementation at the bars is only meaningful where this reports no flipped discrete
+    stat and a small fraction of the bar: elsewhere the trajectory amplifies rounding differences
+    beyond them.  kw goes to Model.transition (seed, inv_metric, factor, max_depth, ...).
+    Returns (flipped, worst error over the bar)."""
+    rng = np.random.default_rng(20191)
+    flips, worst = 0, 0.0
+    for k, (q0, gid, it, eps) in enumerate(starts):
+        q0 = np.asarray(q0, np.float64)
+        w = want[k] if want is not None else model.transition(q0, gid=gid, iteration=it, eps=eps, **kw)
+        r = rng.choice([-1.0, 1.0], q0.shape)
+        g = model.transition(q0 * (1.0 + rel * r), gid=gid, iteration=it, eps=eps, **kw)
+        f, e = replay_errors(g, w)
+        flips += int(f)
+        worst = max(worst, e)
+    return flips, worst

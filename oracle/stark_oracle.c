@@ -14,6 +14,9 @@
  *     sampling, biased progressive top level, generalized U-turn on rho / p_sharp),
  *     expl_leapfrog, diag_e_metric, stepsize_adaptation (Nesterov dual averaging),
  *     windowed_adaptation + var_adaptation + welford_var_estimator, base_hmc::init_stepsize.
+ *     Next to the diagonal code, behind a metric selector: dense_e_metric (tau, dtau_dp, sample_p
+ *     through an own textbook Cholesky, no BLAS / LAPACK) and covar_adaptation +
+ *     welford_covar_estimator (hmc_nuts_dense_e_adapt), and unit_e (the step size alone adapts).
  *     Stan is not vendored under /root/reference and cannot be installed here, so the
  *     sampler is "parity unpinned" at the Stan boundary; it is
  *     pinned by exact posterior moments (tests) and by the GPU/CPU trajectory check.
@@ -289,6 +292,8 @@ typedef struct {
   uint64_t seed;
   double stepsize_jitter;
   int uturn_ext;      /* 0: Stan 2.19 single criterion; 1: + the checks between subtrees (Stan >= 2.23) */
+  int metric;         /* 0: diag_e; 1: dense_e (hmc_nuts_dense_e_adapt); 2: unit_e (step size only) */
+  const double* inv_metric_dense;   /* dense_e: NULL (identity) or the D x D row-major initial M^-1 */
 } orc_cfg;
 
 typedef struct {
@@ -312,7 +317,13 @@ typedef struct {
   unsigned win_counter, win_size, next_window;
   double wf_n; double* wf_m; double* wf_m2;
   uint32_t ss_call;
+  /* dense_e (metric == METRIC_DENSE): the D x D row-major M^-1, its Cholesky factor L (lower,
+   * M^-1 = L L^T), the Welford M2 of covar_adaptation and a work vector; inv_metric is unused */
+  int metric;
+  double* minv; double* chol; double* wf_c2; double* work;
 } nuts;
+
+enum { METRIC_DIAG = 0, METRIC_DENSE = 1, METRIC_UNIT = 2 };
 
 static double* dalloc(int n) { return (double*)calloc((size_t)(n > 0 ? n : 1), sizeof(double)); }
 static void pt_alloc(ps_point* z, int D) { z->q = dalloc(D); z->p = dalloc(D); z->g = dalloc(D); z->V = 0; z->H = 0; }
@@ -335,7 +346,56 @@ static void update_potential_gradient(nuts* s, ps_point* z) {
   s->n_grad++;
 }
 
+/* ---- dense_e_metric (Stan 2.19.1): plain sequential loops over the full matrix ---- */
+/* Textbook Cholesky (Cholesky-Banachiewicz, row by row) of the lower triangle of the D x D
+ * row-major A: L lower with A = L L^T, the upper triangle of L zero.  Returns -1 on a
+ * non-positive or NaN pivot. */
+int orc_cholesky(const double* A, int D, double* L) {
+  for (int i = 0; i < D; ++i) {
+    for (int j = 0; j <= i; ++j) {
+      double acc = A[(size_t)i * D + j];
+      for (int k = 0; k < j; ++k) acc -= L[(size_t)i * D + k] * L[(size_t)j * D + k];
+      if (j < i) L[(size_t)i * D + j] = acc / L[(size_t)j * D + j];
+      else {
+        if (!(acc > 0.0)) return -1;
+        L[(size_t)i * D + i] = sqrt(acc);
+      }
+    }
+    for (int j = i + 1; j < D; ++j) L[(size_t)i * D + j] = 0.0;
+  }
+  return 0;
+}
+
+static void dense_dtau_dp(const nuts* s, const double* p, double* out) {   /* M^-1 p */
+  int D = s->D;
+  for (int i = 0; i < D; ++i) {
+    const double* row = s->minv + (size_t)i * D;
+    double acc = 0.0;
+    for (int j = 0; j < D; ++j) acc += row[j] * p[j];
+    out[i] = acc;
+  }
+}
+
+static double dense_tau(const nuts* s, const double* p) {     /* 0.5 p^T M^-1 p */
+  dense_dtau_dp(s, p, s->work);
+  double t = 0.0;
+  for (int i = 0; i < s->D; ++i) t += p[i] * s->work[i];
+  return 0.5 * t;
+}
+
+/* dense_e_metric::sample_p: p = llt(M^-1).matrixU().solve(u) = L^-T u, by back-substitution. */
+static void dense_sample_p(nuts* s, double* p, uint32_t c1, uint32_t c2hi, uint32_t tag) {
+  int D = s->D;
+  for (int i = 0; i < D; ++i) p[i] = orc_normal(s->seed, s->gid, c1, c2hi, (uint32_t)i, tag);
+  for (int i = D - 1; i >= 0; --i) {
+    double acc = p[i];
+    for (int j = i + 1; j < D; ++j) acc -= s->chol[(size_t)j * D + i] * p[j];
+    p[i] = acc / s->chol[(size_t)i * D + i];
+  }
+}
+
 static double tau_kin(const nuts* s, const ps_point* z) {   /* diag_e_metric::tau */
+  if (s->metric == METRIC_DENSE) return dense_tau(s, z->p);
   double t = 0.0;
   for (int i = 0; i < s->D; ++i) t += z->p[i] * s->inv_metric[i] * z->p[i];
   return 0.5 * t;
@@ -343,10 +403,12 @@ static double tau_kin(const nuts* s, const ps_point* z) {   /* diag_e_metric::ta
 static double Hfn(const nuts* s, const ps_point* z) { return z->V + tau_kin(s, z); }
 
 static void dtau_dp(const nuts* s, const ps_point* z, double* out) {
+  if (s->metric == METRIC_DENSE) { dense_dtau_dp(s, z->p, out); return; }
   for (int i = 0; i < s->D; ++i) out[i] = s->inv_metric[i] * z->p[i];
 }
 
 static void sample_p(nuts* s, ps_point* z, uint32_t c1, uint32_t c2hi, uint32_t tag) {
+  if (s->metric == METRIC_DENSE) { dense_sample_p(s, z->p, c1, c2hi, tag); return; }
   for (int i = 0; i < s->D; ++i)
     z->p[i] = orc_normal(s->seed, s->gid, c1, c2hi, (uint32_t)i, tag) / sqrt(s->inv_metric[i]);
 }
@@ -356,6 +418,10 @@ static double rand_uniform(nuts* s) { return orc_uniform(s->seed, s->gid, s->ite
 static void evolve(nuts* s, ps_point* z, double epsilon) {    /* expl_leapfrog::evolve */
   double he = 0.5 * epsilon;
   for (int i = 0; i < s->D; ++i) z->p[i] -= he * z->g[i];                      /* begin_update_p */
+  if (s->metric == METRIC_DENSE) {                                             /* update_q, dense_e */
+    dense_dtau_dp(s, z->p, s->work);
+    for (int i = 0; i < s->D; ++i) z->q[i] += epsilon * s->work[i];
+  } else
   for (int i = 0; i < s->D; ++i) z->q[i] += epsilon * (s->inv_metric[i] * z->p[i]); /* update_q */
   update_potential_gradient(s, z);
   for (int i = 0; i < s->D; ++i) z->p[i] -= he * z->g[i];                      /* end_update_p */
@@ -675,14 +741,60 @@ static int learn_variance(nuts* s, const double* q) {     /* var_adaptation::lea
   return 0;
 }
 
+/* covar_adaptation::learn_covariance (Stan 2.19.1) with welford_covar_estimator: the dense_e twin
+ * of learn_variance.  M2 += (q - m) delta^T is not symmetric in floating point; the metric is read
+ * from its lower triangle and mirrored, so that M^-1 is symmetric to the bit (the Cholesky reads
+ * only that triangle).  Returns 1 at a window's end, -1 if the new metric has a non-positive pivot. */
+static int learn_covariance(nuts* s, const double* q) {
+  int D = s->D;
+  if (adaptation_window(s)) {       /* welford_covar_estimator::add_sample */
+    s->wf_n += 1.0;
+    for (int i = 0; i < D; ++i) {
+      s->work[i] = q[i] - s->wf_m[i];                 /* delta */
+      s->wf_m[i] += s->work[i] / s->wf_n;
+    }
+    for (int i = 0; i < D; ++i) {
+      double di = q[i] - s->wf_m[i];
+      for (int j = 0; j < D; ++j) s->wf_c2[(size_t)i * D + j] += di * s->work[j];
+    }
+  }
+  if (end_adaptation_window(s)) {
+    compute_next_window(s);
+    double n = s->wf_n;
+    for (int i = 0; i < D; ++i)
+      for (int j = 0; j <= i; ++j) {
+        double v = s->minv[(size_t)i * D + j];
+        if (n > 1) v = s->wf_c2[(size_t)i * D + j] / (n - 1.0);
+        v = (n / (n + 5.0)) * v + (i == j ? 1e-3 * (5.0 / (n + 5.0)) : 0.0);
+        s->minv[(size_t)i * D + j] = v;
+        s->minv[(size_t)j * D + i] = v;
+      }
+    s->wf_n = 0; memset(s->wf_m, 0, sizeof(double) * D); memset(s->wf_c2, 0, sizeof(double) * D * D);
+    ++s->win_counter;
+    return orc_cholesky(s->minv, D, s->chol) < 0 ? -1 : 1;
+  }
+  ++s->win_counter;
+  return 0;
+}
+
+static void dense_alloc(nuts* s) {
+  size_t n = (size_t)s->D * s->D;
+  s->minv = (double*)calloc(n, sizeof(double)); s->chol = (double*)calloc(n, sizeof(double));
+  s->work = dalloc(s->D);
+}
+static void dense_free(nuts* s) { free(s->minv); free(s->chol); free(s->wf_c2); free(s->work); }
+
 /* One chain of hmc_nuts_diag_e_adapt (services/sample + util/run_adaptive_sampler).
  *   gid        global chain id (shard * chains + chain): the RNG stream key
  *   init       D unconstrained values, or NULL for uniform(-R, R)
  *   q_out      (num_warmup+num_samples) x D unconstrained draws (every transition)
  *   lp_out     (num_warmup+num_samples) lp__ values
  *   st_out     (num_warmup+num_samples) x 6 (accept, stepsize, treedepth, n_leapfrog, divergent, energy)
- *   final      1 + D: final nominal stepsize, inverse metric
- * Returns the number of gradient evaluations, or -1 on a step-size error. */
+ *   final      1 + D: final nominal stepsize, inverse metric (dense_e: 1 + D * D, the row-major matrix)
+ * cfg->metric selects diag_e / dense_e / unit_e; under dense_e the windows run covar_adaptation
+ * and under unit_e only the step size adapts.
+ * Returns the number of gradient evaluations, or -1 on a step-size error (under dense_e also
+ * when a metric has a non-positive pivot). */
 long orc_run_chain(const orc_data* m, const orc_cfg* cfg, uint32_t gid, const double* init,
                    double* q_out, double* lp_out, double* st_out, double* final) {
   nuts s; memset(&s, 0, sizeof(s));
@@ -692,6 +804,15 @@ long orc_run_chain(const orc_data* m, const orc_cfg* cfg, uint32_t gid, const do
   for (int i = 0; i < D; ++i) s.inv_metric[i] = 1.0;
   s.max_depth = cfg->max_depth; s.max_deltaH = 1000.0;
   s.wf_m = dalloc(D); s.wf_m2 = dalloc(D);
+  s.metric = cfg->metric;
+  if (s.metric == METRIC_DENSE) {
+    dense_alloc(&s);
+    s.wf_c2 = (double*)calloc((size_t)D * D, sizeof(double));
+    for (int i = 0; i < D; ++i)
+      for (int j = 0; j < D; ++j)
+        s.minv[(size_t)i * D + j] = cfg->inv_metric_dense ? cfg->inv_metric_dense[(size_t)i * D + j] : (double)(i == j);
+    if (orc_cholesky(s.minv, D, s.chol) < 0) { dense_free(&s); free(s.inv_metric); free(s.wf_m); free(s.wf_m2); return -1; }
+  }
   pt_alloc(&s.z, D);
   for (int i = 0; i < D; ++i)
     s.z.q[i] = init ? init[i] : -cfg->init_radius + 2.0 * cfg->init_radius * orc_uniform(cfg->seed, gid, 0, (uint32_t)i, TAG_INIT);
@@ -719,7 +840,11 @@ long orc_run_chain(const orc_data* m, const orc_cfg* cfg, uint32_t gid, const do
     }
     if (adapt && t < cfg->num_warmup) {
       learn_stepsize(&s, st.accept);
-      if (s.var_on && learn_variance(&s, s.z.q)) {
+      int upd = 0;
+      if (s.var_on && s.metric != METRIC_UNIT)
+        upd = s.metric == METRIC_DENSE ? learn_covariance(&s, s.z.q) : learn_variance(&s, s.z.q);
+      if (upd < 0) rc = -1;
+      if (upd > 0) {
         if (init_stepsize(&s) < 0) rc = -1;
         s.mu = log(10.0 * s.nom_eps);
         da_restart(&s);
@@ -727,8 +852,13 @@ long orc_run_chain(const orc_data* m, const orc_cfg* cfg, uint32_t gid, const do
       if (t == cfg->num_warmup - 1) s.nom_eps = exp(s.x_bar);   /* complete_adaptation */
     }
   }
-  if (final) { final[0] = s.nom_eps; memcpy(final + 1, s.inv_metric, sizeof(double) * D); }
+  if (final) {
+    final[0] = s.nom_eps;
+    if (s.metric == METRIC_DENSE) memcpy(final + 1, s.minv, sizeof(double) * D * D);
+    else memcpy(final + 1, s.inv_metric, sizeof(double) * D);
+  }
   long ng = s.n_grad;
+  if (s.metric == METRIC_DENSE) dense_free(&s);
   free(s.inv_metric); free(s.wf_m); free(s.wf_m2); pt_free(&s.z);
   return rc < 0 ? -1 : ng;
 }
@@ -753,6 +883,35 @@ long orc_transition(const orc_data* m, uint64_t seed, uint32_t gid, uint32_t ite
   if (st_out) { st_out[0] = st.accept; st_out[1] = st.eps; st_out[2] = st.depth; st_out[3] = st.n_leapfrog; st_out[4] = st.divergent; st_out[5] = st.energy; }
   long ng = s.n_grad;
   free(s.inv_metric); pt_free(&s.z);
+  return ng;
+}
+
+/* orc_transition under a dense metric (Stan's dense_e): inv_metric is the D x D row-major M^-1.
+ * chol: NULL (factored here), or orc_cholesky's factor of the same matrix, so that a caller with
+ * many transitions under one metric factors it once.  Returns -1 on a non-positive pivot. */
+long orc_transition_dense(const orc_data* m, uint64_t seed, uint32_t gid, uint32_t iter, int max_depth,
+                          double eps, const double* inv_metric, const double* chol, double* q, double* lp,
+                          double* st_out, int uturn_ext) {
+  nuts s; memset(&s, 0, sizeof(s));
+  s.m = m; s.D = orc_dim(m); s.seed = seed; s.gid = gid; s.iter = iter;
+  s.uturn_ext = uturn_ext;
+  s.metric = METRIC_DENSE;
+  int D = s.D;
+  dense_alloc(&s);
+  memcpy(s.minv, inv_metric, sizeof(double) * D * D);
+  if (chol) memcpy(s.chol, chol, sizeof(double) * D * D);
+  else if (orc_cholesky(s.minv, D, s.chol) < 0) { dense_free(&s); return -1; }
+  s.max_depth = max_depth; s.max_deltaH = 1000.0; s.nom_eps = eps;
+  pt_alloc(&s.z, D);
+  memcpy(s.z.q, q, sizeof(double) * D);
+  update_potential_gradient(&s, &s.z);
+  orc_stats st;
+  transition(&s, &st);
+  memcpy(q, s.z.q, sizeof(double) * D);
+  *lp = -s.z.V;
+  if (st_out) { st_out[0] = st.accept; st_out[1] = st.eps; st_out[2] = st.depth; st_out[3] = st.n_leapfrog; st_out[4] = st.divergent; st_out[5] = st.energy; }
+  long ng = s.n_grad;
+  dense_free(&s); pt_free(&s.z);
   return ng;
 }
 

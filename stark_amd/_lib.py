@@ -94,6 +94,7 @@ SIGNATURES = [
     ("stk_sampler_draws_unconstrained", ctypes.c_int, [_vp, ctypes.c_int, _vp]),
     ("stk_sampler_adaptation", ctypes.c_int, [_vp, _vp, _vp]),
     ("stk_sampler_adaptation_dense", ctypes.c_int, [_vp, _vp, _vp]),
+    ("stk_sampler_metric_factor_dense", ctypes.c_int, [_vp, _vp]),
     ("stk_sampler_iterations", ctypes.c_int, [_vp, _vp]),
     ("stk_sampler_destroy", ctypes.c_int, [_vp]),
     ("stk_sampler_state_bytes", ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),

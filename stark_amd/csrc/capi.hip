@@ -1078,6 +1078,19 @@ int stk_sampler_adaptation_dense(stk_sampler* s, double* stepsize, double* inv_m
   return STK_OK;
 }
 
+int stk_sampler_metric_factor_dense(stk_sampler* s, double* chol) {
+  ARG_CHECK(s && chol, "stk_sampler_metric_factor_dense: bad arguments");
+  ARG_CHECK(s->A.metric == 1, "stk_sampler_metric_factor_dense: the sampler's metric is not dense_e");
+  stk_ctx* ctx = s->m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  const size_t D = (size_t)s->m->Dmax, Dp = (size_t)s->A.Dp;
+  for (int c = 0; c < s->A.nchains; ++c)
+    STK_HIP_CHECK(hipMemcpy2DAsync(chol + (size_t)c * D * D, sizeof(double) * D, s->A.d_chol + (size_t)c * Dp * Dp,
+                                   sizeof(double) * Dp, sizeof(double) * D, D, hipMemcpyDefault, ctx->stream));
+  STK_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return STK_OK;
+}
+
 int stk_sampler_iterations(stk_sampler* s, int32_t* iters) {
   ARG_CHECK(s && iters, "stk_sampler_iterations: bad arguments");
   stk_ctx* ctx = s->m->ctx;

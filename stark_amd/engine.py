@@ -460,6 +460,14 @@ class Sampler:
         check(_lib.load().stk_sampler_adaptation(self._h, eps.ctypes.data, im.ctypes.data))
         return eps, im
 
+    def metric_factor(self):
+        """Every chain's Cholesky factor L of the dense_e inverse metric, M^-1 = L L^T: (nchains, D, D)."""
+        n = self.model.nshards * self.cfg.chains
+        D = max(self.model.D)
+        L = np.zeros((n, D, D))
+        check(_lib.load().stk_sampler_metric_factor_dense(self._h, L.ctypes.data))
+        return L
+
     def result(self) -> SampleResult:
         info = self.info()
         if info["errors"]:

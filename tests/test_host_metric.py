@@ -58,4 +58,4 @@ def test_make_config_refuses_wrong_shapes_and_names():
 def test_library_exports_the_dense_entry_points():
     from stark_amd import _lib
     lib = _lib.load()
-    assert lib.stk_sampler_adaptation_dense and lib.stk_transition_dense
+    assert lib.stk_sampler_adaptation_dense and lib.stk_transition_dense and lib.stk_sampler_metric_factor_dense

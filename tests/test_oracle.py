@@ -336,3 +336,233 @@ def test_nuts_table_math_emulation_accuracy():
     assert M.ulps(M.log1p01_mt(e), np.log1p(e.astype(np.longdouble))).max() < 3
     sp = M.exp_mt(np.array([-np.inf, np.inf, np.nan, -1000.0, 1000.0]))
     assert sp[0] == 0 and sp[1] == np.inf and np.isnan(sp[2]) and sp[3] == 0 and sp[4] == np.inf
+
+
+# ================================================================ the oracle's dense metric (dense_e)
+def _dense_data(orc, family, n, d, seed, xscale=1.0):
+    rng = np.random.default_rng(seed)
+    X = xscale * rng.uniform(-1.7, 1.7, (n, d))
+    beta = rng.normal(0, 1 / np.sqrt(d), d) / xscale
+    if family == "logistic":
+        y = (rng.uniform(size=n) < 1 / (1 + np.exp(-(0.2 + X @ beta)))).astype(np.int32)
+        return X, y, orc.FAM_LOGREG, d + 1
+    return X, 0.3 + X @ beta + rng.normal(size=n), orc.FAM_LINREG, d + 2
+
+
+def _rows_over_bars(rows):
+    """rows: (where, got (q, lp, stats), want (q, lp, stats)).  Asserts the replay bars of
+    tests/test_gpu_dense_metric.py's _check_rows on every row."""
+    for where, (q, lp, st), (oq, olp, ost) in rows:
+        assert st[2] == ost[2] and st[3] == ost[3] and st[4] == ost[4], (where, st, ost)
+        np.testing.assert_allclose(q, oq, rtol=1e-8, atol=1e-10, err_msg=str(where))
+        assert abs(lp - olp) <= 1e-9 * max(1.0, abs(olp)), (where, lp, olp)
+        np.testing.assert_allclose(st[[0, 5]], ost[[0, 5]], rtol=1e-9, atol=1e-12, err_msg=str(where))
+
+
+def test_oracle_cholesky_is_a_factor(orc):
+    rng = np.random.default_rng(2)
+    for D in (1, 2, 7, 40):
+        G = rng.normal(size=(D, D))
+        A = G @ G.T / D + 0.5 * np.eye(D)
+        A = np.tril(A) + np.tril(A, -1).T
+        L = orc.cholesky(A)
+        assert np.all(np.triu(L, 1) == 0) and np.all(np.diag(L) > 0)
+        np.testing.assert_allclose(L @ L.T, A, rtol=0, atol=1e-14 * np.abs(A).max() * D)
+        np.testing.assert_allclose(L, np.linalg.cholesky(A), rtol=1e-12, atol=1e-15)
+    bad = np.eye(3)
+    bad[0, 1] = bad[1, 0] = 2.0
+    with pytest.raises(ValueError, match="positive definite"):
+        orc.cholesky(bad)
+
+
+@pytest.mark.parametrize("family", ["schools", "logistic", "linear"])
+def test_oracle_dense_with_a_diagonal_matrix_is_the_diagonal_oracle(orc, family):
+    """M^-1 = diag(v): dense and diagonal transitions differ only in the order of the sums (the dense
+    loops add exact zeros and divide by sqrt(v) where the diagonal path divides by sqrt(v) too)."""
+    rng = np.random.default_rng(8)
+    if family == "schools":
+        m = orc.Model(orc.FAM_SCHOOLS, y=orc.SCHOOLS_Y, sigma=orc.SCHOOLS_SIGMA)
+        eps_list = (0.1, 0.3)
+    else:
+        X, y, fam, _ = _dense_data(orc, family, 200, 7, 3)
+        m = orc.Model(fam, X=X, y=y)
+        eps_list = (0.02, 0.06)
+    v = rng.uniform(0.5, 2.0, m.D)
+    if family == "linear":
+        v[0] /= 200
+        v[-1] /= 400
+    depths = set()
+    for eps in eps_list:
+        for c in range(6):
+            q0 = rng.normal(0, 0.1, m.D)
+            kw = dict(seed=13, gid=c, iteration=3, eps=eps, max_depth=6)
+            a = m.transition(q0, inv_metric=np.diag(v), **kw)
+            b = m.transition(q0, inv_metric=v, **kw)
+            np.testing.assert_array_equal(a[2][1:5], b[2][1:5])
+            np.testing.assert_allclose(a[0], b[0], rtol=1e-12, atol=0)
+            assert abs(a[1] - b[1]) <= 1e-12 * abs(b[1])
+            np.testing.assert_allclose(a[2][[0, 5]], b[2][[0, 5]], rtol=1e-12, atol=0)
+            assert a[3] == b[3]
+            depths.add(int(a[2][2]))
+    assert max(depths) >= 3, depths
+
+
+@pytest.mark.parametrize("family", ["logistic", "linear"])
+def test_oracle_block_dense_metric_is_the_diagonal_oracle_on_reparametrised_data(orc, family):
+    """blockdiag(a, L L^T[, s]) on (X, q) vs the diagonal oracle on (X L, q'), d = 9, max_depth 6."""
+    d, n, chains = 9, 300, 16
+    lin = family == "linear"
+    X, y, fam, D = _dense_data(orc, family, n, d, 100 * d + int(lin), xscale=0.07 if lin else 1.0)
+    rng = np.random.default_rng(7 * d + int(lin))
+    Lb = np.tril(rng.normal(0, 0.3 / np.sqrt(d), (d, d)), -1) + np.diag(rng.uniform(0.5, 1.5, d))
+    a, s = rng.uniform(0.5, 2.0, 2)
+    if lin:
+        a, s = a / n, s / (2 * n)
+    Minv = np.zeros((D, D))
+    Minv[0, 0] = a
+    B = Lb @ Lb.T
+    Minv[1:d + 1, 1:d + 1] = np.tril(B) + np.tril(B, -1).T
+    im = np.ones(D)
+    im[0] = a
+    if lin:
+        Minv[-1, -1] = im[-1] = s
+    q0p = rng.normal(0, 0.1, (chains, D))
+    to_q = lambda qp: np.concatenate([qp[:1], Lb @ qp[1:d + 1], qp[d + 1:]])   # noqa: E731
+    om, omr = orc.Model(fam, X=X, y=y), orc.Model(fam, X=np.ascontiguousarray(X @ Lb), y=y)
+    rows, depths = [], set()
+    for eps in (0.02, 0.05, 0.1, 0.3):
+        for c in range(chains):
+            kw = dict(seed=31, gid=c, iteration=4, eps=eps, max_depth=6)
+            oq, olp, ost, _ = omr.transition(q0p[c], inv_metric=im, **kw)
+            q, lp, st, _ = om.transition(to_q(q0p[c]), inv_metric=Minv, **kw)
+            rows.append(((eps, c), (q, lp, st), (to_q(oq), olp, ost)))
+            depths.add(int(ost[2]))
+    assert max(depths) >= 4, depths
+    _rows_over_bars(rows)
+
+
+@pytest.mark.parametrize("D", [11, 202])
+def test_oracle_general_dense_metric_one_leaf(orc, D):
+    """A random SPD M^-1 with alpha-beta and log sigma cross terms at max_depth 1: the draw is q0 or
+    one of the two one-leapfrog candidates of p = L^-T u, in numpy (the arithmetic of
+    test_gpu_dense_metric.py's test_general_dense_metric_one_leaf)."""
+    d, n, seed, it = D - 2, 300, 19, 0
+    X, y, fam, _ = _dense_data(orc, "linear", n, d, 5 * D)
+    rng = np.random.default_rng(D)
+    G = rng.normal(size=(D, D))
+    Minv = (G @ G.T / D + 0.5 * np.eye(D)) / n
+    Minv = np.tril(Minv) + np.tril(Minv, -1).T
+    assert abs(Minv[0, 1]) > 0 and abs(Minv[-1, 1]) > 0 and abs(Minv[-1, 0]) > 0
+    L = np.linalg.cholesky(Minv)
+    om = orc.Model(fam, X=X, y=y)
+    eps = 0.35 if D == 11 else 0.1
+    ols, _ = orc.linreg_exact_moments(X, y)
+    rss = float(((y - np.hstack([np.ones((n, 1)), X]) @ ols) ** 2).sum())
+    q0 = np.concatenate([ols, [0.5 * np.log(rss / n)]]) + np.random.default_rng(3).normal(0, 0.02, (16, D))
+    moved = 0
+    for c in range(16):
+        q, lp, st, ng = om.transition(q0[c], seed=seed, gid=c, iteration=it, eps=eps, inv_metric=Minv, max_depth=1)
+        u = np.array([orc.lib().orc_normal(seed, c, it, 0, e, orc.TAG_MOM) for e in range(D)])
+        p = np.linalg.solve(L.T, u)
+        lp0, g0 = om.lpgrad(q0[c])
+        H0 = -lp0 + 0.5 * p @ Minv @ p
+        cands = []
+        for sgn in (1.0, -1.0):
+            ph = p + 0.5 * sgn * eps * g0
+            q1 = q0[c] + sgn * eps * (Minv @ ph)
+            lp1, g1 = om.lpgrad(q1)
+            p1 = ph + 0.5 * sgn * eps * g1
+            H1 = -lp1 + 0.5 * p1 @ Minv @ p1
+            cands.append((q1, 1.0 if H0 - H1 > 0 else float(np.exp(H0 - H1)), lp1))
+        assert st[2] == 1 and st[3] == 1 and ng == 2, st
+        if np.array_equal(q, q0[c]):
+            err = min(abs(st[0] - a) for _, a, _ in cands)
+        else:
+            moved += 1
+            q1, acc, lp1 = cands[int(np.argmin([np.abs(q - c1).max() for c1, _, _ in cands]))]
+            np.testing.assert_allclose(q, q1, rtol=1e-8, atol=1e-10, err_msg=str(c))
+            assert abs(lp - lp1) <= 1e-9 * max(1.0, abs(lp1)), (lp, lp1)
+            err = abs(st[0] - acc)
+        assert err <= 1e-9, (c, st[0], [a for _, a, _ in cands])
+    assert moved > 8, moved
+
+
+def _correlated_linear(n=400, d=12, rho=0.9, seed=5):
+    """The data of tests/test_gpu_dense_metric.py's dense_e tests."""
+    rng = np.random.default_rng(seed)
+    X = np.sqrt(rho) * rng.normal(size=(n, 1)) + np.sqrt(1 - rho) * rng.normal(size=(n, d))
+    beta = rng.normal(0, 1, d)
+    return X, 0.3 + X @ beta + rng.normal(size=n)
+
+
+def test_oracle_dense_run_adapts_by_the_formula_and_samples_the_posterior(orc):
+    """run_chain(metric="dense_e") on the correlated linear data: the final matrix is Stan's
+    covar_adaptation formula on the run's own last window (num_warmup 300: draws 150..249), the
+    closed-form moments hold within 5 MCSE and the trees are at most a third of diag_e's."""
+    from stark_amd.diagnostics import ess
+    X, y = _correlated_linear()
+    mean, _ = orc.linreg_exact_moments(X, y)
+    om = orc.Model(orc.FAM_LINREG, X=X, y=y)
+    chains, nw, ns = 8, 300, 300
+    dense = [om.run_chain(num_warmup=nw, num_samples=ns, seed=5, gid=c, metric="dense_e") for c in range(chains)]
+    diag = [om.run_chain(num_warmup=nw, num_samples=ns, seed=5, gid=c) for c in range(chains)]
+    for c, r in enumerate(dense):
+        assert r["inv_metric"].shape == (14, 14)
+        w = r["q"][150:250]
+        n = len(w)
+        cov = np.cov(w.T, ddof=1)
+        want = (n / (n + 5.0)) * cov + 1e-3 * (5.0 / (n + 5.0)) * np.eye(14)
+        sc = np.sqrt(np.outer(np.diag(cov), np.diag(cov)))
+        assert np.all(np.abs(r["inv_metric"] - want) <= 1e-12 * sc), (c, (np.abs(r["inv_metric"] - want) / sc).max())
+        np.testing.assert_array_equal(r["inv_metric"], r["inv_metric"].T)
+    z = []
+    for k in range(13):
+        x = np.stack([r["q"][nw:, k] for r in dense])
+        z.append((x.mean() - mean[k]) / (x.std(ddof=1) / np.sqrt(ess(x))))
+    assert np.all(np.abs(z) < 5), z
+    lf_dense = np.mean([r["stats"][nw:, 3].mean() for r in dense])
+    lf_diag = np.mean([r["stats"][nw:, 3].mean() for r in diag])
+    assert lf_dense <= lf_diag / 3.0, (lf_dense, lf_diag)
+
+
+def test_oracle_metric_selector(orc):
+    """unit_e keeps the unit metric and adapts the step; diag_e is the default; a dense initial
+    matrix that is not positive definite is the step-size-error code."""
+    X, y, fam, D = _dense_data(orc, "logistic", 300, 4, 6)
+    om = orc.Model(fam, X=X, y=y)
+    kw = dict(num_warmup=150, num_samples=10, seed=4, gid=1)
+    u = om.run_chain(metric="unit_e", **kw)
+    np.testing.assert_array_equal(u["inv_metric"], np.ones(D))
+    assert u["stepsize"] != 1.0 and u["stepsize"] > 0
+    a, b = om.run_chain(**kw), om.run_chain(metric="diag_e", **kw)
+    np.testing.assert_array_equal(a["q"], b["q"])
+    assert np.any(a["inv_metric"] != 1.0)
+    # a diagonal initial matrix: the init buffer (75 transitions under the initial metric) is diag_e's
+    v = np.linspace(0.5, 1.5, D)
+    e = om.run_chain(metric="dense_e", inv_metric=np.diag(v), **kw)
+    assert e["inv_metric"].shape == (D, D) and np.abs(e["inv_metric"] - np.diag(np.diag(e["inv_metric"]))).max() > 0
+    bad = np.eye(D)
+    bad[0, 1] = bad[1, 0] = 2.0
+    with pytest.raises(RuntimeError, match="positive definite"):
+        om.run_chain(metric="dense_e", inv_metric=bad, **kw)
+    with pytest.raises(ValueError, match="shape"):
+        om.run_chain(metric="dense_e", inv_metric=np.eye(D + 1), **kw)
+
+
+def test_oracle_self_replay_reports_flips_and_errors(orc):
+    """On a proper posterior the oracle replays itself far inside the bars; on linearly separable
+    logistic data (flat priors: the chains run off) it does not, and the helper says so."""
+    X, y, fam, D = _dense_data(orc, "logistic", 400, 9, 77)
+    om = orc.Model(fam, X=X, y=y)
+    rng = np.random.default_rng(1)
+    G = rng.normal(size=(D, D))
+    Minv = (G @ G.T / D + 0.5 * np.eye(D)) / 400
+    Minv = np.tril(Minv) + np.tril(Minv, -1).T
+    starts = [(rng.normal(0, 0.1, D), c, 2, 0.2) for c in range(8)]
+    flips, worst = orc.self_replay(om, starts, seed=9, inv_metric=Minv, factor=orc.cholesky(Minv), max_depth=6)
+    assert flips == 0 and worst <= 1e-2, (flips, worst)
+    flips0, worst0 = orc.self_replay(om, starts, seed=9, inv_metric=Minv, max_depth=6, rel=0.0)
+    assert flips0 == 0 and worst0 == 0.0                 # the same start: the same bits, factored per call or once
+    far = [(q * 1e3, c, it, eps) for q, c, it, eps in starts]
+    _, worst_far = orc.self_replay(om, far, seed=9, inv_metric=Minv, max_depth=6, rel=1e-6)
+    assert worst_far > 1.0, worst_far
