@@ -10,8 +10,11 @@
  *   stk_model_create_synthetic  SURVEY.md 8d synthetic shards (bench; no host rows)
  *   stk_log_density_grad        Stan log_prob<propto=true,jacobian=true> + gradient, the
  *                               unit of work inside stark/stark.py:48 `sm.sampling`
- *   stk_log_density_grad_shards the same for every shard at once, launched as a sampling run
- *                               launches it (parity hook)
+ *   stk_log_density_grad_shards the same for every shard at once, one sweep launch per group
+ *                               (parity hook; C must be a single batch size)
+ *   stk_log_density_grad_chains the same at any C >= 1, through the chain batches and grouped
+ *                               launches of a sampling run (parity hook)
+ *   stk_chain_batches           the batches a regression shard's `chains` run as (host only)
  *   stk_sample / stk_sampler_*  stark/stark.py:48-56  `sm.sampling(data, **kw)` +
  *                               `fit.extract()` -> P x S matrix, for every local partition
  *                               (stark/stark.py:65 mapPartitions(_mcmc(...)))
@@ -83,7 +86,8 @@ typedef struct {
 typedef struct {
   int32_t num_warmup;
   int32_t num_samples;
-  int32_t chains;            /* chains per shard */
+  int32_t chains;            /* chains per shard: any count >= 1; regressions run it as the batches of
+                                stk_chain_batches (stark/stark.py:48 forwards `chains` untouched) */
   int32_t max_depth;         /* 1..30.  8 schools: the fused kernel holds a chain's 17 vectors and
                                 max_depth x 4 (stan2.19) or x 7 (stan2.23) stack vectors of
                                 Dp = roundup8(J + 2) doubles in LDS; a config whose image exceeds the
@@ -132,13 +136,15 @@ typedef struct {
   int64_t grad_evals;   /* chain-gradient evaluations issued (all local chains)          */
   int64_t leapfrogs;    /* leapfrog steps inside NUTS trajectories                        */
   int64_t steps;        /* state-machine steps launched                                   */
-  int64_t sweeps;       /* data-sweep launches that ran (regression families)             */
-  double sweep_ms;      /* summed HIP-event time of the sweep kernel (profiling on only)  */
+  int64_t sweeps;       /* steps whose data sweeps ran (regression families)              */
+  double sweep_ms;      /* summed HIP-event time of those steps' sweep kernels (profiling on only);
+                           one step's event pair spans the sweeps of all its chain batches  */
   int32_t divergent;    /* divergent transitions after warmup                             */
   int32_t errors;       /* chains stopped by a step-size error                            */
   int32_t min_iter;     /* fewest transitions completed by any chain                      */
   int32_t done;         /* chains that completed num_warmup + num_samples                 */
-  int64_t shard_sweeps; /* shard passes inside those sweeps (bytes = shard_sweeps * n*(8d+4)) */
+  int64_t shard_sweeps; /* shard passes inside those sweeps, one per shard per chain-batch launch
+                           (bytes = shard_sweeps * n*(8d+4))                               */
 } stk_run_info;
 
 STK_API const char* stk_last_error(void);
@@ -179,10 +185,21 @@ STK_API int stk_model_device_bytes(const stk_model* m, int64_t* bytes);
 
 /* ---- log density + gradient at C points of one shard (parity hook) ---- */
 STK_API int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, double* lp, double* grad);
-/* lp and gradient of EVERY shard at C points each, through the grouped launches of a
- * sampling run (parity hook).  q: [nshards][C][D], lp: [nshards][C], grad: [nshards][C][D]
- * (grad may be NULL).  Regressions only; C must be a chain count the sampler takes. */
+/* lp and gradient of EVERY shard at C points each (parity hook): one sweep launch per group; C
+ * must be a single batch size.  q: [nshards][C][D], lp: [nshards][C], grad: [nshards][C][D]
+ * (grad may be NULL).  Regressions only. */
 STK_API int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double* lp, double* grad);
+/* The same arrays at ANY C >= 1, run through exactly the chain batches (stk_chain_batches) and
+ * grouped launches of a sampling run at chains = C (parity hook).  Regressions only. */
+STK_API int stk_log_density_grad_chains(stk_model* m, const double* q, int32_t C, double* lp, double* grad);
+/* The contiguous chain batches that the C chains of a regression shard with d covariates run as:
+ * greedy, largest first, over the single-launch sizes {64, 16, 8, 4, 2, 1} that a sweep covers at
+ * d (1, 2, 4, 8, 16: d <= 1024; 64: any d), no padding -- e.g. d = 100: 3 = 2 + 1, 17 = 16 + 1, 70 = 64 + 4 + 2.  A pure host
+ * function of (C, d): needs no device and is the same on every rank.  Writes the first `cap` sizes
+ * (sizes may be NULL when cap is 0) and returns the number of batches, or STK_E_ARG (C < 1, or no
+ * sweep covers d).  Chain c of shard s keeps RNG stream shard_ids[s] * chains + c, and every
+ * layout (draws, stats, the full-data block, the saved state) is that of a single batch. */
+STK_API int stk_chain_batches(int32_t C, int32_t d, int32_t* sizes, int32_t cap);
 
 /* ---- sampling: stark/stark.py:43-56 for every shard of the model ---- */
 STK_API int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out);

@@ -87,6 +87,8 @@ SIGNATURES = [
     ("stk_model_device_bytes", ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),
     ("stk_log_density_grad", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _vp, _vp]),
     ("stk_log_density_grad_shards", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    ("stk_log_density_grad_chains", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    ("stk_chain_batches", ctypes.c_int, [_i32, _i32, _vp, _i32]),
     ("stk_sampler_create", ctypes.c_int, [_vp, ctypes.POINTER(Config), _pp]),
     ("stk_sampler_run", ctypes.c_int, [_vp, _i32, _i64]),
     ("stk_sampler_info", ctypes.c_int, [_vp, ctypes.POINTER(RunInfo)]),

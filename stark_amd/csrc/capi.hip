@@ -28,12 +28,12 @@ void stk_sweep_geometry(int64_t n, int d, int* T, int* LD, int* G, size_t* lds_b
 bool stk_sweep_supported(int C, int d);
 hipError_t stk_launch_sweep(int family, const ShardDev* shards_dev, int shard0, int nsh, int64_t n, int d, int T, int LD, int G,
                             int Gs, size_t lds, const double* q, int C, int Dp, double* partial, const int* req_step,
-                            int step_id, int* ran, hipStream_t st, const SweepWs* ws = nullptr);
+                            int step_id, int* ran, hipStream_t st, const SweepWs* ws = nullptr, int Ct = 0, int c0 = 0);
 size_t stk_sweep_ws_bytes(int64_t n_max, int d, int C, int nshards);
 SweepWs stk_sweep_ws(void* base, int64_t n_max, int d, int nshards);
 hipError_t stk_launch_sweep_reduce(int family, const ShardDev* shards_dev, int shard0, int nsh, int d, int G, int Gs,
                                    const double* q, int C, int Dp, double* partial, const int* req_step, int step_id,
-                                   double* lp_out, double* g_out, hipStream_t st);
+                                   double* lp_out, double* g_out, hipStream_t st, int Ct = 0, int c0 = 0);
 hipError_t stk_launch_check_y01(const int32_t* y, int64_t n, int64_t* first, hipStream_t st);
 hipError_t stk_launch_gen_shard(double* X, double* yd, int32_t* yi, int64_t nrows, int d, int64_t grow0,
                                 uint64_t seed, double alpha, const double* beta, double noise_sigma, int family,
@@ -119,9 +119,14 @@ struct stk_model {
   int64_t bytes = 0;
 };
 
+// The chain counts that are ONE sweep launch in the two single-launch parity hooks (stk_log_density_grad's
+// own batching and stk_log_density_grad_shards): their acceptance set stays as it was before the
+// sampler batched chains -- 16 only where k_sweep16 itself runs (d <= 128).
+static bool hook_single_launch(int C, int d) { return stk_sweep_supported(C, d) && (C != 16 || d <= 128); }
+
 // The grouped sweep launches of a regression model at C chains per shard: consecutive shards of
 // equal n share one launch of nsh * G blocks; every shard's partial sums lie Gs = max G chunks
-// apart.  One construction for the sampler and the multi-shard parity hook.
+// apart.  One construction for every batch of the sampler (chain_plan) and the multi-shard parity hooks.
 struct SweepGroup { int shard0, nsh, T, LD, G; size_t lds; };
 struct SweepPlan {
   std::vector<SweepGroup> groups;
@@ -149,6 +154,77 @@ static SweepPlan sweep_plan(const stk_model* m, int C) {
   return p;
 }
 
+// The chain batches of a regression shard's C chains: greedy, largest first, over the single-launch
+// sizes {64, 16, 8, 4, 2, 1} a sweep covers at d (stk_sweep_supported: the ONE place that says
+// whether 16 is a batch size at d).  A pure function of (C, d) -- never of n, the shard count or
+// the device -- so every rank derives the same plan.  No padding, no idle chains.
+static std::vector<int> chain_batches(int C, int d) {
+  std::vector<int> b;
+  for (const int sz : {64, 16, 8, 4, 2, 1}) {
+    if (!stk_sweep_supported(sz, d)) continue;
+    for (; C >= sz; C -= sz) b.push_back(sz);
+  }
+  if (C != 0) b.clear();   // no sweep covers d
+  return b;
+}
+
+// A run's sweeps at Ct chains per shard: every batch has its own grouped launches (sweep_plan at
+// the batch's size), its own region of the partial-sum buffer and its first chain c0; the 64-chain
+// workspace is one, reused by successive 64-batches on the stream.
+struct ChainBatch {
+  int c0 = 0, C = 0, Gs = 1;
+  size_t part_off = 0;        // doubles into the partial-sum buffer
+  std::vector<SweepGroup> groups;
+};
+struct ChainPlan {
+  std::vector<ChainBatch> batches;
+  int Ct = 0;
+  int64_t nmax = 0;
+  size_t partial_bytes = 0, ws_bytes = 0;
+};
+static ChainPlan chain_plan(const stk_model* m, int Ct) {
+  ChainPlan cp;
+  cp.Ct = Ct;
+  int c0 = 0;
+  for (const int sz : chain_batches(Ct, m->d)) {
+    SweepPlan p = sweep_plan(m, sz);
+    ChainBatch b;
+    b.c0 = c0;
+    b.C = sz;
+    b.Gs = p.Gs;
+    b.part_off = cp.partial_bytes / sizeof(double);
+    b.groups = std::move(p.groups);
+    cp.partial_bytes += p.partial_bytes;
+    cp.ws_bytes = std::max(cp.ws_bytes, p.ws_bytes);
+    cp.nmax = p.nmax;
+    cp.batches.push_back(std::move(b));
+    c0 += sz;
+  }
+  return cp;
+}
+// Every batch's sweep over every shard group; then (plan_reduces) every batch's reduction.
+static hipError_t plan_sweeps(const stk_model* m, const ChainPlan& cp, const ShardDev* shd, const double* q, int Dp,
+                              double* partial, const int* req_step, int step_id, int* ran, const SweepWs* ws,
+                              hipStream_t st) {
+  for (const auto& b : cp.batches)
+    for (const auto& gr : b.groups)
+      if (const hipError_t e = stk_launch_sweep(m->family, shd, gr.shard0, gr.nsh, m->sh[gr.shard0].n, m->d, gr.T, gr.LD,
+                                                gr.G, b.Gs, gr.lds, q, b.C, Dp, partial + b.part_off, req_step, step_id,
+                                                ran, st, ws, cp.Ct, b.c0))
+        return e;
+  return hipSuccess;
+}
+static hipError_t plan_reduces(const stk_model* m, const ChainPlan& cp, const ShardDev* shd, const double* q, int Dp,
+                               double* partial, const int* req_step, int step_id, double* lp, double* g,
+                               hipStream_t st) {
+  for (const auto& b : cp.batches)
+    for (const auto& gr : b.groups)
+      if (const hipError_t e = stk_launch_sweep_reduce(m->family, shd, gr.shard0, gr.nsh, m->d, gr.G, b.Gs, q, b.C, Dp,
+                                                       partial + b.part_off, req_step, step_id, lp, g, st, cp.Ct, b.c0))
+        return e;
+  return hipSuccess;
+}
+
 struct stk_sampler {
   stk_model* m = nullptr;
   stk_config cfg{};
@@ -164,8 +240,7 @@ struct stk_sampler {
   SweepWs sws{};
   stk_allreduce_fn ar_fn = nullptr;   // full-data mode: rank-sum of [grad | lp] after every reduce
   void* ar_user = nullptr;
-  int Gs = 1;
-  std::vector<SweepGroup> groups;
+  ChainPlan plan;
   std::vector<hipEvent_t> ev;
   std::vector<int> iv_host;
   std::vector<unsigned long long> cnt_host;
@@ -500,7 +575,7 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
     size_t lds;
     // the chain batch the sampler's sweep uses: 64 (two-pass fp64 MFMA GEMMs) from 64 points,
     // 16 (fp64 MFMA) from 16 when d <= 128, else 4 / 2 / 1
-    const int Cb = C <= 1 ? 1 : (C <= 2 ? 2 : (C >= 64 ? 64 : (C < 16 || !stk_sweep_supported(16, s.d) ? 4 : 16)));
+    const int Cb = C <= 1 ? 1 : (C <= 2 ? 2 : (C >= 64 ? 64 : (C < 16 || !hook_single_launch(16, s.d) ? 4 : 16)));
     stk_sweep_geometry(s.n, s.d, &T, &LD, &G, &lds, Cb);
     const int PW = s.d + 2;
     const size_t wsb = stk_sweep_ws_bytes(s.n, s.d, Cb, m->nshards);
@@ -549,7 +624,7 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
 int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_shards: bad arguments");
   ARG_CHECK(m->family == STK_LOGREG || m->family == STK_LINREG, "stk_log_density_grad_shards: regression families only");
-  ARG_CHECK(stk_sweep_supported(C, m->d), "chains per shard must be 1, 2, 4, 8, 16 (d <= 128) or 64 for regressions");
+  ARG_CHECK(hook_single_launch(C, m->d), "points per shard must be a single batch size here: 1, 2, 4, 8, 16 (d <= 128) or 64");
   stk_ctx* ctx = m->ctx;
   STK_HIP_CHECK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -585,6 +660,54 @@ int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double
                                    hipMemcpyDefault, st));
   STK_HIP_CHECK(hipStreamSynchronize(st));
   return STK_OK;
+}
+
+// The same at ANY C >= 1 points per shard: the chain batches and grouped launches of a sampling
+// run at chains = C (chain_plan).
+int stk_log_density_grad_chains(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
+  ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_chains: bad arguments");
+  ARG_CHECK(m->family == STK_LOGREG || m->family == STK_LINREG, "stk_log_density_grad_chains: regression families only");
+  ARG_CHECK(!chain_batches(C, m->d).empty(), "no sweep covers %d covariates (1..1024)", m->d);
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const ShardDev* shd = m->sh_dev.as<ShardDev>();
+  const int D = m->Dmax;
+  const int Dp = (m->Dmax + 7) / 8 * 8;
+  const size_t rows = (size_t)m->nshards * C;
+  const ChainPlan plan = chain_plan(m, C);
+  SweepWs ws{};
+  if (plan.ws_bytes) {
+    RC(ctx->scratch[4].ensure(plan.ws_bytes));
+    ws = stk_sweep_ws(ctx->scratch[4].p, plan.nmax, m->d, m->nshards);
+  }
+  RC(ctx->scratch[0].ensure(sizeof(double) * rows * Dp));
+  RC(ctx->scratch[1].ensure(sizeof(double) * rows));
+  RC(ctx->scratch[2].ensure(sizeof(double) * rows * Dp));
+  RC(ctx->scratch[3].ensure(plan.partial_bytes));
+  double* qb = ctx->scratch[0].as<double>();
+  double* lpb = ctx->scratch[1].as<double>();
+  double* gb = ctx->scratch[2].as<double>();
+  double* part = ctx->scratch[3].as<double>();
+  STK_HIP_CHECK(hipMemcpy2DAsync(qb, sizeof(double) * Dp, q, sizeof(double) * D, sizeof(double) * D, rows,
+                                 hipMemcpyDefault, st));
+  STK_HIP_CHECK(plan_sweeps(m, plan, shd, qb, Dp, part, nullptr, 0, nullptr, plan.ws_bytes ? &ws : nullptr, st));
+  STK_HIP_CHECK(plan_reduces(m, plan, shd, qb, Dp, part, nullptr, 0, lpb, gb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(lp, lpb, sizeof(double) * rows, hipMemcpyDefault, st));
+  if (grad)
+    STK_HIP_CHECK(hipMemcpy2DAsync(grad, sizeof(double) * D, gb, sizeof(double) * Dp, sizeof(double) * D, rows,
+                                   hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
+// The chain batches a regression shard's C chains run as at d covariates (host only: no device).
+int stk_chain_batches(int32_t C, int32_t d, int32_t* sizes, int32_t cap) {
+  ARG_CHECK(C >= 1 && d >= 1 && cap >= 0 && (sizes || cap == 0), "stk_chain_batches: need C >= 1, d >= 1, cap >= 0");
+  const std::vector<int> b = chain_batches(C, d);
+  ARG_CHECK(!b.empty(), "no sweep covers %d covariates (1..1024)", d);
+  for (size_t i = 0; i < b.size() && (int32_t)i < cap; ++i) sizes[i] = b[i];
+  return (int)b.size();
 }
 
 // ---------------------------------------------------------------- sampler
@@ -684,7 +807,7 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
               "8-schools with J = %d at max_depth %d (nuts_criterion %d) needs %zu bytes of LDS per workgroup, the limit is %zu: "
               "lower max_depth",
               m->Dmax - 2, cfg->max_depth, cfg->nuts_criterion, lds, BIG_LDS_BYTES);
-  } else ARG_CHECK(stk_sweep_supported(cfg->chains, m->d), "chains per shard must be 1, 2, 4, 8, 16 (d <= 128) or 64 for regressions");
+  } else ARG_CHECK(!chain_batches(cfg->chains, m->d).empty(), "no sweep covers %d covariates (1..1024)", m->d);
   stk_sampler* s = new stk_sampler();
   s->m = m;
   m->refs++;
@@ -807,10 +930,9 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
     }
   }
   if (rc == STK_OK && m->family != STK_SCHOOLS) {
-    // sweep geometry, grouped by consecutive shards of equal n
-    SweepPlan plan = sweep_plan(m, cfg->chains);
-    s->groups = std::move(plan.groups);
-    s->Gs = plan.Gs;
+    // the chain batches, each with its sweep geometry grouped by consecutive shards of equal n
+    s->plan = chain_plan(m, cfg->chains);
+    const ChainPlan& plan = s->plan;
     rc = s->partial.ensure(plan.partial_bytes);
     if (rc == STK_OK && plan.ws_bytes) {
       rc = s->ws.ensure(plan.ws_bytes);
@@ -878,16 +1000,12 @@ static int run_split_batch(stk_sampler* s, int nsteps, int pause_at) {
     const int step_id = s->step;
     const bool pk = prof && step_id % every == 0;
     if (pk) STK_HIP_CHECK(hipEventRecord(s->ev[2 * k], st));
-    for (const auto& gr : s->groups) {
-      STK_HIP_CHECK(stk_launch_sweep(m->family, A.shards, gr.shard0, gr.nsh, m->sh[gr.shard0].n, m->d, gr.T, gr.LD, gr.G, s->Gs, gr.lds,
-                                     A.qeval, A.C, A.Dp, s->partial.as<double>(), A.req_step, step_id,
-                                     prof ? s->ran.as<int>() : nullptr, st, s->sws.qT ? &s->sws : nullptr));
-    }
+    // one event pair spans the sweeps of all the step's batches
+    STK_HIP_CHECK(plan_sweeps(m, s->plan, A.shards, A.qeval, A.Dp, s->partial.as<double>(), A.req_step, step_id,
+                              prof ? s->ran.as<int>() : nullptr, s->sws.qT ? &s->sws : nullptr, st));
     if (pk) STK_HIP_CHECK(hipEventRecord(s->ev[2 * k + 1], st));
-    for (const auto& gr : s->groups) {
-      STK_HIP_CHECK(stk_launch_sweep_reduce(m->family, A.shards, gr.shard0, gr.nsh, m->d, gr.G, s->Gs, A.qeval, A.C,
-                                            A.Dp, s->partial.as<double>(), A.req_step, step_id, A.lp_in, A.g_in, st));
-    }
+    STK_HIP_CHECK(plan_reduces(m, s->plan, A.shards, A.qeval, A.Dp, s->partial.as<double>(), A.req_step, step_id,
+                               A.lp_in, A.g_in, st));
     if (s->ar_fn) {
       const int r = s->ar_fn(s->ar_user, A.g_in, (int64_t)A.nchains * (A.Dp + 1), (void*)st);
       if (r != 0) {

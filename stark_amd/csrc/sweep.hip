@@ -48,10 +48,10 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
 
   for (int i = tid; i < C * d; i += NT) {
     const int c = i / d, j = i % d;
-    Bs[c * LD + j] = A.q[(size_t)(shard * C + c) * A.Dp + 1 + j];
+    Bs[c * LD + j] = A.q[chain_row(A, shard, c) * A.Dp + 1 + j];
   }
   if (tid < C) {
-    const double* qc = A.q + (size_t)(shard * C + tid) * A.Dp;
+    const double* qc = A.q + chain_row(A, shard, tid) * A.Dp;
     Al[tid] = qc[0];
     Al[C + tid] = (FAM == STK_LINREG) ? exp(-qc[d + 1]) : 0.0;
   }
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep2(SweepArgs A) {
   const ShardDev sh = A.shards[shard];
   const int d = sh.d, LD = A.LD, tid = threadIdx.x, lane = tid & 63, w = uniform_int(tid >> 6);
   const int64_t r0 = sh.n * chunk / A.G, r1 = sh.n * (chunk + 1) / A.G;
-  const cptr_t<double> qs = cp(A.q) + (size_t)shard * C * A.Dp;   // chain c: (alpha, beta, [u])
+  const cptr_t<double> qs = cp(A.q) + chain_row(A, shard) * A.Dp;   // chain c: (alpha, beta, [u])
   const gptr_t<double> X = gp(sh.x);
   const gptr_t<yv_t> Y = (gptr_t<yv_t>)(FAM == STK_LOGREG ? (const void*)sh.yi : (const void*)sh.y);
 
@@ -488,7 +488,7 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
   double* const dsc = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + (size_t)NW * NB * SS);  // [NW][8][C]
 
   // ---- per-lane constants: beta pieces (forward) and alpha / 1/sigma (residual)
-  const double* qs = A.q + (size_t)shard * C * A.Dp;
+  const double* qs = A.q + chain_row(A, shard) * A.Dp;
   const int fi = lane & 7, frow = w * 8 + (lane >> 3);   // forward: lane-in-row, row in tile
   double bt[S3_MAXP][C][2];
 #pragma unroll
@@ -681,7 +681,7 @@ __global__ __launch_bounds__(256) void k_qt_swizzle(SweepArgs A, int d) {
   const int i = blockIdx.x * 256 + threadIdx.x;     // k * 64 + c
   if (i >= KP * G5_C) return;
   const int k = i >> 6, c = i & 63;
-  const double v = k < d ? A.q[((size_t)shard * G5_C + c) * A.Dp + 1 + k] : 0.0;
+  const double v = k < d ? A.q[chain_row(A, shard, c) * A.Dp + 1 + k] : 0.0;
   char* img = reinterpret_cast<char*>(A.qT + (size_t)shard * KP * G5_C);
   *reinterpret_cast<double*>(img + g5_chain_off(k, c)) = v;
 }
@@ -756,7 +756,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
   double* const sptab = reinterpret_cast<double*>(stg + NS * STG);
   if constexpr (FAM == STK_LOGREG) exp_table_init(sptab);
   // per-lane chain constants: chain 16 c2 + lr
-  const double* qb = A.q + (size_t)shard * G5_C * A.Dp;
+  const double* qb = A.q + chain_row(A, shard) * A.Dp;
   double alpha[NCT], inv_s[NCT];
 #pragma unroll
   for (int c2 = 0; c2 < NCT; ++c2) {
@@ -1073,7 +1073,7 @@ __global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce(SweepArgs A, double*
   double t = part[0][threadIdx.x];
 #pragma unroll
   for (int i = 1; i < RD_W; ++i) t += part[i][threadIdx.x];
-  const size_t gid = (size_t)shard * C + c;
+  const size_t gid = chain_row(A, shard, c);
   double* g = g_out + gid * A.Dp;
   const double* qc = A.q + gid * A.Dp;
   // normal(0, s) priors on alpha (q[0]) and beta (q[1..d]): lp -= pa a^2/2 + pb |b|^2/2 (Stan's
@@ -1109,6 +1109,7 @@ using namespace stk;
 
 // Host-side geometry: depends only on (n, d, C) so reductions are identical on 1 or N GPUs.
 // v3 (LDS-DMA ring) for even d <= 104 and C <= 4, v2 for other even d <= 128, else v1.
+// C = 16: k_sweep16 (4) for d <= 128, k_sweep16w (6) past it; C = 64: the two GEMM passes (5).
 // stk_sweep_force_variant (1 | 2 | 3, 0 = by shape) is set by tools/sweep_micro.hip only: the
 // library reads no environment variable to pick a kernel.
 int stk_sweep_force_variant = 0;
@@ -1124,7 +1125,10 @@ static int sweep3_nb(int d, int C) {
 
 static int sweep_variant(int64_t n, int d, int C) {
   if (C == G5_C) return (((n + 511) / 512 + G5_TR + G5_FTR) * d * 8 < ((int64_t)1 << 31)) ? 5 : 0;   // chunk bytes (+ pass F's last tile) fit a buffer descriptor
-  if (C == SM_C) return (stk_sweep16_supported(d) && (n * d * 8) / 512 < ((int64_t)1 << 30)) ? 4 : 0;
+  if (C == SM_C) {
+    if ((n * d * 8) / 512 >= ((int64_t)1 << 30)) return 0;      // chunk bytes fit a buffer descriptor
+    return stk_sweep16_supported(d) ? 4 : (stk_sweep16w_supported(d) ? 6 : 0);
+  }
   const int f = sweep_forced();
   const bool v3ok = d % 2 == 0 && d / 2 <= S3_KMAX && (C == 1 || C == 2 || C == 4) && sweep3_nb(d, C) >= 3 &&
                     (n * d * 8) / 512 < ((int64_t)1 << 30);
@@ -1157,6 +1161,13 @@ void stk_sweep_geometry(int64_t n, int d, int* T, int* LD, int* G, size_t* lds_b
     *LD = 1;
     *G = (int)g;
     *lds_bytes = stk_sweep16_lds_bytes(STK_LOGREG, d);   // the larger of the two families
+    return;
+  }
+  if (var == 6) {                       // k_sweep16w (sweep16w.hip): LD carries the waves per block
+    *T = 64;
+    *LD = stk_sweep16w_waves(d);
+    *G = stk_sweep16w_chunks(n);
+    *lds_bytes = stk_sweep16w_lds_bytes(STK_LOGREG, d);
     return;
   }
   if (var == 3) {
@@ -1248,7 +1259,12 @@ static hipError_t pick_tile(const SweepArgs& A, int64_t n, int d, int T, int nbl
 
 template <int FAM>
 static hipError_t pick_c(const SweepArgs& A, int64_t n, int d, int T, int nblocks, size_t lds, hipStream_t st) {
-  if (A.C == SM_C) return sweep_variant(n, d, A.C) == 4 ? stk_launch_sweep16(FAM, A, d, nblocks, lds, st) : hipErrorInvalidValue;
+  if (A.C == SM_C) {
+    const int var = sweep_variant(n, d, A.C);
+    if (var == 4) return stk_launch_sweep16(FAM, A, d, nblocks, lds, st);
+    if (var == 6) return stk_launch_sweep16w(FAM, A, d, nblocks, lds, st);
+    return hipErrorInvalidValue;
+  }
   switch (A.C) {
     case 1: return pick_tile<FAM, 1>(A, n, d, T, nblocks, lds, st);
     case 2: return pick_tile<FAM, 2>(A, n, d, T, nblocks, lds, st);
@@ -1260,7 +1276,7 @@ static hipError_t pick_c(const SweepArgs& A, int64_t n, int d, int T, int nblock
 
 bool stk_sweep_supported(int C, int d) {
   if (C == G5_C) return d >= 1 && d <= 4096;
-  if (C == SM_C) return d >= 1 && d <= 128;
+  if (C == SM_C) return d >= 1 && (stk_sweep16_supported(d) || stk_sweep16w_supported(d));   // the one place a 16-batch is ruled in or out at d
   if (!(C == 1 || C == 2 || C == 4 || C == 8)) return false;
   return d >= 1 && d <= 1024;
 }
@@ -1279,11 +1295,15 @@ SweepWs stk_sweep_ws(void* base, int64_t n_max, int d, int nshards) {
   return w;
 }
 
-// Launch the sweep over `nsh` shards starting at shard0 (all with the same n, d geometry).
+// Launch the sweep over `nsh` shards starting at shard0 (all with the same n, d geometry) for the
+// batch of C chains that starts at chain c0 of every shard's Ct.
 hipError_t stk_launch_sweep(int family, const ShardDev* shards_dev, int shard0, int nsh, int64_t n, int d, int T,
                             int LD, int G, int Gs, size_t lds, const double* q, int C, int Dp, double* partial,
-                            const int* req_step, int step_id, int* ran, hipStream_t st, const SweepWs* ws = nullptr) {
+                            const int* req_step, int step_id, int* ran, hipStream_t st, const SweepWs* ws = nullptr,
+                            int Ct = 0, int c0 = 0) {
   SweepArgs A{shards_dev, q, partial, req_step, step_id, C, Dp, G, LD, d + 2, shard0, Gs, ran};
+  A.Ct = Ct > 0 ? Ct : C;   // a batch of C chains starting at chain c0 of the shard's Ct (default: the only batch)
+  A.c0 = c0;
   const int nblocks = nsh * G;
   if (sweep_variant(n, d, C) == 5) {
     if (!ws || !ws->qT || !ws->R || ws->Rrows < (n + G5_TR - 1) / G5_TR * G5_TR) return hipErrorInvalidValue;
@@ -1310,8 +1330,10 @@ hipError_t stk_launch_sweep(int family, const ShardDev* shards_dev, int shard0, 
 
 hipError_t stk_launch_sweep_reduce(int family, const ShardDev* shards_dev, int shard0, int nsh, int d, int G, int Gs,
                                    const double* q, int C, int Dp, double* partial, const int* req_step,
-                                   int step_id, double* lp_out, double* g_out, hipStream_t st) {
+                                   int step_id, double* lp_out, double* g_out, hipStream_t st, int Ct = 0, int c0 = 0) {
   SweepArgs A{shards_dev, q, partial, req_step, step_id, C, Dp, G, 0, d + 2, shard0, Gs, nullptr};
+  A.Ct = Ct > 0 ? Ct : C;
+  A.c0 = c0;
   dim3 grid(nsh * C, (d + 2 + 63) / 64);
   if (family == STK_LOGREG)
     hipLaunchKernelGGL(k_sweep_reduce<STK_LOGREG>, grid, dim3(64 * RD_W), 0, st, A, lp_out, g_out, C);

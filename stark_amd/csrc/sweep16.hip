@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   char* const slot = reinterpret_cast<char*>(lds) + (size_t)w * SS;
   double* const tab = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + (size_t)NW * SS);
   if constexpr (LOGI) exp_table_init(tab);
-  const double* qs = A.q + (size_t)shard * C * A.Dp;
+  const double* qs = A.q + chain_row(A, shard) * A.Dp;
   double bf[KF];                   // beta_{lr} at the column k-step s of lane group lh takes (forward)
 #pragma unroll
   for (int s = 0; s < KF; ++s) {

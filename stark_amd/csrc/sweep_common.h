@@ -1,5 +1,6 @@
 // Types and helpers shared by the regression sweeps (sweep.hip: C != 16 and the 64-chain GEMM
-// passes; sweep16.hip: the 16-chain fp64-MFMA sweep) and by the measurement tools in tools/.
+// passes; sweep16.hip: the 16-chain fp64-MFMA sweep; sweep16w.hip: its K-split for d > 128) and by
+// the measurement tools in tools/.
 #pragma once
 #include "common.h"
 
@@ -9,7 +10,7 @@ typedef double dbl2 __attribute__((ext_vector_type(2)));   // loads from any add
 
 struct SweepArgs {
   const ShardDev* shards;
-  const double* q;        // [nshards*C][Dp] evaluation points
+  const double* q;        // [nshards*Ct][Dp] evaluation points; this launch: rows shard*Ct + c0 + c, c < C
   double* partial;        // [nshards][G][C][PW]
   const int* req_step;    // nullptr: always run
   int step_id;
@@ -20,7 +21,14 @@ struct SweepArgs {
   double* qT;             // v5 workspace: [nshards][KP][64] swizzled beta^T images (KP = d rounded to 32)
   double* R;              // v5 workspace: [nshards][Rrows][64] residuals d eta, swizzled rows
   int64_t Rrows;          // v5: rows of R per shard (n rounded up to 64)
+  int Ct;                 // chains per shard in q / lp / grad (C when the launch is the shard's only batch)
+  int c0;                 // first chain of this launch's batch within its shard
 };
+
+// Row of chain c of the launch's batch in q, lp_out and g_out.
+__device__ __forceinline__ size_t chain_row(const SweepArgs& A, int shard, int c = 0) {
+  return (size_t)shard * A.Ct + A.c0 + c;
+}
 
 __device__ __forceinline__ void wait_vmcnt(int n) {
   // s_waitcnt encoding (gfx9): vmcnt [3:0] + [15:14], expcnt [6:4] = 7, lgkmcnt [11:8] = 15
@@ -134,3 +142,11 @@ __device__ __forceinline__ double logit_resid4(double eta, uint32_t y, const dou
 bool stk_sweep16_supported(int d);
 size_t stk_sweep16_lds_bytes(int family, int d);
 hipError_t stk_launch_sweep16(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
+
+// The wide 16-chain sweep (sweep16w.hip, 128 < d <= 1024): waves per block (= column slabs, passed
+// as SweepArgs.LD), chunks per shard, LDS bytes, launch.
+bool stk_sweep16w_supported(int d);
+int stk_sweep16w_waves(int d);
+int stk_sweep16w_chunks(int64_t n);
+size_t stk_sweep16w_lds_bytes(int family, int d);
+hipError_t stk_launch_sweep16w(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);

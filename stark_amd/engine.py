@@ -176,6 +176,17 @@ def make_config(num_warmup=1000, num_samples=1000, chains=1, max_depth=10, adapt
     return c
 
 
+def chain_batches(chains: int, n_cols: int) -> list[int]:
+    """The contiguous chain batches that ``chains`` chains per shard of a regression with ``n_cols``
+    covariates run as (stk_chain_batches): greedy, largest first, over the single-launch sizes
+    {64, 16, 8, 4, 2, 1} a sweep covers at that width.  Host only: needs no device."""
+    sizes = np.zeros(max(int(chains), 1), np.int32)
+    n = _lib.load().stk_chain_batches(int(chains), int(n_cols), sizes.ctypes.data, sizes.size)
+    if n < 0:
+        check(n)
+    return [int(v) for v in sizes[:n]]
+
+
 class Model:
     """Shards of one model family resident on one device (``stk_model``)."""
 
@@ -293,6 +304,19 @@ class Model:
         lp = np.empty(q.shape[:2])
         g = np.empty(q.shape)
         check(_lib.load().stk_log_density_grad_shards(self._h, q.ctypes.data, C, lp.ctypes.data, g.ctypes.data))
+        return lp, g
+
+    def log_density_grad_chains(self, q):
+        """The same at ANY C >= 1 points per shard (q: nshards x C x D), through the chain batches
+        (``chain_batches(C, d)``) and grouped launches of a sampling run at ``chains=C``
+        (see stk_log_density_grad_chains); regressions only."""
+        q = np.ascontiguousarray(q, np.float64)
+        if q.ndim != 3 or q.shape[0] != self.nshards or q.shape[2] != self.D[0]:
+            raise ValueError(f"q must be [nshards = {self.nshards}, C, D = {self.D[0]}], got {q.shape}")
+        C = q.shape[1]
+        lp = np.empty(q.shape[:2])
+        g = np.empty(q.shape)
+        check(_lib.load().stk_log_density_grad_chains(self._h, q.ctypes.data, C, lp.ctypes.data, g.ctypes.data))
         return lp, g
 
     def set_prior(self, alpha=None, beta=None):

@@ -281,6 +281,10 @@ class Stark:
         1 x 1 weight block of its own and the parameters are combined from their own
         covariance (engine.consensus).  permuted=False keeps chain order in the draws.
 
+        chains= is any count >= 1 (default 1, stark/stark.py:62-63); the regression families run a
+        count that is not one of 1, 2, 4, 8, 16, 64 as contiguous batches of those sizes
+        (engine.chain_batches), one data sweep per batch and step.
+
         Raises stark_amd._lib.LinAlgError when a shard holds too few draws for
         its covariance to be invertible: each shard needs more than P draws, i.e.
         ceil((iter - warmup) / thin) * chains > P (P = the model's parameters + lp__; with separate_lp the

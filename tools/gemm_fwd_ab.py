@@ -178,6 +178,7 @@ int main(int argc, char** argv) {
   void* wsb; CK(hipMalloc(&wsb, stk_sweep_ws_bytes(rows, d, C, nsh)));
   SweepWs ws = stk_sweep_ws(wsb, rows, d, nsh);
   SweepArgs A{sh_d, q, partial, nullptr, 0, C, Dp, G, LD, d + 2, 0, G, nullptr};
+  A.Ct = C;
   A.qT = ws.qT; A.R = ws.R; A.Rrows = ws.Rrows;
   hipLaunchKernelGGL(k_qt_swizzle, dim3((g5_kp(d) * G5_C + 255) / 256, nsh), dim3(256), 0, st, A, d);
   CK(hipStreamSynchronize(st));

@@ -99,6 +99,7 @@ int main(int argc, char** argv) {
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
   SweepArgs A{sh_d, q, partial, nullptr, 0, C, Dp, G, LD, d + 2, 0, G, nullptr};
+  A.Ct = C;
   const size_t l16 = stk_sweep16_lds_bytes(fam, d);
   // LDS of the committed kernel before beta moved to registers (its block image of beta for
   // KF < 28 beside the slots), which the legacy k_sweepe arm also fits in

@@ -226,6 +226,7 @@ int main(int argc, char** argv) {
     hipLaunchKernelGGL(k_stream, dim3(nsh * G), dim3(256), 0, st, sh_d, G, sink);
   });
   SweepArgs A{sh_d, q, partial, nullptr, 0, C, Dp, G, d | 1, d + 2, 0, G, nullptr};
+  A.Ct = C;
   hipFuncSetAttribute((const void*)k_skeleton<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if ((size_t)64 * (d | 1) * 8 <= 160 * 1024)
     timeit("skeleton", (double)nsh * rows * 8.0 * d, [&] {   // v2's register pipeline, no arithmetic
@@ -240,6 +241,7 @@ int main(int argc, char** argv) {
       const int64_t nt = (rows + 63) / 64;
       int g3 = (int)std::min<int64_t>(512, (nt + 7) / 8);
       SweepArgs A3{sh_d, q, partial, nullptr, 0, C, Dp, g3, nb, d + 2, 0, g3, nullptr};
+      A3.Ct = C;
       char name[32];
       snprintf(name, sizeof name, "skel3 nb%d", nb);
       timeit(name, (double)nsh * rows * 8.0 * d, [&] {
@@ -249,6 +251,7 @@ int main(int argc, char** argv) {
   }
   if (sweep_variant(rows, d, C) == 3) {
     SweepArgs A3{sh_d, q, partial, nullptr, 0, C, Dp, G, LD, d + 2, 0, G, nullptr};
+    A3.Ct = C;
     auto abl = [&](const char* name, auto kern) {
       hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       timeit(name, bytes, [&] { hipLaunchKernelGGL(kern, dim3(nsh * G), dim3(512), lds, st, A3, LD); });
@@ -262,6 +265,7 @@ int main(int argc, char** argv) {
   }
   if (sweep_variant(rows, d, C) == 4 && d == 100) {
     SweepArgs A4{sh_d, q, partial, nullptr, 0, C, Dp, G, LD, d + 2, 0, G, nullptr};
+    A4.Ct = C;
     auto abl = [&](const char* name, auto kern) {
       hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       timeit(name, bytes, [&] { hipLaunchKernelGGL(kern, dim3(nsh * G), dim3(256), lds, st, A4, LD); });
