@@ -15,6 +15,9 @@
  *   stk_log_density_grad_chains the same at any C >= 1, through the chain batches and grouped
  *                               launches of a sampling run (parity hook)
  *   stk_chain_batches           the batches a regression shard's `chains` run as (host only)
+ *   stk_fingerprint_words /     a 64-bit fingerprint of a shard's rows, on the device or the host;
+ *   stk_shard_fingerprint_host / saved sampler states are bound to it (no reference counterpart)
+ *   stk_model_fingerprint
  *   stk_sample / stk_sampler_*  stark/stark.py:48-56  `sm.sampling(data, **kw)` +
  *                               `fit.extract()` -> P x S matrix, for every local partition
  *                               (stark/stark.py:65 mapPartitions(_mcmc(...)))
@@ -183,6 +186,52 @@ STK_API int stk_model_info(const stk_model* m, int shard, int32_t* D, int32_t* P
 STK_API int stk_model_copy_data(stk_model* m, int shard, double* x, double* y, int32_t* y_int);
 STK_API int stk_model_device_bytes(const stk_model* m, int64_t* bytes);
 
+/* ---- data fingerprint: a cheap, position-sensitive 64-bit fingerprint of a shard's rows, computed
+ * where they lie (one HBM-speed read), with a host twin that gives the same bits -- to check rows
+ * before an upload or on another rank, and what a saved sampler state is bound to (below).  It is
+ * not cryptographic: it detects accidents (other rows, swapped rows, one flipped bit, a shifted
+ * slice), not an adversary.  No reference counterpart.  All arithmetic is on unsigned 64-bit
+ * integers, modulo 2^64:
+ *
+ *   K = 0x9E3779B97F4A7C15        M = 0xD6E8FEB86659FD93
+ *   fmix(a):  a ^= a >> 32;  a *= M;  a ^= a >> 29;  return a
+ *   T[0..4] = 0x243F6A8885A308D3, 0x13198A2E03707344, 0xA4093822299F31D0,
+ *             0x082EFA98EC4E6C89, 0x452821E638D01377
+ *   words(w[0..m), tag, index0) = sum over i < m of  fmix( w[i] + (index0 + i + 1) * K + T[tag] )
+ *
+ * A stream of doubles contributes the doubles' bit patterns (-0.0 differs from 0.0, NaN payloads
+ * count); a stream of int32 contributes every element's 32-bit pattern zero-extended to 64 bits,
+ * and its index counts elements.  words is additive over index ranges,
+ * words(a ++ b, t, i0) = words(a, t, i0) + words(b, t, i0 + len(a)), and an integer sum, so every
+ * reduction order gives the same bits.
+ *
+ *   shard fingerprint = fmix( words([family, n_rows, n_cols], 0, 0)     n_cols = 0 for schools
+ *                           + words(x: n_rows * n_cols doubles, row-major, 1, 0)   regressions
+ *                           + words(y doubles, 2, 0)                    linreg, schools
+ *                           + words(y_int int32, 3, 0)                  logreg
+ *                           + words(sigma doubles, 4, 0) )              schools
+ *
+ * Priors are not part of it (the saved state's geometry check covers them).
+ *
+ * stk_fingerprint_words: *sum = words(buf[0..count), tag, index0), word_bytes 8 or 4 (buf aligned
+ * to it).  With a context it runs on the context's device and stream; buf may be device memory
+ * (read in place) or host memory (staged).  ctx == NULL asks for the host twin: buf must be host
+ * memory and no device is needed.  STK_E_ARG: word_bytes not 4 or 8, tag outside 0..4, count < 0,
+ * buf NULL with count > 0; count == 0 gives 0.
+ * stk_shard_fingerprint_host: the fingerprint of one shard of host pointers (the struct
+ * stk_model_create takes, the same pointers required per family); pure host code.
+ * stk_model_fingerprint: the same value from the shard's device arrays; computed at the first
+ * call for that shard and cached (the data never changes after creation), so model creation and
+ * runs that never ask pay nothing. */
+STK_API int stk_fingerprint_words(stk_ctx* ctx, const void* buf, int64_t count, int32_t word_bytes, int32_t tag,
+                                  uint64_t index0, uint64_t* sum);
+STK_API int stk_shard_fingerprint_host(int family, const stk_shard* shard, uint64_t* out);
+STK_API int stk_model_fingerprint(stk_model* m, int shard, uint64_t* out);
+/* The shard's arrays where the model keeps them: *out is filled with n_rows, n_cols and the DEVICE
+ * addresses of x / y / y_int / sigma (NULL for the arrays the family has not), read-only and valid
+ * while the model lives -- e.g. to fingerprint a row range with stk_fingerprint_words. */
+STK_API int stk_model_shard_arrays(const stk_model* m, int shard, stk_shard* out);
+
 /* ---- log density + gradient at C points of one shard (parity hook) ---- */
 STK_API int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, double* lp, double* grad);
 /* lp and gradient of EVERY shard at C points each (parity hook): one sweep launch per group; C
@@ -236,11 +285,19 @@ STK_API int stk_sampler_destroy(stk_sampler* s);
  * on another device -- continues bit for bit as the unsplit run would (the reference has no
  * counterpart: a pystan fit cannot be resumed; SURVEY.md 8 aux "checkpoint/resume").
  * stk_sampler_state_bytes gives the size of the blob; stk_sampler_load_state refuses a blob
- * of another geometry / config (STK_E_ARG) before writing anything.  The data rows themselves
- * are not hashed (that would read the whole shard): loading into a model of the same geometry
- * built from other data is the caller's error and is not detected.  A dense_e sampler's state also
- * carries every chain's M^-1, its Cholesky factor and the window's Welford M2, and the config check
- * includes the metric: a diag_e blob is refused by a dense_e sampler and the reverse. */
+ * of another geometry / config (STK_E_ARG) before writing anything.  The blob (version 2) is also
+ * bound to the data: after its header it carries the fingerprint of every shard
+ * (stk_model_fingerprint, computed on the device the first time a state is saved or loaded and
+ * cached in the model), and a model of the same geometry built from other rows -- another
+ * data_seed, another file, another rank's slice, one flipped bit -- is refused with STK_E_ARG
+ * "the state was saved against other data (shard s)", again before anything is written.  A
+ * version-1 blob (no fingerprints) is refused with a message that names its version.  A dense_e
+ * sampler's state also carries every chain's M^-1, its Cholesky factor and the window's Welford
+ * M2, and the config check includes the metric: a diag_e blob is refused by a dense_e sampler and
+ * the reverse.  Full-data mode is part of the config check too: a blob saved by a sampler with an
+ * all-reduce callback and a plain sampler refuse each other.  A full-data resume is, in this order,
+ * stk_sampler_create -> stk_sampler_set_allreduce -> stk_sampler_load_state: set_allreduce needs a
+ * sampler that has not run (and moves the [grad | lp] block, which load_state then fills). */
 STK_API int stk_sampler_state_bytes(stk_sampler* s, int64_t* bytes);
 STK_API int stk_sampler_save_state(stk_sampler* s, void* buf, int64_t bytes);
 STK_API int stk_sampler_load_state(stk_sampler* s, const void* buf, int64_t bytes);

@@ -85,6 +85,10 @@ SIGNATURES = [
                                       ctypes.POINTER(_i64)]),
     ("stk_model_copy_data", ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
     ("stk_model_device_bytes", ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),
+    ("stk_fingerprint_words", ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _u64, ctypes.POINTER(_u64)]),
+    ("stk_shard_fingerprint_host", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Shard), ctypes.POINTER(_u64)]),
+    ("stk_model_fingerprint", ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(_u64)]),
+    ("stk_model_shard_arrays", ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(Shard)]),
     ("stk_log_density_grad", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _vp, _vp]),
     ("stk_log_density_grad_shards", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp]),
     ("stk_log_density_grad_chains", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp]),

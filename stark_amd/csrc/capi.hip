@@ -45,6 +45,10 @@ size_t stk_general_inverse_work_bytes(int P);
 hipError_t stk_launch_consensus_solve(const double* sum_w, const double* sum_wtheta, int P, int S, double* inv_buf,
                                       double* work, int32_t* status, double* out, hipStream_t st, bool general);
 size_t stk_spd_inverse_work_bytes(int P, int batch);
+uint64_t stk_fp_fmix(uint64_t a);
+uint64_t stk_fp_words_host(const void* buf, int64_t count, int word_bytes, int tag, uint64_t index0);
+hipError_t stk_launch_fp_words(const void* buf, int64_t count, int word_bytes, int tag, uint64_t index0,
+                               unsigned long long* sum, hipStream_t st);
 
 // ---------------------------------------------------------------- errors
 static thread_local char g_err[1024] = "";
@@ -117,6 +121,8 @@ struct stk_model {
   std::vector<DevBuf> bufs;
   DevBuf sh_dev;
   int64_t bytes = 0;
+  std::vector<uint64_t> fp;   // shard fingerprints, computed on first use (the data never changes)
+  std::vector<char> fp_ok;
 };
 
 // The chain counts that are ONE sweep launch in the two single-launch parity hooks (stk_log_density_grad's
@@ -245,6 +251,8 @@ struct stk_sampler {
   std::vector<int> iv_host;
   std::vector<unsigned long long> cnt_host;
 };
+
+static int model_fingerprint(stk_model* m, int shard, uint64_t* out);   // cached; with the fingerprint entry points
 
 extern "C" {
 
@@ -1222,10 +1230,11 @@ int stk_sampler_iterations(stk_sampler* s, int32_t* iters) {
 }  // extern "C"
 
 // ---------------------------------------------------------------- checkpoint / resume
-// Blob: StateHeader, then the device segments in state_segments() order.  The header's
-// geometry hash covers everything that shapes the state or its evolution (model family and
-// shard geometry, priors, every sampler setting, the RNG seed and shard ids), so a blob only
-// loads into a sampler that continues the same run.
+// Blob (version 2): StateHeader, one uint64 data fingerprint per shard (stk_model_fingerprint),
+// then the device segments in state_segments() order.  The header's geometry hash covers
+// everything that shapes the state or its evolution (model family and shard geometry, priors,
+// every sampler setting, the RNG seed and shard ids, full-data mode) and the fingerprints cover
+// the rows, so a blob only loads into a sampler that continues the same run on the same data.
 namespace {
 struct StateHeader {
   char magic[8];
@@ -1240,6 +1249,7 @@ struct Seg {
   size_t bytes;
 };
 const char kStateMagic[8] = {'S', 'T', 'K', 'S', 'T', 'A', 'T', 'E'};
+constexpr uint32_t kStateVersion = 2;   // 1: no fingerprints after the header
 
 std::vector<Seg> state_segments(const stk_sampler* s) {
   const NutsArgs& A = s->A;
@@ -1283,6 +1293,7 @@ int state_geometry(const stk_sampler* s, uint64_t* out) {
   f.add(A.delta), f.add(A.gamma), f.add(A.kappa), f.add(A.t0), f.add(A.seed), f.add(A.jitter);
   f.add(A.uturn_ext), f.add(A.cpw_cap), f.add(A.ud_first), f.add(A.ud_iters), f.add(s->nch);
   if (A.metric) f.add(A.metric);   // diag_e blobs keep the hash they always had
+  f.add((int)(s->ar_fn != nullptr));   // full-data mode: its [grad | lp] block holds sums over ranks
   std::vector<int32_t> ids(m->nshards);
   for (int i = 0; i < m->nshards; ++i) ids[i] = i;
   if (A.shard_ids)
@@ -1297,7 +1308,7 @@ extern "C" {
 
 int stk_sampler_state_bytes(stk_sampler* s, int64_t* bytes) {
   ARG_CHECK(s && bytes, "stk_sampler_state_bytes: bad arguments");
-  size_t n = sizeof(StateHeader);
+  size_t n = sizeof(StateHeader) + sizeof(uint64_t) * (size_t)s->m->nshards;
   for (const Seg& g : state_segments(s)) n += g.bytes;
   *bytes = (int64_t)n;
   return STK_OK;
@@ -1314,9 +1325,11 @@ int stk_sampler_save_state(stk_sampler* s, void* buf, int64_t bytes) {
   const auto segs = state_segments(s);
   StateHeader h{};
   memcpy(h.magic, kStateMagic, 8);
-  h.version = 1;
+  h.version = kStateVersion;
   h.nsegs = (uint32_t)segs.size();
   RC(state_geometry(s, &h.geometry));
+  std::vector<uint64_t> fps(s->m->nshards);
+  for (int sh = 0; sh < s->m->nshards; ++sh) RC(model_fingerprint(s->m, sh, &fps[sh]));
   h.step = s->step;
   h.steps = s->steps;
   h.sweeps = s->sweeps;
@@ -1325,7 +1338,8 @@ int stk_sampler_save_state(stk_sampler* s, void* buf, int64_t bytes) {
   for (size_t i = 0; i < segs.size(); ++i) h.seg_bytes[i] = segs[i].bytes;
   char* out = static_cast<char*>(buf);
   memcpy(out, &h, sizeof(h));
-  size_t off = sizeof(h);
+  memcpy(out + sizeof(h), fps.data(), sizeof(uint64_t) * fps.size());
+  size_t off = sizeof(h) + sizeof(uint64_t) * fps.size();
   for (const Seg& g : segs) {
     STK_HIP_CHECK(hipMemcpyAsync(out + off, g.p, g.bytes, hipMemcpyDefault, ctx->stream));
     off += g.bytes;
@@ -1341,6 +1355,10 @@ int stk_sampler_load_state(stk_sampler* s, const void* buf, int64_t bytes) {
   if (bytes >= (int64_t)sizeof(StateHeader)) {   // another metric: said so, before the sizes are compared
     StateHeader h0;
     memcpy(&h0, buf, sizeof(h0));
+    ARG_CHECK(memcmp(h0.magic, kStateMagic, 8) || h0.version == kStateVersion,
+              "stk_sampler_load_state: the blob is a version %u sampler state, this library reads version %u "
+              "(version 1 carries no data fingerprints): save the state again with this library",
+              h0.version, kStateVersion);
     ARG_CHECK(memcmp(h0.magic, kStateMagic, 8) || h0.nsegs == state_segments(s).size(),
               "stk_sampler_load_state: the state was saved with another metric (%u segments, this sampler has %zu)",
               h0.nsegs, state_segments(s).size());
@@ -1354,12 +1372,19 @@ int stk_sampler_load_state(stk_sampler* s, const void* buf, int64_t bytes) {
   const auto segs = state_segments(s);
   uint64_t geo = 0;
   RC(state_geometry(s, &geo));
-  ARG_CHECK(!memcmp(h.magic, kStateMagic, 8) && h.version == 1, "stk_sampler_load_state: not a sampler state blob");
+  ARG_CHECK(!memcmp(h.magic, kStateMagic, 8) && h.version == kStateVersion,
+            "stk_sampler_load_state: not a sampler state blob");
   ARG_CHECK(h.geometry == geo && h.nsegs == segs.size(),
             "stk_sampler_load_state: the state belongs to another model geometry or sampler config");
   for (size_t i = 0; i < segs.size(); ++i)
     ARG_CHECK(h.seg_bytes[i] == segs[i].bytes, "stk_sampler_load_state: segment %zu size mismatch", i);
   const char* in = static_cast<const char*>(buf) + sizeof(h);
+  for (int sh = 0; sh < s->m->nshards; ++sh, in += sizeof(uint64_t)) {   // the rows, not only their shape
+    uint64_t saved, mine;
+    memcpy(&saved, in, sizeof(saved));
+    RC(model_fingerprint(s->m, sh, &mine));
+    ARG_CHECK(saved == mine, "stk_sampler_load_state: the state was saved against other data (shard %d)", sh);
+  }
   for (const Seg& g : segs) {
     STK_HIP_CHECK(hipMemcpyAsync(g.p, in, g.bytes, hipMemcpyDefault, ctx->stream));
     in += g.bytes;
@@ -1613,6 +1638,119 @@ int stk_consensus_blocked(stk_ctx* ctx, const double* draws, int32_t nshards, in
                           const int32_t* row_block, double* out, int32_t* shard_used) {
   ARG_CHECK(out && row_block, "stk_consensus_blocked: out / row_block is NULL");
   return consensus_run(ctx, draws, nshards, P, S, row_block, nullptr, nullptr, out, shard_used);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- data fingerprint
+// words() of the header: words([family, n_rows, n_cols], 0, 0).
+static uint64_t fp_shard_header(int family, int64_t n_rows, int n_cols) {
+  const uint64_t h[3] = {(uint64_t)family, (uint64_t)n_rows, (uint64_t)(family == STK_SCHOOLS ? 0 : n_cols)};
+  return stk_fp_words_host(h, 3, 8, 0, 0);
+}
+
+// One kernel per data array of the shard, all adding into one zeroed device word; cached.
+static int model_fingerprint(stk_model* m, int shard, uint64_t* out) {
+  if (m->fp_ok.size() != (size_t)m->nshards) {
+    m->fp.assign(m->nshards, 0);
+    m->fp_ok.assign(m->nshards, 0);
+  }
+  if (!m->fp_ok[shard]) {
+    stk_ctx* ctx = m->ctx;
+    STK_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const ShardDev& s = m->sh[shard];
+    RC(ctx->scratch[5].ensure(sizeof(unsigned long long)));
+    unsigned long long* sum = ctx->scratch[5].as<unsigned long long>();
+    STK_HIP_CHECK(hipMemsetAsync(sum, 0, sizeof(*sum), st));
+    if (s.x) STK_HIP_CHECK(stk_launch_fp_words(s.x, s.n * s.d, 8, 1, 0, sum, st));
+    if (s.y) STK_HIP_CHECK(stk_launch_fp_words(s.y, s.n, 8, 2, 0, sum, st));
+    if (s.yi) STK_HIP_CHECK(stk_launch_fp_words(s.yi, s.n, 4, 3, 0, sum, st));
+    if (s.sigma) STK_HIP_CHECK(stk_launch_fp_words(s.sigma, s.n, 8, 4, 0, sum, st));
+    unsigned long long v = 0;
+    STK_HIP_CHECK(hipMemcpyAsync(&v, sum, sizeof(v), hipMemcpyDeviceToHost, st));
+    STK_HIP_CHECK(hipStreamSynchronize(st));
+    m->fp[shard] = stk_fp_fmix(fp_shard_header(m->family, s.n, s.d) + (uint64_t)v);
+    m->fp_ok[shard] = 1;
+  }
+  *out = m->fp[shard];
+  return STK_OK;
+}
+
+extern "C" {
+
+int stk_fingerprint_words(stk_ctx* ctx, const void* buf, int64_t count, int32_t word_bytes, int32_t tag,
+                          uint64_t index0, uint64_t* sum) {
+  ARG_CHECK(sum, "stk_fingerprint_words: sum is NULL");
+  ARG_CHECK(word_bytes == 4 || word_bytes == 8, "stk_fingerprint_words: word_bytes must be 4 or 8, got %d", word_bytes);
+  ARG_CHECK(tag >= 0 && tag <= 4, "stk_fingerprint_words: tag must be in 0..4, got %d", tag);
+  ARG_CHECK(count >= 0, "stk_fingerprint_words: count must be >= 0");
+  ARG_CHECK(buf || count == 0, "stk_fingerprint_words: buf is NULL");
+  ARG_CHECK(((uintptr_t)buf & (uintptr_t)(word_bytes - 1)) == 0, "stk_fingerprint_words: buf is not aligned to %d bytes",
+            word_bytes);
+  *sum = 0;
+  if (count == 0) return STK_OK;
+  if (!ctx) {   // the caller asked for the host twin: no device is touched
+    *sum = stk_fp_words_host(buf, count, word_bytes, tag, index0);
+    return STK_OK;
+  }
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  RC(ctx->scratch[5].ensure(sizeof(unsigned long long)));
+  unsigned long long* acc = ctx->scratch[5].as<unsigned long long>();
+  STK_HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(*acc), st));
+  if (is_device_ptr(buf, ctx->device)) {
+    STK_HIP_CHECK(stk_launch_fp_words(buf, count, word_bytes, tag, index0, acc, st));
+  } else {   // host (or another device's) memory: staged in pieces, words() is additive over index ranges
+    const int64_t piece = ((int64_t)64 << 20) / word_bytes;
+    RC(ctx->scratch[6].ensure((size_t)std::min(count, piece) * word_bytes));
+    const char* src = static_cast<const char*>(buf);
+    for (int64_t i0 = 0; i0 < count; i0 += piece) {
+      const int64_t n = std::min(piece, count - i0);
+      STK_HIP_CHECK(hipMemcpyAsync(ctx->scratch[6].p, src + i0 * word_bytes, (size_t)n * word_bytes, hipMemcpyDefault, st));
+      STK_HIP_CHECK(stk_launch_fp_words(ctx->scratch[6].p, n, word_bytes, tag, index0 + (uint64_t)i0, acc, st));
+    }
+  }
+  unsigned long long v = 0;
+  STK_HIP_CHECK(hipMemcpyAsync(&v, acc, sizeof(v), hipMemcpyDeviceToHost, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  *sum = v;
+  return STK_OK;
+}
+
+int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
+  ARG_CHECK(sh && out, "stk_shard_fingerprint_host: bad arguments");
+  ARG_CHECK(family == STK_SCHOOLS || family == STK_LINREG || family == STK_LOGREG, "unknown model family %d", family);
+  ARG_CHECK(sh->n_rows > 0, "stk_shard_fingerprint_host: n_rows must be positive");
+  uint64_t acc = fp_shard_header(family, sh->n_rows, sh->n_cols);
+  if (family == STK_SCHOOLS) {
+    ARG_CHECK(sh->y && sh->sigma, "stk_shard_fingerprint_host: schools needs y and sigma");
+    acc += stk_fp_words_host(sh->y, sh->n_rows, 8, 2, 0) + stk_fp_words_host(sh->sigma, sh->n_rows, 8, 4, 0);
+  } else {
+    ARG_CHECK(sh->x && sh->n_cols > 0, "stk_shard_fingerprint_host: regression needs x");
+    acc += stk_fp_words_host(sh->x, sh->n_rows * sh->n_cols, 8, 1, 0);
+    if (family == STK_LOGREG) {
+      ARG_CHECK(sh->y_int, "stk_shard_fingerprint_host: logreg needs y_int");
+      acc += stk_fp_words_host(sh->y_int, sh->n_rows, 4, 3, 0);
+    } else {
+      ARG_CHECK(sh->y, "stk_shard_fingerprint_host: linreg needs y");
+      acc += stk_fp_words_host(sh->y, sh->n_rows, 8, 2, 0);
+    }
+  }
+  *out = stk_fp_fmix(acc);
+  return STK_OK;
+}
+
+int stk_model_shard_arrays(const stk_model* m, int shard, stk_shard* out) {
+  ARG_CHECK(m && out && shard >= 0 && shard < m->nshards, "stk_model_shard_arrays: bad arguments");
+  const ShardDev& s = m->sh[shard];
+  *out = stk_shard{s.n, s.d, s.x, s.y, s.yi, s.sigma};
+  return STK_OK;
+}
+
+int stk_model_fingerprint(stk_model* m, int shard, uint64_t* out) {
+  ARG_CHECK(m && out && shard >= 0 && shard < m->nshards, "stk_model_fingerprint: bad arguments");
+  return model_fingerprint(m, shard, out);
 }
 
 }  // extern "C"

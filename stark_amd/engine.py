@@ -187,6 +187,79 @@ def chain_batches(chains: int, n_cols: int) -> list[int]:
     return [int(v) for v in sizes[:n]]
 
 
+def _host_shard(family, sh):
+    """One shard dict ({"y", "sigma"} or {"x", "y"}) as a ``stk_shard`` of host pointers, plus the
+    arrays that keep those pointers alive."""
+    if family == STK_SCHOOLS:
+        y = np.ascontiguousarray(sh["y"], np.float64)
+        sig = np.ascontiguousarray(sh["sigma"], np.float64)
+        if y.shape != sig.shape or y.ndim != 1:
+            raise ValueError("schools shard: y and sigma must be equal-length vectors")
+        return Shard(len(y), 0, None, y.ctypes.data, None, sig.ctypes.data), [y, sig]
+    x = np.ascontiguousarray(sh["x"], np.float64)
+    if x.ndim != 2:
+        raise ValueError("regression shard: x must be N x K")
+    if family == STK_LOGREG:
+        y = np.ascontiguousarray(sh["y"], np.int32)
+        if np.any((y != 0) & (y != 1)):
+            raise ValueError("bernoulli_logit: y must be 0 or 1")
+        shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, None, y.ctypes.data, None)
+    else:
+        y = np.ascontiguousarray(sh["y"], np.float64)
+        shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, y.ctypes.data, None, None)
+    if y.shape[0] != x.shape[0]:
+        raise ValueError("x and y row counts differ")
+    return shard, [x, y]
+
+
+_WORD_BYTES = {np.dtype(np.float64): 8, np.dtype(np.uint64): 8, np.dtype(np.int32): 4}
+
+
+def fingerprint_words(buf, tag: int, index0: int = 0, ctx: "Context | None" = None, count: int | None = None,
+                      word_bytes: int = 8) -> np.uint64:
+    """``words(buf, tag, index0)`` of the data fingerprint (stk_fingerprint_words; the definition is in
+    ``include/stark_hip.h``): the position-sensitive sum over a stream of 8- or 4-byte words.
+
+    buf: a numpy array of float64 / uint64 (8-byte words) or int32 (4-byte words, zero-extended), a
+    cuda torch tensor of such a dtype, or a device address (int) with ``count`` words of ``word_bytes``.
+    ctx: None runs the host twin (numpy input only, no device needed); a Context runs the kernel on
+    its device -- host arrays are staged, device memory is read where it lies."""
+    if isinstance(buf, (int, np.integer)):
+        if ctx is None or count is None:
+            raise ValueError("a device address needs ctx and count")
+        ptr, n, wb = int(buf), int(count), int(word_bytes)
+    else:
+        if isinstance(buf, np.ndarray):
+            dt = buf.dtype
+        elif hasattr(buf, "data_ptr"):
+            if ctx is None and buf.is_cuda:
+                raise ValueError("a device tensor needs ctx")
+            dt = np.dtype(str(buf.dtype).replace("torch.", ""))
+        else:
+            raise TypeError(f"unsupported buffer type {type(buf)}")
+        if dt not in _WORD_BYTES:
+            raise TypeError(f"fingerprint_words takes float64, uint64 or int32 words, got {dt}")
+        ptr, wb = _ptr(buf), _WORD_BYTES[dt]
+        n = int(buf.size if isinstance(buf, np.ndarray) else buf.numel())
+    out = ctypes.c_uint64()
+    check(_lib.load().stk_fingerprint_words(ctx._h if ctx is not None else None, ctypes.c_void_p(ptr), n, wb,
+                                            int(tag), int(index0) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(out)))
+    return np.uint64(out.value)
+
+
+def shard_fingerprint(family, shard) -> np.uint64:
+    """The data fingerprint of one shard of host rows -- the dict ``Model`` takes -- computed on the
+    host (stk_shard_fingerprint_host): equal to ``Model.fingerprint(s)`` of a model holding these
+    rows as shard s, so rows can be checked before an upload, or on another rank."""
+    fam = FAMILIES.get(family, family)
+    if fam not in FAMILY_NAMES:
+        raise ValueError(f"unknown model family {family!r}")
+    sh, _held = _host_shard(fam, shard)
+    out = ctypes.c_uint64()
+    check(_lib.load().stk_shard_fingerprint_host(fam, ctypes.byref(sh), ctypes.byref(out)))
+    return np.uint64(out.value)
+
+
 class Model:
     """Shards of one model family resident on one device (``stk_model``)."""
 
@@ -212,28 +285,8 @@ class Model:
         keep = []
         arr = (Shard * len(shards))()
         for i, sh in enumerate(shards):
-            if self.family == STK_SCHOOLS:
-                y = np.ascontiguousarray(sh["y"], np.float64)
-                sig = np.ascontiguousarray(sh["sigma"], np.float64)
-                if y.shape != sig.shape or y.ndim != 1:
-                    raise ValueError("schools shard: y and sigma must be equal-length vectors")
-                keep += [y, sig]
-                arr[i] = Shard(len(y), 0, None, y.ctypes.data, None, sig.ctypes.data)
-            else:
-                x = np.ascontiguousarray(sh["x"], np.float64)
-                if x.ndim != 2:
-                    raise ValueError("regression shard: x must be N x K")
-                if self.family == STK_LOGREG:
-                    y = np.ascontiguousarray(sh["y"], np.int32)
-                    if np.any((y != 0) & (y != 1)):
-                        raise ValueError("bernoulli_logit: y must be 0 or 1")
-                    arr[i] = Shard(x.shape[0], x.shape[1], x.ctypes.data, None, y.ctypes.data, None)
-                else:
-                    y = np.ascontiguousarray(sh["y"], np.float64)
-                    arr[i] = Shard(x.shape[0], x.shape[1], x.ctypes.data, y.ctypes.data, None, None)
-                if y.shape[0] != x.shape[0]:
-                    raise ValueError("x and y row counts differ")
-                keep += [x, y]
+            arr[i], held = _host_shard(self.family, sh)
+            keep += held
         h = ctypes.c_void_p()
         check(_lib.load().stk_model_create(self.ctx._h, self.family, arr, len(shards), ctypes.byref(h)))
         return h
@@ -265,6 +318,36 @@ class Model:
         v = ctypes.c_int64()
         check(_lib.load().stk_model_device_bytes(self._h, ctypes.byref(v)))
         return v.value
+
+    def fingerprint(self, shard: int | None = None):
+        """The data fingerprint of one shard (np.uint64), or of every shard (an array of nshards
+        values) when `shard` is None (stk_model_fingerprint): one read of the shard's device arrays
+        at the first call, cached afterwards.  ``shard_fingerprint`` gives the same value from host
+        rows; a saved sampler state only loads into a model whose fingerprints match."""
+        lib = _lib.load()
+        out = np.zeros(self.nshards, np.uint64)
+        for s in (range(self.nshards) if shard is None else [int(shard)]):
+            v = ctypes.c_uint64()
+            check(lib.stk_model_fingerprint(self._h, s, ctypes.byref(v)))
+            if shard is not None:
+                return np.uint64(v.value)
+            out[s] = v.value
+        return out
+
+    def device_arrays(self, shard: int) -> dict:
+        """Device addresses of the shard's arrays with their word counts (stk_model_shard_arrays):
+        {"x": (ptr, n * d), "y": (ptr, n), ...} for the arrays the family has ("y" of a logistic
+        shard is int32).  Read-only, valid while the model lives."""
+        sh = Shard()
+        check(_lib.load().stk_model_shard_arrays(self._h, int(shard), ctypes.byref(sh)))
+        out = {}
+        if sh.x:
+            out["x"] = (sh.x, sh.n_rows * sh.n_cols)
+        if sh.y or sh.y_int:
+            out["y"] = (sh.y or sh.y_int, sh.n_rows)
+        if sh.sigma:
+            out["sigma"] = (sh.sigma, sh.n_rows)
+        return out
 
     def copy_data(self, shard: int):
         n, D = self.n_rows[shard], self.D[shard]
@@ -416,9 +499,10 @@ class Sampler:
 
     def save_state(self) -> np.ndarray:
         """The run so far as a byte blob (uint8 array): every chain's device state, the draws
-        and the step counters (stk_sampler_save_state).  load_state() of the blob into a sampler
-        of the same model geometry and config -- in another process, on another GPU --
-        continues the run bit for bit as if it had never stopped."""
+        and the step counters (stk_sampler_save_state), behind a header that carries the data
+        fingerprint of every shard.  load_state() of the blob into a sampler of the same model
+        geometry, config and data -- in another process, on another GPU -- continues the run bit
+        for bit as if it had never stopped."""
         n = ctypes.c_int64()
         lib = _lib.load()
         check(lib.stk_sampler_state_bytes(self._h, ctypes.byref(n)))
@@ -427,7 +511,11 @@ class Sampler:
         return buf
 
     def load_state(self, blob) -> "Sampler":
-        """Resume a run saved by save_state() (raises StarkHipError on another geometry / config)."""
+        """Resume a run saved by save_state().  Raises StarkHipError (STK_E_ARG) before anything is
+        written when the blob belongs to another model geometry or sampler config (full-data mode
+        included: call set_allreduce() before load_state()), when it is a version-1 blob, or when the
+        model holds other rows than the run was saved with: "the state was saved against other data
+        (shard s)" -- every shard's fingerprint (Model.fingerprint) is compared."""
         buf = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob,
                                    np.uint8)
         check(_lib.load().stk_sampler_load_state(self._h, buf.ctypes.data, buf.size))
