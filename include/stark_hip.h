@@ -15,6 +15,7 @@
  *   stk_log_density_grad_chains the same at any C >= 1, through the chain batches and grouped
  *                               launches of a sampling run (parity hook)
  *   stk_chain_batches           the batches a regression shard's `chains` run as (host only)
+ *   stk_sweep_launch_info       the kernel and launch shape one batch's sweep has at (rows, d, C) (host only)
  *   stk_fingerprint_words /     a 64-bit fingerprint of a shard's rows, on the device or the host;
  *   stk_shard_fingerprint_host / saved sampler states are bound to it (no reference counterpart)
  *   stk_model_fingerprint
@@ -249,6 +250,16 @@ STK_API int stk_log_density_grad_chains(stk_model* m, const double* q, int32_t C
  * sweep covers d).  Chain c of shard s keeps RNG stream shard_ids[s] * chains + c, and every
  * layout (draws, stats, the full-data block, the saved state) is that of a single batch. */
 STK_API int stk_chain_batches(int32_t C, int32_t d, int32_t* sizes, int32_t cap);
+/* The sweep that one batch of C chains (a size stk_chain_batches returns) runs over a shard of
+ * n_rows rows and d covariates, as the sampler and the parity hooks launch it.  out[0] kind: 1 k_sweep,
+ * 2 k_sweep2, 3 k_sweep3, 4 k_sweep16, 5 the 64-chain GEMM passes, 6 k_sweep16w; out[1] rows per tile;
+ * out[2] the kernel's LD argument (kinds 1, 2: LDS row stride in doubles; 3: ring slots per wave; 4: 1;
+ * 5: 0; 6: waves per block); out[3] chunks per shard; out[4] dynamic LDS bytes per block; out[5] bytes
+ * of 64-chain workspace per shard (0 unless kind 5).  A pure host function of (n_rows, d, C): needs no
+ * device.  STK_E_ARG when C is not a batch size at d, or when no sweep covers the shape (a shard so
+ * long that one of its chunks does not fit a buffer descriptor) -- the shapes stk_sampler_create and
+ * the stk_log_density_grad* hooks refuse with the same code before they launch anything. */
+STK_API int stk_sweep_launch_info(int64_t n_rows, int32_t d, int32_t C, int64_t out[6]);
 
 /* ---- sampling: stark/stark.py:43-56 for every shard of the model ---- */
 STK_API int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out);

@@ -93,6 +93,7 @@ SIGNATURES = [
     ("stk_log_density_grad_shards", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp]),
     ("stk_log_density_grad_chains", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp]),
     ("stk_chain_batches", ctypes.c_int, [_i32, _i32, _vp, _i32]),
+    ("stk_sweep_launch_info", ctypes.c_int, [_i64, _i32, _i32, _vp]),
     ("stk_sampler_create", ctypes.c_int, [_vp, ctypes.POINTER(Config), _pp]),
     ("stk_sampler_run", ctypes.c_int, [_vp, _i32, _i64]),
     ("stk_sampler_info", ctypes.c_int, [_vp, ctypes.POINTER(RunInfo)]),
@@ -143,6 +144,8 @@ def load():
             pass
     lib = ctypes.CDLL(LIB_PATH)
     for name, res, args in SIGNATURES:
+        if "STARK_HIP_LIB" in os.environ and not hasattr(lib, name):
+            continue   # an A/B arm built from an older revision (tools/lib_ab.py) lacks the newer entry points
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -8,47 +8,10 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.h"
+#include "launchers.h"
 #include <cmath>
 
 using namespace stk;
-
-// ---- kernels' launchers (other translation units)
-int stk_nch_for(int Dmax);
-size_t stk_fused_lds_bytes(const NutsArgs& A, int nch);
-hipError_t stk_launch_nuts_init(const NutsArgs& A, const double* init, const double* inv_metric, double stepsize,
-                                double init_radius, hipStream_t st);
-hipError_t stk_launch_nuts_step(const NutsArgs& A, int nch, int step_id, int pause_at, hipStream_t st);
-hipError_t stk_launch_nuts_fused(const NutsArgs& A, int nch, int pause_at, int max_steps, hipStream_t st);
-hipError_t stk_launch_dense_init(const NutsArgs& A, const double* minv0, const double* chol0, hipStream_t st);
-hipError_t stk_launch_nuts_step_dense(const NutsArgs& A, int nch, int step_id, int pause_at, hipStream_t st);
-hipError_t stk_launch_schools_lpgrad(const ShardDev* shards, int shard, int nch, const double* q, int C, int Dp,
-                                     double* lp, double* g, hipStream_t st);
-void stk_sweep_geometry(int64_t n, int d, int* T, int* LD, int* G, size_t* lds_bytes, int C);
-bool stk_sweep_supported(int C, int d);
-hipError_t stk_launch_sweep(int family, const ShardDev* shards_dev, int shard0, int nsh, int64_t n, int d, int T, int LD, int G,
-                            int Gs, size_t lds, const double* q, int C, int Dp, double* partial, const int* req_step,
-                            int step_id, int* ran, hipStream_t st, const SweepWs* ws = nullptr, int Ct = 0, int c0 = 0);
-size_t stk_sweep_ws_bytes(int64_t n_max, int d, int C, int nshards);
-SweepWs stk_sweep_ws(void* base, int64_t n_max, int d, int nshards);
-hipError_t stk_launch_sweep_reduce(int family, const ShardDev* shards_dev, int shard0, int nsh, int d, int G, int Gs,
-                                   const double* q, int C, int Dp, double* partial, const int* req_step, int step_id,
-                                   double* lp_out, double* g_out, hipStream_t st, int Ct = 0, int c0 = 0);
-hipError_t stk_launch_check_y01(const int32_t* y, int64_t n, int64_t* first, hipStream_t st);
-hipError_t stk_launch_gen_shard(double* X, double* yd, int32_t* yi, int64_t nrows, int d, int64_t grow0,
-                                uint64_t seed, double alpha, const double* beta, double noise_sigma, int family,
-                                hipStream_t st);
-hipError_t stk_launch_consensus_products(const double* X, int nshards, int P, int S, const int32_t* blk, double* mean,
-                                         int32_t* rowbad, int32_t* used, int32_t* status, double* cov, double* W,
-                                         double* work, double* sum_w, double* sum_wtheta, hipStream_t st);
-size_t stk_general_inverse_work_bytes(int P);
-hipError_t stk_launch_consensus_solve(const double* sum_w, const double* sum_wtheta, int P, int S, double* inv_buf,
-                                      double* work, int32_t* status, double* out, hipStream_t st, bool general);
-size_t stk_spd_inverse_work_bytes(int P, int batch);
-uint64_t stk_fp_fmix(uint64_t a);
-uint64_t stk_fp_words_host(const void* buf, int64_t count, int word_bytes, int tag, uint64_t index0);
-hipError_t stk_launch_fp_words(const void* buf, int64_t count, int word_bytes, int tag, uint64_t index0,
-                               unsigned long long* sum, hipStream_t st);
 
 // ---------------------------------------------------------------- errors
 static thread_local char g_err[1024] = "";
@@ -130,40 +93,11 @@ struct stk_model {
 // sampler batched chains -- 16 only where k_sweep16 itself runs (d <= 128).
 static bool hook_single_launch(int C, int d) { return stk_sweep_supported(C, d) && (C != 16 || d <= 128); }
 
-// The grouped sweep launches of a regression model at C chains per shard: consecutive shards of
-// equal n share one launch of nsh * G blocks; every shard's partial sums lie Gs = max G chunks
-// apart.  One construction for every batch of the sampler (chain_plan) and the multi-shard parity hooks.
-struct SweepGroup { int shard0, nsh, T, LD, G; size_t lds; };
-struct SweepPlan {
-  std::vector<SweepGroup> groups;
-  int Gs = 1;
-  int64_t nmax = 0;
-  size_t partial_bytes = 0;   // [nshards][Gs][C][d + 2] doubles
-  size_t ws_bytes = 0;        // v5 workspace for every shard (0 for the other variants)
-};
-static SweepPlan sweep_plan(const stk_model* m, int C) {
-  SweepPlan p;
-  for (int sh = 0; sh < m->nshards;) {
-    SweepGroup gr{};
-    gr.shard0 = sh;
-    stk_sweep_geometry(m->sh[sh].n, m->d, &gr.T, &gr.LD, &gr.G, &gr.lds, C);
-    int e = sh + 1;
-    while (e < m->nshards && m->sh[e].n == m->sh[sh].n) ++e;
-    gr.nsh = e - sh;
-    p.Gs = std::max(p.Gs, gr.G);
-    p.groups.push_back(gr);
-    sh = e;
-  }
-  for (int sh = 0; sh < m->nshards; ++sh) p.nmax = std::max<int64_t>(p.nmax, m->sh[sh].n);
-  p.partial_bytes = sizeof(double) * (size_t)m->nshards * p.Gs * C * (m->d + 2);
-  p.ws_bytes = stk_sweep_ws_bytes(p.nmax, m->d, C, m->nshards);
-  return p;
-}
-
 // The chain batches of a regression shard's C chains: greedy, largest first, over the single-launch
-// sizes {64, 16, 8, 4, 2, 1} a sweep covers at d (stk_sweep_supported: the ONE place that says
-// whether 16 is a batch size at d).  A pure function of (C, d) -- never of n, the shard count or
-// the device -- so every rank derives the same plan.  No padding, no idle chains.
+// sizes {64, 16, 8, 4, 2, 1} a sweep covers at d (stk_sweep_supported, sweep.hip, says whether 16
+// is a batch size at d; stk_sweep_plan then picks each batch's kernel).  A pure function of
+// (C, d) -- never of n, the shard count or the device -- so every rank derives the same plan.
+// No padding, no idle chains.
 static std::vector<int> chain_batches(int C, int d) {
   std::vector<int> b;
   for (const int sz : {64, 16, 8, 4, 2, 1}) {
@@ -174,61 +108,118 @@ static std::vector<int> chain_batches(int C, int d) {
   return b;
 }
 
-// A run's sweeps at Ct chains per shard: every batch has its own grouped launches (sweep_plan at
-// the batch's size), its own region of the partial-sum buffer and its first chain c0; the 64-chain
-// workspace is one, reused by successive 64-batches on the stream.
+// A run's sweeps over shards [first, first + count) at Ct chains per shard, the one construction
+// for the sampler and the parity hooks.  Every chain batch has its first chain c0, its own region
+// of the partial-sum buffer and its grouped launches: consecutive shards of equal n share one
+// launch of nsh * G blocks (stk_sweep_plan decides the kernel and its shape), and every shard's
+// partial sums lie Gs = the batch's largest G chunks apart.  The 64-chain workspace is one, reused
+// by successive 64-batches on the stream.
+struct SweepGroup { int shard0, nsh; SweepLaunch launch; };
 struct ChainBatch {
-  int c0 = 0, C = 0, Gs = 1;
+  int c0 = 0, Gs = 1;
   size_t part_off = 0;        // doubles into the partial-sum buffer
   std::vector<SweepGroup> groups;
 };
 struct ChainPlan {
   std::vector<ChainBatch> batches;
   int Ct = 0;
-  int64_t nmax = 0;
-  size_t partial_bytes = 0, ws_bytes = 0;
+  size_t partial_bytes = 0;   // every batch's [nshards][Gs][C][d + 2] doubles
+  SweepLaunch ws_at{};        // the 64-batch launch of the shard with the most rows (kind 0: no workspace)
+  size_t ws_bytes = 0;        // its workspace for every shard of the model
 };
-static ChainPlan chain_plan(const stk_model* m, int Ct) {
-  ChainPlan cp;
-  cp.Ct = Ct;
-  int c0 = 0;
-  for (const int sz : chain_batches(Ct, m->d)) {
-    SweepPlan p = sweep_plan(m, sz);
+// Refuses, before anything is launched, a shard that no sweep covers at its n, d and batch size.
+static int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int count, ChainPlan* cp) {
+  *cp = ChainPlan();
+  for (const int sz : sizes) {
     ChainBatch b;
-    b.c0 = c0;
-    b.C = sz;
-    b.Gs = p.Gs;
-    b.part_off = cp.partial_bytes / sizeof(double);
-    b.groups = std::move(p.groups);
-    cp.partial_bytes += p.partial_bytes;
-    cp.ws_bytes = std::max(cp.ws_bytes, p.ws_bytes);
-    cp.nmax = p.nmax;
-    cp.batches.push_back(std::move(b));
-    c0 += sz;
+    b.c0 = cp->Ct;
+    b.part_off = cp->partial_bytes / sizeof(double);
+    for (int sh = first; sh < first + count;) {
+      SweepGroup gr{sh, 1, stk_sweep_plan(m->sh[sh].n, m->d, sz, 0)};
+      ARG_CHECK(gr.launch.kind != SWEEP_NONE,
+                "shard %d: no sweep covers n = %lld rows of d = %d covariates at C = %d chains (a chunk of the shard "
+                "must fit a buffer descriptor: split the shard)", sh, (long long)m->sh[sh].n, m->d, sz);
+      while (sh + gr.nsh < first + count && m->sh[sh + gr.nsh].n == m->sh[sh].n) ++gr.nsh;
+      b.Gs = std::max(b.Gs, gr.launch.G);
+      if (gr.launch.ws_bytes > cp->ws_at.ws_bytes) cp->ws_at = gr.launch;
+      b.groups.push_back(gr);
+      sh += gr.nsh;
+    }
+    cp->partial_bytes += sizeof(double) * (size_t)m->nshards * b.Gs * sz * (m->d + 2);
+    cp->Ct += sz;
+    cp->batches.push_back(std::move(b));
   }
-  return cp;
+  cp->ws_bytes = cp->ws_at.ws_bytes * m->nshards;
+  return STK_OK;
 }
-// Every batch's sweep over every shard group; then (plan_reduces) every batch's reduction.
-static hipError_t plan_sweeps(const stk_model* m, const ChainPlan& cp, const ShardDev* shd, const double* q, int Dp,
-                              double* partial, const int* req_step, int step_id, int* ran, const SweepWs* ws,
-                              hipStream_t st) {
-  for (const auto& b : cp.batches)
+// Every batch's sweep over every shard group; then (plan_reduces) every batch's reduction.  `run`
+// holds the run's buffers; a batch's partial-sum region, stride and first chain are filled in here.
+static SweepCall batch_call(const ChainPlan& cp, const ChainBatch& b, SweepCall c) {
+  c.partial += b.part_off;
+  c.Gs = b.Gs;
+  c.Ct = cp.Ct;
+  c.c0 = b.c0;
+  return c;
+}
+static hipError_t plan_sweeps(const stk_model* m, const ChainPlan& cp, const SweepCall& run, hipStream_t st) {
+  for (const auto& b : cp.batches) {
+    const SweepCall c = batch_call(cp, b, run);
     for (const auto& gr : b.groups)
-      if (const hipError_t e = stk_launch_sweep(m->family, shd, gr.shard0, gr.nsh, m->sh[gr.shard0].n, m->d, gr.T, gr.LD,
-                                                gr.G, b.Gs, gr.lds, q, b.C, Dp, partial + b.part_off, req_step, step_id,
-                                                ran, st, ws, cp.Ct, b.c0))
-        return e;
+      if (const hipError_t e = stk_launch_sweep(m->family, gr.launch, gr.shard0, gr.nsh, c, st)) return e;
+  }
   return hipSuccess;
 }
-static hipError_t plan_reduces(const stk_model* m, const ChainPlan& cp, const ShardDev* shd, const double* q, int Dp,
-                               double* partial, const int* req_step, int step_id, double* lp, double* g,
+static hipError_t plan_reduces(const stk_model* m, const ChainPlan& cp, const SweepCall& run, double* lp, double* g,
                                hipStream_t st) {
-  for (const auto& b : cp.batches)
+  for (const auto& b : cp.batches) {
+    const SweepCall c = batch_call(cp, b, run);
     for (const auto& gr : b.groups)
-      if (const hipError_t e = stk_launch_sweep_reduce(m->family, shd, gr.shard0, gr.nsh, m->d, gr.G, b.Gs, q, b.C, Dp,
-                                                       partial + b.part_off, req_step, step_id, lp, g, st, cp.Ct, b.c0))
-        return e;
+      if (const hipError_t e = stk_launch_sweep_reduce(m->family, gr.launch, gr.shard0, gr.nsh, c, lp, g, st)) return e;
+  }
   return hipSuccess;
+}
+
+// The body of the regression parity hooks.  np points of D doubles at q go to rows [row0, row0 +
+// nrows) of the [nshards * plan.Ct][Dp] point buffer (the last point repeated to fill), the plan's
+// sweeps and reductions run, and lp / grad of the first np rows come back.  The caller synchronises.
+static int hook_eval(stk_model* m, const ChainPlan& plan, size_t row0, size_t nrows, const double* q, size_t np,
+                     double* lp, double* grad) {
+  stk_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->stream;
+  const int D = m->Dmax, Dp = (m->Dmax + 7) / 8 * 8;   // one d for every shard of a regression model
+  const size_t rows = (size_t)m->nshards * plan.Ct, pitch = sizeof(double) * Dp, width = sizeof(double) * D;
+  SweepWs ws{};
+  if (plan.ws_bytes) {
+    RC(ctx->scratch[4].ensure(plan.ws_bytes));
+    ws = stk_sweep_ws(ctx->scratch[4].p, plan.ws_at, m->nshards);
+  }
+  RC(ctx->scratch[0].ensure(rows * pitch));
+  RC(ctx->scratch[1].ensure(sizeof(double) * rows));
+  RC(ctx->scratch[2].ensure(rows * pitch));
+  RC(ctx->scratch[3].ensure(plan.partial_bytes));
+  double* qb = ctx->scratch[0].as<double>();
+  double* lpb = ctx->scratch[1].as<double>();
+  double* gb = ctx->scratch[2].as<double>();
+  STK_HIP_CHECK(hipMemcpy2DAsync(qb + row0 * Dp, pitch, q, width, width, np, hipMemcpyDefault, st));
+  for (size_t r = np; r < nrows; ++r)
+    STK_HIP_CHECK(hipMemcpyAsync(qb + (row0 + r) * Dp, q + (np - 1) * D, width, hipMemcpyDefault, st));
+  const SweepCall run{m->sh_dev.as<ShardDev>(), qb, ctx->scratch[3].as<double>(), nullptr, 0, nullptr,
+                      plan.ws_bytes ? &ws : nullptr, Dp, 0, 0, 0};
+  STK_HIP_CHECK(plan_sweeps(m, plan, run, st));
+  STK_HIP_CHECK(plan_reduces(m, plan, run, lpb, gb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(lp, lpb + row0, sizeof(double) * np, hipMemcpyDefault, st));
+  if (grad) STK_HIP_CHECK(hipMemcpy2DAsync(grad, width, gb + row0 * Dp, pitch, width, np, hipMemcpyDefault, st));
+  return STK_OK;
+}
+// Every shard at sum(sizes) points each, in those chain batches.
+static int hook_every_shard(stk_model* m, const std::vector<int>& sizes, const double* q, double* lp, double* grad) {
+  STK_HIP_CHECK(hipSetDevice(m->ctx->device));
+  ChainPlan plan;
+  RC(chain_plan(m, sizes, 0, m->nshards, &plan));
+  const size_t rows = (size_t)m->nshards * plan.Ct;
+  RC(hook_eval(m, plan, 0, rows, q, rows, lp, grad));
+  STK_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  return STK_OK;
 }
 
 struct stk_sampler {
@@ -567,58 +558,29 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
   STK_HIP_CHECK(hipSetDevice(ctx->device));
   const ShardDev& s = m->sh[shard];
   const int D = s.D;
-  const int Dp = (m->Dmax + 7) / 8 * 8;
   hipStream_t st = ctx->stream;
-  const ShardDev* shd = m->sh_dev.as<ShardDev>();
-  if (m->family == STK_SCHOOLS) {
-    RC(ctx->scratch[0].ensure(sizeof(double) * (size_t)C * Dp));
-    RC(ctx->scratch[1].ensure(sizeof(double) * (size_t)C));
-    RC(ctx->scratch[2].ensure(sizeof(double) * (size_t)C * Dp));
-    STK_HIP_CHECK(hipMemcpy2DAsync(ctx->scratch[0].p, sizeof(double) * Dp, q, sizeof(double) * D, sizeof(double) * D,
-                                   C, hipMemcpyDefault, st));
-    STK_HIP_CHECK(stk_launch_schools_lpgrad(shd, shard, stk_nch_for(m->Dmax), ctx->scratch[0].as<double>(), C, Dp,
-                                            ctx->scratch[1].as<double>(), ctx->scratch[2].as<double>(), st));
-  } else {
-    int T, LD, G;
-    size_t lds;
+  if (m->family != STK_SCHOOLS) {
     // the chain batch the sampler's sweep uses: 64 (two-pass fp64 MFMA GEMMs) from 64 points,
-    // 16 (fp64 MFMA) from 16 when d <= 128, else 4 / 2 / 1
+    // 16 (fp64 MFMA) from 16 when d <= 128, else 4 / 2 / 1; this shard alone, the last point
+    // repeated to fill the last batch (the kernel reads rows shard * Cb + c of the point buffer)
     const int Cb = C <= 1 ? 1 : (C <= 2 ? 2 : (C >= 64 ? 64 : (C < 16 || !hook_single_launch(16, s.d) ? 4 : 16)));
-    stk_sweep_geometry(s.n, s.d, &T, &LD, &G, &lds, Cb);
-    const int PW = s.d + 2;
-    const size_t wsb = stk_sweep_ws_bytes(s.n, s.d, Cb, m->nshards);
-    SweepWs ws{};
-    if (wsb) {
-      RC(ctx->scratch[4].ensure(wsb));
-      ws = stk_sweep_ws(ctx->scratch[4].p, s.n, s.d, m->nshards);
-    }
-    RC(ctx->scratch[0].ensure(sizeof(double) * (size_t)(m->nshards * Cb) * Dp));
-    RC(ctx->scratch[1].ensure(sizeof(double) * (size_t)(m->nshards * Cb)));
-    RC(ctx->scratch[2].ensure(sizeof(double) * (size_t)(m->nshards * Cb) * Dp));
-    RC(ctx->scratch[3].ensure(sizeof(double) * (size_t)m->nshards * G * Cb * PW));
-    for (int c0 = 0; c0 < C; c0 += Cb) {
-      const int nb = std::min(Cb, C - c0);
-      // the kernel reads rows shard*Cb + c of the point buffer
-      double* qb = ctx->scratch[0].as<double>() + (size_t)shard * Cb * Dp;
-      for (int c = 0; c < Cb; ++c) {
-        const int src = c0 + std::min(c, nb - 1);
-        STK_HIP_CHECK(hipMemcpyAsync(qb + (size_t)c * Dp, q + (size_t)src * D, sizeof(double) * D, hipMemcpyDefault, st));
-      }
-      STK_HIP_CHECK(stk_launch_sweep(m->family, shd, shard, 1, s.n, s.d, T, LD, G, G, lds, ctx->scratch[0].as<double>(), Cb,
-                                     Dp, ctx->scratch[3].as<double>(), nullptr, 0, nullptr, st, wsb ? &ws : nullptr));
-      STK_HIP_CHECK(stk_launch_sweep_reduce(m->family, shd, shard, 1, s.d, G, G, ctx->scratch[0].as<double>(), Cb, Dp,
-                                            ctx->scratch[3].as<double>(), nullptr, 0, ctx->scratch[1].as<double>(),
-                                            ctx->scratch[2].as<double>(), st));
-      double* lpb = ctx->scratch[1].as<double>() + (size_t)shard * Cb;
-      double* gb = ctx->scratch[2].as<double>() + (size_t)shard * Cb * Dp;
-      STK_HIP_CHECK(hipMemcpyAsync(lp + c0, lpb, sizeof(double) * nb, hipMemcpyDefault, st));
-      if (grad)
-        STK_HIP_CHECK(hipMemcpy2DAsync(grad + (size_t)c0 * D, sizeof(double) * D, gb, sizeof(double) * Dp,
-                                       sizeof(double) * D, nb, hipMemcpyDefault, st));
-    }
+    ChainPlan plan;
+    RC(chain_plan(m, {Cb}, shard, 1, &plan));
+    for (int c0 = 0; c0 < C; c0 += Cb)
+      RC(hook_eval(m, plan, (size_t)shard * Cb, Cb, q + (size_t)c0 * D, std::min(Cb, C - c0), lp + c0,
+                   grad ? grad + (size_t)c0 * D : nullptr));
     STK_HIP_CHECK(hipStreamSynchronize(st));
     return STK_OK;
   }
+  const int Dp = (m->Dmax + 7) / 8 * 8;
+  RC(ctx->scratch[0].ensure(sizeof(double) * (size_t)C * Dp));
+  RC(ctx->scratch[1].ensure(sizeof(double) * (size_t)C));
+  RC(ctx->scratch[2].ensure(sizeof(double) * (size_t)C * Dp));
+  STK_HIP_CHECK(hipMemcpy2DAsync(ctx->scratch[0].p, sizeof(double) * Dp, q, sizeof(double) * D, sizeof(double) * D,
+                                 C, hipMemcpyDefault, st));
+  STK_HIP_CHECK(stk_launch_schools_lpgrad(m->sh_dev.as<ShardDev>(), shard, stk_nch_for(m->Dmax),
+                                          ctx->scratch[0].as<double>(), C, Dp, ctx->scratch[1].as<double>(),
+                                          ctx->scratch[2].as<double>(), st));
   STK_HIP_CHECK(hipMemcpyAsync(lp, ctx->scratch[1].p, sizeof(double) * C, hipMemcpyDefault, st));
   if (grad)
     STK_HIP_CHECK(hipMemcpy2DAsync(grad, sizeof(double) * D, ctx->scratch[2].p, sizeof(double) * Dp, sizeof(double) * D,
@@ -627,87 +589,38 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
   return STK_OK;
 }
 
-// Every shard at C points each through the sampler's grouped launches (sweep_plan): the parity
-// hook for multi-shard grids, shard0 > 0 and a partial-sum stride Gs above a group's own G.
+// Every shard at C points each through the sampler's grouped launches (chain_plan with the one
+// batch C): the parity hook for multi-shard grids, shard0 > 0 and a partial-sum stride Gs above a
+// group's own G.
 int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_shards: bad arguments");
   ARG_CHECK(m->family == STK_LOGREG || m->family == STK_LINREG, "stk_log_density_grad_shards: regression families only");
   ARG_CHECK(hook_single_launch(C, m->d), "points per shard must be a single batch size here: 1, 2, 4, 8, 16 (d <= 128) or 64");
-  stk_ctx* ctx = m->ctx;
-  STK_HIP_CHECK(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const ShardDev* shd = m->sh_dev.as<ShardDev>();
-  const int D = m->Dmax;                       // one d for every shard of a regression model
-  const int Dp = (m->Dmax + 7) / 8 * 8;
-  const size_t rows = (size_t)m->nshards * C;
-  const SweepPlan plan = sweep_plan(m, C);
-  SweepWs ws{};
-  if (plan.ws_bytes) {
-    RC(ctx->scratch[4].ensure(plan.ws_bytes));
-    ws = stk_sweep_ws(ctx->scratch[4].p, plan.nmax, m->d, m->nshards);
-  }
-  RC(ctx->scratch[0].ensure(sizeof(double) * rows * Dp));
-  RC(ctx->scratch[1].ensure(sizeof(double) * rows));
-  RC(ctx->scratch[2].ensure(sizeof(double) * rows * Dp));
-  RC(ctx->scratch[3].ensure(plan.partial_bytes));
-  double* qb = ctx->scratch[0].as<double>();
-  double* lpb = ctx->scratch[1].as<double>();
-  double* gb = ctx->scratch[2].as<double>();
-  double* part = ctx->scratch[3].as<double>();
-  STK_HIP_CHECK(hipMemcpy2DAsync(qb, sizeof(double) * Dp, q, sizeof(double) * D, sizeof(double) * D, rows,
-                                 hipMemcpyDefault, st));
-  for (const auto& gr : plan.groups)
-    STK_HIP_CHECK(stk_launch_sweep(m->family, shd, gr.shard0, gr.nsh, m->sh[gr.shard0].n, m->d, gr.T, gr.LD, gr.G, plan.Gs,
-                                   gr.lds, qb, C, Dp, part, nullptr, 0, nullptr, st, plan.ws_bytes ? &ws : nullptr));
-  for (const auto& gr : plan.groups)
-    STK_HIP_CHECK(stk_launch_sweep_reduce(m->family, shd, gr.shard0, gr.nsh, m->d, gr.G, plan.Gs, qb, C, Dp, part,
-                                          nullptr, 0, lpb, gb, st));
-  STK_HIP_CHECK(hipMemcpyAsync(lp, lpb, sizeof(double) * rows, hipMemcpyDefault, st));
-  if (grad)
-    STK_HIP_CHECK(hipMemcpy2DAsync(grad, sizeof(double) * D, gb, sizeof(double) * Dp, sizeof(double) * D, rows,
-                                   hipMemcpyDefault, st));
-  STK_HIP_CHECK(hipStreamSynchronize(st));
-  return STK_OK;
+  return hook_every_shard(m, {C}, q, lp, grad);
 }
 
 // The same at ANY C >= 1 points per shard: the chain batches and grouped launches of a sampling
-// run at chains = C (chain_plan).
+// run at chains = C.
 int stk_log_density_grad_chains(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_chains: bad arguments");
   ARG_CHECK(m->family == STK_LOGREG || m->family == STK_LINREG, "stk_log_density_grad_chains: regression families only");
   ARG_CHECK(!chain_batches(C, m->d).empty(), "no sweep covers %d covariates (1..1024)", m->d);
-  stk_ctx* ctx = m->ctx;
-  STK_HIP_CHECK(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const ShardDev* shd = m->sh_dev.as<ShardDev>();
-  const int D = m->Dmax;
-  const int Dp = (m->Dmax + 7) / 8 * 8;
-  const size_t rows = (size_t)m->nshards * C;
-  const ChainPlan plan = chain_plan(m, C);
-  SweepWs ws{};
-  if (plan.ws_bytes) {
-    RC(ctx->scratch[4].ensure(plan.ws_bytes));
-    ws = stk_sweep_ws(ctx->scratch[4].p, plan.nmax, m->d, m->nshards);
-  }
-  RC(ctx->scratch[0].ensure(sizeof(double) * rows * Dp));
-  RC(ctx->scratch[1].ensure(sizeof(double) * rows));
-  RC(ctx->scratch[2].ensure(sizeof(double) * rows * Dp));
-  RC(ctx->scratch[3].ensure(plan.partial_bytes));
-  double* qb = ctx->scratch[0].as<double>();
-  double* lpb = ctx->scratch[1].as<double>();
-  double* gb = ctx->scratch[2].as<double>();
-  double* part = ctx->scratch[3].as<double>();
-  STK_HIP_CHECK(hipMemcpy2DAsync(qb, sizeof(double) * Dp, q, sizeof(double) * D, sizeof(double) * D, rows,
-                                 hipMemcpyDefault, st));
-  STK_HIP_CHECK(plan_sweeps(m, plan, shd, qb, Dp, part, nullptr, 0, nullptr, plan.ws_bytes ? &ws : nullptr, st));
-  STK_HIP_CHECK(plan_reduces(m, plan, shd, qb, Dp, part, nullptr, 0, lpb, gb, st));
-  STK_HIP_CHECK(hipMemcpyAsync(lp, lpb, sizeof(double) * rows, hipMemcpyDefault, st));
-  if (grad)
-    STK_HIP_CHECK(hipMemcpy2DAsync(grad, sizeof(double) * D, gb, sizeof(double) * Dp, sizeof(double) * D, rows,
-                                   hipMemcpyDefault, st));
-  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return hook_every_shard(m, chain_batches(C, m->d), q, lp, grad);
+}
+
+// The sweep one batch of C chains runs over a shard of n_rows x d (host only: no device).
+// out: kind, T, the LD handed to the kernel, G, LDS bytes, 64-chain workspace bytes per shard.
+int stk_sweep_launch_info(int64_t n_rows, int32_t d, int32_t C, int64_t out[6]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_sweep_launch_info: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(stk_sweep_supported(C, d), "%d chains are not one batch at %d covariates (stk_chain_batches)", C, d);
+  const SweepLaunch p = stk_sweep_plan(n_rows, d, C, 0);
+  ARG_CHECK(p.kind != SWEEP_NONE, "no sweep covers n = %lld rows of d = %d covariates at C = %d chains",
+            (long long)n_rows, d, C);
+  const int64_t v[6] = {p.kind, p.T, stk_sweep_args_ld(p), p.G, (int64_t)p.lds, (int64_t)p.ws_bytes};
+  memcpy(out, v, sizeof(v));
   return STK_OK;
 }
+
 
 // The chain batches a regression shard's C chains run as at d covariates (host only: no device).
 int stk_chain_batches(int32_t C, int32_t d, int32_t* sizes, int32_t cap) {
@@ -802,6 +715,7 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
   std::vector<double> minv_host, chol_host;
   if (dense && cfg->inv_metric_dense)
     RC(dense_metric_host(cfg->inv_metric_dense, m->Dmax, (m->Dmax + 7) / 8 * 8, &minv_host, &chol_host));
+  ChainPlan plan;
   if (m->family == STK_SCHOOLS) {
     ARG_CHECK(nch <= 2, "8-schools supports J <= 126");
     // the fused kernel keeps a chain's vectors and its max_depth-deep tree stack in LDS
@@ -815,7 +729,10 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
               "8-schools with J = %d at max_depth %d (nuts_criterion %d) needs %zu bytes of LDS per workgroup, the limit is %zu: "
               "lower max_depth",
               m->Dmax - 2, cfg->max_depth, cfg->nuts_criterion, lds, BIG_LDS_BYTES);
-  } else ARG_CHECK(!chain_batches(cfg->chains, m->d).empty(), "no sweep covers %d covariates (1..1024)", m->d);
+  } else {   // the chain batches, each with its sweeps grouped by consecutive shards of equal n
+    ARG_CHECK(!chain_batches(cfg->chains, m->d).empty(), "no sweep covers %d covariates (1..1024)", m->d);
+    RC(chain_plan(m, chain_batches(cfg->chains, m->d), 0, m->nshards, &plan));
+  }
   stk_sampler* s = new stk_sampler();
   s->m = m;
   m->refs++;
@@ -938,14 +855,12 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
     }
   }
   if (rc == STK_OK && m->family != STK_SCHOOLS) {
-    // the chain batches, each with its sweep geometry grouped by consecutive shards of equal n
-    s->plan = chain_plan(m, cfg->chains);
-    const ChainPlan& plan = s->plan;
     rc = s->partial.ensure(plan.partial_bytes);
     if (rc == STK_OK && plan.ws_bytes) {
       rc = s->ws.ensure(plan.ws_bytes);
-      if (rc == STK_OK) s->sws = stk_sweep_ws(s->ws.p, plan.nmax, m->d, m->nshards);
+      if (rc == STK_OK) s->sws = stk_sweep_ws(s->ws.p, plan.ws_at, m->nshards);
     }
+    s->plan = std::move(plan);
     if (rc == STK_OK) rc = s->ran.ensure(sizeof(int) * 64);
   }
   if (rc == STK_OK) {
@@ -1009,11 +924,11 @@ static int run_split_batch(stk_sampler* s, int nsteps, int pause_at) {
     const bool pk = prof && step_id % every == 0;
     if (pk) STK_HIP_CHECK(hipEventRecord(s->ev[2 * k], st));
     // one event pair spans the sweeps of all the step's batches
-    STK_HIP_CHECK(plan_sweeps(m, s->plan, A.shards, A.qeval, A.Dp, s->partial.as<double>(), A.req_step, step_id,
-                              prof ? s->ran.as<int>() : nullptr, s->sws.qT ? &s->sws : nullptr, st));
+    const SweepCall run{A.shards, A.qeval, s->partial.as<double>(), A.req_step, step_id, prof ? s->ran.as<int>() : nullptr,
+                        s->sws.qT ? &s->sws : nullptr, A.Dp, 0, 0, 0};
+    STK_HIP_CHECK(plan_sweeps(m, s->plan, run, st));
     if (pk) STK_HIP_CHECK(hipEventRecord(s->ev[2 * k + 1], st));
-    STK_HIP_CHECK(plan_reduces(m, s->plan, A.shards, A.qeval, A.Dp, s->partial.as<double>(), A.req_step, step_id,
-                               A.lp_in, A.g_in, st));
+    STK_HIP_CHECK(plan_reduces(m, s->plan, run, A.lp_in, A.g_in, st));
     if (s->ar_fn) {
       const int r = s->ar_fn(s->ar_user, A.g_in, (int64_t)A.nchains * (A.Dp + 1), (void*)st);
       if (r != 0) {

@@ -25,7 +25,7 @@
 //                    whose sum W comes from the caller, inverts it by partial pivoting instead)
 // k_mgemm: fp64 MFMA, one 16 x 16 NB output tile per block, K split over the block's waves,
 // every output a fixed-order sum (cov_s only on the upper tiles, stored both ways).
-#include "common.h"
+#include "launchers.h"
 #include <math.h>
 #include <algorithm>
 #include <utility>

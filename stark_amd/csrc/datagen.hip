@@ -5,7 +5,7 @@
 //   logistic: y_i = 1{u_i < 1/(1+exp(-eta_i))};  linear: y_i = eta_i + sigma * N(0,1)
 // Rows carry their GLOBAL index, so a shard's contents do not depend on how the
 // dataset was split across GPUs.
-#include "common.h"
+#include "launchers.h"
 #include <math.h>
 
 namespace stk {

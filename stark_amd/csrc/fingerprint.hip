@@ -6,7 +6,7 @@
 // and the host twin's left-to-right loop give the same bits.  fmix has ONE 64 x 64 multiply: the
 // kernel has to stay under the HBM time of the read at gfx950's 32-bit integer multiply rate
 // (DESIGN.md "Data fingerprint").
-#include "common.h"
+#include "launchers.h"
 #include <string.h>
 #include <algorithm>
 #include <type_traits>

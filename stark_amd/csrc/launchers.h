@@ -1,0 +1,108 @@
+// Host-side launchers and helpers that cross translation units of libstark_hip.so: declared once
+// here, included by capi.hip (the caller) and by every file that defines one, so a signature
+// that drifts is a compile error instead of a second overload that links and runs.
+#pragma once
+#include "common.h"
+
+namespace stk {
+
+struct SweepArgs;   // sweep_common.h (device side)
+
+// Which regression sweep runs; the numbers are those of tests/golden/sweep_launch.json.
+enum SweepKind : int {
+  SWEEP_NONE = 0,     // no sweep: the chunk bytes do not fit a buffer descriptor, or (C, d) has no kernel
+  SWEEP_V1 = 1,       // k_sweep       any d <= 1024, C <= 8
+  SWEEP_V2 = 2,       // k_sweep2      even d <= 128, C <= 8
+  SWEEP_V3 = 3,       // k_sweep3      even d <= 104, C <= 4
+  SWEEP_16 = 4,       // k_sweep16     C = 16, d <= 128 (sweep16.hip)
+  SWEEP_GEMM64 = 5,   // k_qt_swizzle + k_gemm_fwd + k_gemm_bwd, C = 64
+  SWEEP_16W = 6,      // k_sweep16w    C = 16, 128 < d <= 1024 (sweep16w.hip)
+};
+
+// The kernel and launch shape of one sweep over a shard of n rows: a function of (n, d, C) only,
+// so reductions are identical on 1 or N GPUs.  Built by stk_sweep_plan, the one place that reads
+// (n, d, C) to choose a kernel; the launchers dispatch on `kind`.  Kind 0 carries no geometry.
+struct SweepLaunch {
+  SweepKind kind;
+  int C, d;
+  int T;              // rows per tile
+  int G;              // chunks per shard
+  size_t lds;         // dynamic LDS bytes per block (kind 5: pass F's; pass B sizes its own)
+  int ld;             // kinds 1, 2: row stride of the X tile in LDS, in doubles
+  int ring;           // kind 3: ring slots per wave
+  int waves;          // kind 6: waves per block (= column slabs)
+  int64_t Rrows;      // kind 5: rows of the residual matrix R per shard (n rounded up to 64)
+  size_t ws_bytes;    // kind 5: workspace bytes one shard needs (beta^T image + R); else 0
+};
+
+// What one launch adds to its plan: where the data is and which batch of the shard's chains this is.
+struct SweepCall {
+  const ShardDev* shards;
+  const double* q;        // [nshards * Ct][Dp] evaluation points
+  double* partial;        // the batch's [nshards][Gs][C][d + 2] partial sums
+  const int* req_step;    // nullptr: every shard runs
+  int step_id;
+  int* ran;               // nullptr, or the profiling counters
+  const SweepWs* ws;      // kind 5's workspace (stk_sweep_ws); nullptr when no batch needs one
+  int Dp;
+  int Gs;                 // partial-sum stride in chunks per shard: the largest G of the batch's groups
+  int Ct, c0;             // chains per shard in q / lp / grad, first chain of this batch
+};
+
+}  // namespace stk
+
+// ---- sweep.hip
+bool stk_sweep_supported(int C, int d);
+// force: 1 | 2 pins k_sweep | k_sweep2 where the shape allows (tools/sweep_micro.hip); the library passes 0.
+stk::SweepLaunch stk_sweep_plan(int64_t n, int d, int C, int force);
+int stk_sweep_args_ld(const stk::SweepLaunch& p);   // the plan's per-kind field as SweepArgs.LD
+stk::SweepWs stk_sweep_ws(void* base, const stk::SweepLaunch& at_nmax, int nshards);
+hipError_t stk_launch_sweep(int family, const stk::SweepLaunch& p, int shard0, int nsh, const stk::SweepCall& c,
+                            hipStream_t st);
+hipError_t stk_launch_sweep_reduce(int family, const stk::SweepLaunch& p, int shard0, int nsh, const stk::SweepCall& c,
+                                   double* lp_out, double* g_out, hipStream_t st);
+
+// ---- sweep16.hip: shapes k_sweep16 covers, its LDS bytes, its launch
+bool stk_sweep16_supported(int d);
+size_t stk_sweep16_lds_bytes(int family, int d);
+hipError_t stk_launch_sweep16(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
+
+// ---- sweep16w.hip (128 < d <= 1024): waves per block, chunks per shard, LDS bytes, launch
+bool stk_sweep16w_supported(int d);
+int stk_sweep16w_waves(int d);
+int stk_sweep16w_chunks(int64_t n);
+size_t stk_sweep16w_lds_bytes(int family, int d);
+hipError_t stk_launch_sweep16w(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
+
+// ---- nuts.hip (and its nuts_fused4.hip / nuts_dense.hip translation units)
+int stk_nch_for(int Dmax);
+size_t stk_fused_lds_bytes(const stk::NutsArgs& A, int nch);
+hipError_t stk_launch_nuts_init(const stk::NutsArgs& A, const double* init, const double* inv_metric, double stepsize,
+                                double init_radius, hipStream_t st);
+hipError_t stk_launch_nuts_step(const stk::NutsArgs& A, int nch, int step_id, int pause_at, hipStream_t st);
+hipError_t stk_launch_nuts_fused(const stk::NutsArgs& A, int nch, int pause_at, int max_steps, hipStream_t st);
+hipError_t stk_launch_dense_init(const stk::NutsArgs& A, const double* minv0, const double* chol0, hipStream_t st);
+hipError_t stk_launch_nuts_step_dense(const stk::NutsArgs& A, int nch, int step_id, int pause_at, hipStream_t st);
+hipError_t stk_launch_schools_lpgrad(const stk::ShardDev* shards, int shard, int nch, const double* q, int C, int Dp,
+                                     double* lp, double* g, hipStream_t st);
+
+// ---- datagen.hip
+hipError_t stk_launch_check_y01(const int32_t* y, int64_t n, int64_t* first, hipStream_t st);
+hipError_t stk_launch_gen_shard(double* X, double* yd, int32_t* yi, int64_t nrows, int d, int64_t grow0,
+                                uint64_t seed, double alpha, const double* beta, double noise_sigma, int family,
+                                hipStream_t st);
+
+// ---- combine.hip
+hipError_t stk_launch_consensus_products(const double* X, int nshards, int P, int S, const int32_t* blk, double* mean,
+                                         int32_t* rowbad, int32_t* used, int32_t* status, double* cov, double* W,
+                                         double* work, double* sum_w, double* sum_wtheta, hipStream_t st);
+size_t stk_general_inverse_work_bytes(int P);
+hipError_t stk_launch_consensus_solve(const double* sum_w, const double* sum_wtheta, int P, int S, double* inv_buf,
+                                      double* work, int32_t* status, double* out, hipStream_t st, bool general);
+size_t stk_spd_inverse_work_bytes(int P, int batch);
+
+// ---- fingerprint.hip
+uint64_t stk_fp_fmix(uint64_t a);
+uint64_t stk_fp_words_host(const void* buf, int64_t count, int word_bytes, int tag, uint64_t index0);
+hipError_t stk_launch_fp_words(const void* buf, int64_t count, int word_bytes, int tag, uint64_t index0,
+                               unsigned long long* sum, hipStream_t st);

@@ -23,7 +23,7 @@
 //                 one launch per leapfrog for all chains of all local shards;
 //   k_nuts_fused  local models (8 schools): the gradient is computed inline and each wave
 //                 loops its own chain for up to max_steps leapfrogs in ONE launch.
-#include "common.h"
+#include "launchers.h"
 #include <math.h>
 #include <stdlib.h>
 #include <algorithm>

@@ -1105,15 +1105,16 @@ __global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce(SweepArgs A, double*
 
 }  // namespace stk
 
+#include "launchers.h"
 using namespace stk;
 
-// Host-side geometry: depends only on (n, d, C) so reductions are identical on 1 or N GPUs.
-// v3 (LDS-DMA ring) for even d <= 104 and C <= 4, v2 for other even d <= 128, else v1.
-// C = 16: k_sweep16 (4) for d <= 128, k_sweep16w (6) past it; C = 64: the two GEMM passes (5).
-// stk_sweep_force_variant (1 | 2 | 3, 0 = by shape) is set by tools/sweep_micro.hip only: the
-// library reads no environment variable to pick a kernel.
-int stk_sweep_force_variant = 0;
-static int sweep_forced() { return stk_sweep_force_variant; }
+// The single-launch chain counts a sweep covers at d covariates (the batch sizes of the sampler).
+bool stk_sweep_supported(int C, int d) {
+  if (C == G5_C) return d >= 1 && d <= 4096;
+  if (C == SM_C) return d >= 1 && (stk_sweep16_supported(d) || stk_sweep16w_supported(d));   // here a 16-batch is ruled in or out at d
+  if (!(C == 1 || C == 2 || C == 4 || C == 8)) return false;
+  return d >= 1 && d <= 1024;
+}
 
 // Ring depth of v3: as many slots per wave as fit next to the d-eta scratch (at most 5).
 static int sweep3_nb(int d, int C) {
@@ -1123,193 +1124,173 @@ static int sweep3_nb(int d, int C) {
   return std::min(nb, 5);
 }
 
-static int sweep_variant(int64_t n, int d, int C) {
-  if (C == G5_C) return (((n + 511) / 512 + G5_TR + G5_FTR) * d * 8 < ((int64_t)1 << 31)) ? 5 : 0;   // chunk bytes (+ pass F's last tile) fit a buffer descriptor
-  if (C == SM_C) {
-    if ((n * d * 8) / 512 >= ((int64_t)1 << 30)) return 0;      // chunk bytes fit a buffer descriptor
-    return stk_sweep16_supported(d) ? 4 : (stk_sweep16w_supported(d) ? 6 : 0);
-  }
-  const int f = sweep_forced();
-  const bool v3ok = d % 2 == 0 && d / 2 <= S3_KMAX && (C == 1 || C == 2 || C == 4) && sweep3_nb(d, C) >= 3 &&
-                    (n * d * 8) / 512 < ((int64_t)1 << 30);
-  const bool v2ok = d <= 128 && d % 2 == 0;
-  if (f == 1) return 1;
-  if (f == 2) return v2ok ? 2 : 1;
-  if (v3ok) return 3;
-  return v2ok ? 2 : 1;
+// Chunks per shard: ceil(units / per) of rows or tiles, kept within 1 .. 512.
+static int sweep_chunks(int64_t units, int64_t per) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(512, (units + per - 1) / per));
 }
 
-void stk_sweep_geometry(int64_t n, int d, int* T, int* LD, int* G, size_t* lds_bytes, int C) {
-  const int var = sweep_variant(n, d, C);
-  if (var == 5) {
-    const int64_t nt = (n + G5_TR - 1) / G5_TR;
-    int64_t g = (nt + 3) / 4;            // >= 4 tiles of 64 rows per chunk
-    if (g > 512) g = 512;
-    if (g < 1) g = 1;
-    *T = G5_TR;
-    *LD = 0;
-    *G = (int)g;
-    *lds_bytes = G5_FS * g5_fstage_bytes() + EX_TAB * sizeof(double);   // pass F's (pass B sizes its own)
-    return;
+// The planner: which kernel sweeps n rows of d covariates for C chains, and its launch shape.
+// v3 (LDS-DMA ring) for even d <= 104 and C <= 4, v2 for other even d <= 128, else v1; C = 16:
+// k_sweep16 for d <= 128, k_sweep16w past it; C = 64: the two GEMM passes.  Kind 0 (no geometry)
+// where no kernel covers (C, d) or a chunk's bytes do not fit a buffer descriptor.
+SweepLaunch stk_sweep_plan(int64_t n, int d, int C, int force) {
+  SweepLaunch p{};
+  p.C = C;
+  p.d = d;
+  if (n < 1 || !stk_sweep_supported(C, d)) return p;
+  const int64_t nt = (n + 63) / 64;                                // 64-row tiles (S3_T, G5_TR, the 16-chain sweeps')
+  const bool desc_ok = (n * d * 8) / 512 < ((int64_t)1 << 30);     // chunk bytes fit a buffer descriptor
+  if (C == G5_C) {
+    if (((n + 511) / 512 + G5_TR + G5_FTR) * d * 8 >= ((int64_t)1 << 31)) return p;   // chunk bytes + pass F's last tile
+    p.kind = SWEEP_GEMM64;
+    p.T = G5_TR;
+    p.G = sweep_chunks(nt, 4);
+    p.lds = G5_FS * g5_fstage_bytes() + EX_TAB * sizeof(double);
+    p.Rrows = nt * G5_TR;
+    p.ws_bytes = sizeof(double) * G5_C * ((size_t)g5_kp(d) + (size_t)p.Rrows);
+    return p;
   }
-  if (var == 4) {                       // k_sweep16 (sweep16.hip)
-    const int64_t nt = (n + 63) / 64;
-    int64_t g = (nt + 7) / 8;            // >= 8 tiles of 64 rows per chunk (as v3)
-    if (g > 512) g = 512;
-    if (g < 1) g = 1;
-    *T = 64;
-    *LD = 1;
-    *G = (int)g;
-    *lds_bytes = stk_sweep16_lds_bytes(STK_LOGREG, d);   // the larger of the two families
-    return;
+  if (C == SM_C) {
+    if (!desc_ok) return p;
+    p.T = 64;
+    if (stk_sweep16_supported(d)) {
+      p.kind = SWEEP_16;
+      p.G = sweep_chunks(nt, 8);
+      p.lds = stk_sweep16_lds_bytes(STK_LOGREG, d);   // the larger of the two families
+    } else {
+      p.kind = SWEEP_16W;
+      p.waves = stk_sweep16w_waves(d);
+      p.G = stk_sweep16w_chunks(n);
+      p.lds = stk_sweep16w_lds_bytes(STK_LOGREG, d);
+    }
+    return p;
   }
-  if (var == 6) {                       // k_sweep16w (sweep16w.hip): LD carries the waves per block
-    *T = 64;
-    *LD = stk_sweep16w_waves(d);
-    *G = stk_sweep16w_chunks(n);
-    *lds_bytes = stk_sweep16w_lds_bytes(STK_LOGREG, d);
-    return;
-  }
-  if (var == 3) {
-    const int64_t nt = (n + S3_T - 1) / S3_T;
-    int64_t g = (nt + 7) / 8;            // >= 8 tiles per chunk
-    if (g > 512) g = 512;
-    if (g < 1) g = 1;
-    const int nb = sweep3_nb(d, C);
-    *T = S3_T;
-    *LD = nb;
-    *G = (int)g;
-    const int K = d / 2;
-    const size_t ring = (size_t)S3_W * nb * sweep3_slot_bytes(K) + (size_t)S3_W * 8 * C * sizeof(double);
+  const bool v2ok = d <= 128 && d % 2 == 0;
+  const bool v3ok = d % 2 == 0 && d / 2 <= S3_KMAX && C <= 4 && sweep3_nb(d, C) >= 3 && desc_ok;
+  if (v3ok && force != 1 && force != 2) {
+    p.kind = SWEEP_V3;
+    p.T = S3_T;
+    p.G = sweep_chunks(nt, 8);
+    p.ring = sweep3_nb(d, C);
+    const size_t ring = (size_t)S3_W * p.ring * sweep3_slot_bytes(d / 2) + (size_t)S3_W * 8 * C * sizeof(double);
     const size_t red = ((size_t)S3_W * C * 128 + (size_t)S3_W * 64 * 2) * sizeof(double);
-    *lds_bytes = std::max(ring, red);
-    return;
+    p.lds = std::max(ring, red);
+    return p;
   }
   int t = 64;
   while (t > 8 && (int64_t)t * d > 8192) t >>= 1;
-  int64_t g = (n + (int64_t)8 * t - 1) / ((int64_t)8 * t);
-  if (g > 512) g = 512;
-  if (g < 1) g = 1;
-  *T = t;
-  *G = (int)g;
-  if (var == 2) {
-    *LD = d | 1;
-    const size_t main = (size_t)(64 * (d | 1) + 4 * C * 64 + 64 * C) * sizeof(double);
+  p.T = t;
+  p.G = sweep_chunks(n, (int64_t)8 * t);
+  if (v2ok && force != 1) {
+    p.kind = SWEEP_V2;
+    p.ld = d | 1;
+    const size_t main = (size_t)(64 * p.ld + 4 * C * 64 + 64 * C) * sizeof(double);
     const size_t red = (size_t)std::max(4 * C * 2 * 64, 4 * 256) * sizeof(double);
-    *lds_bytes = std::max(main, red);
-    return;
+    p.lds = std::max(main, red);
+    return p;
   }
-  const int m = (256 / t) % 32;   // LD = m (mod 32): conflict-free ds_read_b64 in the forward pass
-  int ld = d;
-  while ((ld % 32) != m) ++ld;
-  *LD = ld;
+  p.kind = SWEEP_V1;
+  const int m = (256 / t) % 32;   // ld = m (mod 32): conflict-free ds_read_b64 in the forward pass
+  p.ld = d;
+  while ((p.ld % 32) != m) ++p.ld;
   const int JW = d <= 64 ? 64 : (d <= 128 ? 128 : 256);
   const int JPT = (d + JW - 1) / JW;
-  const size_t main = (size_t)(t * ld + C * ld + t * C + 2 * C) * sizeof(double);
+  const size_t main = (size_t)(t * p.ld + C * p.ld + t * C + 2 * C) * sizeof(double);
   const size_t red1 = (size_t)(256 / JW) * C * JW * JPT * sizeof(double);
   const size_t red2 = (size_t)2 * C * 256 * sizeof(double);
-  size_t b = main;
-  if (red1 > b) b = red1;
-  if (red2 > b) b = red2;
-  *lds_bytes = b;
+  p.lds = std::max(main, std::max(red1, red2));
+  return p;
 }
 
-template <int FAM, int C, int T, int JPT, int VEC>
-static hipError_t launch_sweep_t(const SweepArgs& A, int nblocks, size_t lds, hipStream_t st) {
-  if (const hipError_t e = allow_big_lds((const void*)k_sweep<FAM, C, T, JPT, VEC>)) return e;
-  hipLaunchKernelGGL((k_sweep<FAM, C, T, JPT, VEC>), dim3(nblocks), dim3(256), lds, st, A);
-  return hipGetLastError();
+// SweepArgs.LD means something else to every kernel; this is the one place that says what.
+int stk_sweep_args_ld(const SweepLaunch& p) {
+  switch (p.kind) {
+    case SWEEP_V1:
+    case SWEEP_V2: return p.ld;
+    case SWEEP_V3: return p.ring;
+    case SWEEP_16: return 1;
+    case SWEEP_16W: return p.waves;
+    default: return 0;
+  }
+}
+
+// The 64-chain workspace of `nshards` shards at `base`, sized by the plan of the shard with the most rows.
+SweepWs stk_sweep_ws(void* base, const SweepLaunch& at_nmax, int nshards) {
+  SweepWs w{};
+  w.Rrows = at_nmax.Rrows;
+  w.qT = reinterpret_cast<double*>(base);
+  w.R = w.qT + (size_t)nshards * g5_kp(at_nmax.d) * G5_C;
+  return w;
+}
+
+static SweepArgs sweep_args(const SweepLaunch& p, int shard0, const SweepCall& c, int LD) {
+  SweepArgs A{c.shards, c.q, c.partial, c.req_step, c.step_id, p.C, c.Dp, p.G, LD, p.d + 2, shard0, c.Gs, c.ran};
+  A.Ct = c.Ct;
+  A.c0 = c.c0;
+  return A;
 }
 
 template <int FAM, int C, int T, int JPT>
 static hipError_t pick_vec(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  if (d % 2 == 0) return launch_sweep_t<FAM, C, T, JPT, 2>(A, nblocks, lds, st);
-  return launch_sweep_t<FAM, C, T, JPT, 1>(A, nblocks, lds, st);
+  auto kern = d % 2 == 0 ? k_sweep<FAM, C, T, JPT, 2> : k_sweep<FAM, C, T, JPT, 1>;   // 16-B or 8-B tile loads
+  if (const hipError_t e = allow_big_lds((const void*)kern)) return e;
+  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), lds, st, A);
+  return hipGetLastError();
 }
 
 template <int FAM, int C>
-static hipError_t pick_tile(const SweepArgs& A, int64_t n, int d, int T, int nblocks, size_t lds, hipStream_t st) {
-  const int var = sweep_variant(n, d, C);
-  if (var == 3) {
+static hipError_t pick_tile(const SweepLaunch& p, const SweepArgs& A, int nblocks, hipStream_t st) {
+  if (p.kind == SWEEP_V3) {
     if constexpr (C <= 4) {
       auto go = [&](auto kern) {
         if (const hipError_t e = allow_big_lds((const void*)kern)) return e;
-        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(512), lds, st, A, A.LD);
+        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(512), p.lds, st, A, p.ring);
         return hipGetLastError();
       };
-      if (d == 100 && A.LD == 3) return go(k_sweep3<FAM, C, 0, 50, 3>);
-      if (d == 50 && A.LD == 5) return go(k_sweep3<FAM, C, 0, 25, 5>);
+      if (p.d == 100 && p.ring == 3) return go(k_sweep3<FAM, C, 0, 50, 3>);
+      if (p.d == 50 && p.ring == 5) return go(k_sweep3<FAM, C, 0, 25, 5>);
       return go(k_sweep3<FAM, C>);
     }
     return hipErrorInvalidValue;
   }
-  if (var == 2) {
+  if (p.kind == SWEEP_V2) {
     if (const hipError_t e = allow_big_lds((const void*)k_sweep2<FAM, C>)) return e;
-    hipLaunchKernelGGL((k_sweep2<FAM, C>), dim3(nblocks), dim3(256), lds, st, A);
+    hipLaunchKernelGGL((k_sweep2<FAM, C>), dim3(nblocks), dim3(256), p.lds, st, A);
     return hipGetLastError();
   }
-  switch (T) {
-    case 64: return pick_vec<FAM, C, 64, 1>(A, d, nblocks, lds, st);
-    case 32: return pick_vec<FAM, C, 32, 1>(A, d, nblocks, lds, st);
-    case 16: return pick_vec<FAM, C, 16, 2>(A, d, nblocks, lds, st);
-    case 8: return pick_vec<FAM, C, 8, 4>(A, d, nblocks, lds, st);
+  switch (p.T) {
+    case 64: return pick_vec<FAM, C, 64, 1>(A, p.d, nblocks, p.lds, st);
+    case 32: return pick_vec<FAM, C, 32, 1>(A, p.d, nblocks, p.lds, st);
+    case 16: return pick_vec<FAM, C, 16, 2>(A, p.d, nblocks, p.lds, st);
+    case 8: return pick_vec<FAM, C, 8, 4>(A, p.d, nblocks, p.lds, st);
   }
   return hipErrorInvalidValue;
 }
 
 template <int FAM>
-static hipError_t pick_c(const SweepArgs& A, int64_t n, int d, int T, int nblocks, size_t lds, hipStream_t st) {
-  if (A.C == SM_C) {
-    const int var = sweep_variant(n, d, A.C);
-    if (var == 4) return stk_launch_sweep16(FAM, A, d, nblocks, lds, st);
-    if (var == 6) return stk_launch_sweep16w(FAM, A, d, nblocks, lds, st);
-    return hipErrorInvalidValue;
-  }
-  switch (A.C) {
-    case 1: return pick_tile<FAM, 1>(A, n, d, T, nblocks, lds, st);
-    case 2: return pick_tile<FAM, 2>(A, n, d, T, nblocks, lds, st);
-    case 4: return pick_tile<FAM, 4>(A, n, d, T, nblocks, lds, st);
-    case 8: return pick_tile<FAM, 8>(A, n, d, T, nblocks, lds, st);
+static hipError_t pick_c(const SweepLaunch& p, const SweepArgs& A, int nblocks, hipStream_t st) {
+  if (p.kind == SWEEP_16) return stk_launch_sweep16(FAM, A, p.d, nblocks, p.lds, st);
+  if (p.kind == SWEEP_16W) return stk_launch_sweep16w(FAM, A, p.d, nblocks, p.lds, st);
+  if (p.kind < SWEEP_V1 || p.kind > SWEEP_V3) return hipErrorInvalidValue;
+  switch (p.C) {
+    case 1: return pick_tile<FAM, 1>(p, A, nblocks, st);
+    case 2: return pick_tile<FAM, 2>(p, A, nblocks, st);
+    case 4: return pick_tile<FAM, 4>(p, A, nblocks, st);
+    case 8: return pick_tile<FAM, 8>(p, A, nblocks, st);
   }
   return hipErrorInvalidValue;
 }
 
-bool stk_sweep_supported(int C, int d) {
-  if (C == G5_C) return d >= 1 && d <= 4096;
-  if (C == SM_C) return d >= 1 && (stk_sweep16_supported(d) || stk_sweep16w_supported(d));   // the one place a 16-batch is ruled in or out at d
-  if (!(C == 1 || C == 2 || C == 4 || C == 8)) return false;
-  return d >= 1 && d <= 1024;
-}
-
-// Workspace bytes of the sweep for `nshards` shards of at most n_max rows (0 unless v5).
-size_t stk_sweep_ws_bytes(int64_t n_max, int d, int C, int nshards) {
-  if (sweep_variant(n_max, d, C) != 5) return 0;
-  const int64_t rrows = (n_max + G5_TR - 1) / G5_TR * G5_TR;
-  return sizeof(double) * (size_t)nshards * G5_C * ((size_t)g5_kp(d) + (size_t)rrows);
-}
-SweepWs stk_sweep_ws(void* base, int64_t n_max, int d, int nshards) {
-  SweepWs w{};
-  w.Rrows = (n_max + G5_TR - 1) / G5_TR * G5_TR;
-  w.qT = reinterpret_cast<double*>(base);
-  w.R = w.qT + (size_t)nshards * g5_kp(d) * G5_C;
-  return w;
-}
-
-// Launch the sweep over `nsh` shards starting at shard0 (all with the same n, d geometry) for the
-// batch of C chains that starts at chain c0 of every shard's Ct.
-hipError_t stk_launch_sweep(int family, const ShardDev* shards_dev, int shard0, int nsh, int64_t n, int d, int T,
-                            int LD, int G, int Gs, size_t lds, const double* q, int C, int Dp, double* partial,
-                            const int* req_step, int step_id, int* ran, hipStream_t st, const SweepWs* ws = nullptr,
-                            int Ct = 0, int c0 = 0) {
-  SweepArgs A{shards_dev, q, partial, req_step, step_id, C, Dp, G, LD, d + 2, shard0, Gs, ran};
-  A.Ct = Ct > 0 ? Ct : C;   // a batch of C chains starting at chain c0 of the shard's Ct (default: the only batch)
-  A.c0 = c0;
-  const int nblocks = nsh * G;
-  if (sweep_variant(n, d, C) == 5) {
-    if (!ws || !ws->qT || !ws->R || ws->Rrows < (n + G5_TR - 1) / G5_TR * G5_TR) return hipErrorInvalidValue;
-    A.qT = ws->qT;
-    A.R = ws->R;
-    A.Rrows = ws->Rrows;
+// Launch the plan's sweep over `nsh` shards starting at shard0 (all of the plan's n) for the batch
+// of p.C chains that starts at chain c.c0 of every shard's c.Ct.
+hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int nsh, const SweepCall& c, hipStream_t st) {
+  SweepArgs A = sweep_args(p, shard0, c, stk_sweep_args_ld(p));
+  const int nblocks = nsh * p.G, d = p.d;
+  if (p.kind == SWEEP_GEMM64) {
+    if (!c.ws || !c.ws->qT || !c.ws->R || c.ws->Rrows < p.Rrows) return hipErrorInvalidValue;
+    A.qT = c.ws->qT;
+    A.R = c.ws->R;
+    A.Rrows = c.ws->Rrows;
     const int bjb = g5_bjb(d), njb = (d + bjb - 1) / bjb;
     hipLaunchKernelGGL(k_qt_swizzle, dim3((g5_kp(d) * G5_C + 255) / 256, nsh), dim3(256), 0, st, A, d);
     // the split stage schedule needs a tile's NKC = ceil(d / 16) stages to hold its 8 epilogue parts
@@ -1317,27 +1298,25 @@ hipError_t stk_launch_sweep(int family, const ShardDev* shards_dev, int shard0, 
     auto kf = family == STK_LOGREG ? (split ? k_gemm_fwd<STK_LOGREG, G5_FW, 2, G5_FKC, G5_FS, 1> : k_gemm_fwd<STK_LOGREG>)
                                    : (split ? k_gemm_fwd<STK_LINREG, G5_FW, 2, G5_FKC, G5_FS, 1> : k_gemm_fwd<STK_LINREG>);
     if (const hipError_t e = allow_big_lds((const void*)kf)) return e;
-    hipLaunchKernelGGL(kf, dim3(nblocks), dim3(64 * G5_FW), lds, st, A);
+    hipLaunchKernelGGL(kf, dim3(nblocks), dim3(64 * G5_FW), p.lds, st, A);
     auto kb = bjb == 64 ? k_gemm_bwd<64> : bjb == 128 ? k_gemm_bwd<128> : k_gemm_bwd<256>;
     if (const hipError_t e = allow_big_lds((const void*)kb)) return e;
     hipLaunchKernelGGL(kb, dim3(nblocks * njb), dim3(64 * G5_BW), G5_BNS * g5_bstage_bytes(bjb), st, A, njb);
     return hipGetLastError();
   }
-  if (family == STK_LOGREG) return pick_c<STK_LOGREG>(A, n, d, T, nblocks, lds, st);
-  if (family == STK_LINREG) return pick_c<STK_LINREG>(A, n, d, T, nblocks, lds, st);
+  if (family == STK_LOGREG) return pick_c<STK_LOGREG>(p, A, nblocks, st);
+  if (family == STK_LINREG) return pick_c<STK_LINREG>(p, A, nblocks, st);
   return hipErrorInvalidValue;
 }
 
-hipError_t stk_launch_sweep_reduce(int family, const ShardDev* shards_dev, int shard0, int nsh, int d, int G, int Gs,
-                                   const double* q, int C, int Dp, double* partial, const int* req_step,
-                                   int step_id, double* lp_out, double* g_out, hipStream_t st, int Ct = 0, int c0 = 0) {
-  SweepArgs A{shards_dev, q, partial, req_step, step_id, C, Dp, G, 0, d + 2, shard0, Gs, nullptr};
-  A.Ct = Ct > 0 ? Ct : C;
-  A.c0 = c0;
-  dim3 grid(nsh * C, (d + 2 + 63) / 64);
+hipError_t stk_launch_sweep_reduce(int family, const SweepLaunch& p, int shard0, int nsh, const SweepCall& c,
+                                   double* lp_out, double* g_out, hipStream_t st) {
+  SweepArgs A = sweep_args(p, shard0, c, 0);
+  A.ran = nullptr;
+  dim3 grid(nsh * p.C, (p.d + 2 + 63) / 64);
   if (family == STK_LOGREG)
-    hipLaunchKernelGGL(k_sweep_reduce<STK_LOGREG>, grid, dim3(64 * RD_W), 0, st, A, lp_out, g_out, C);
+    hipLaunchKernelGGL(k_sweep_reduce<STK_LOGREG>, grid, dim3(64 * RD_W), 0, st, A, lp_out, g_out, p.C);
   else
-    hipLaunchKernelGGL(k_sweep_reduce<STK_LINREG>, grid, dim3(64 * RD_W), 0, st, A, lp_out, g_out, C);
+    hipLaunchKernelGGL(k_sweep_reduce<STK_LINREG>, grid, dim3(64 * RD_W), 0, st, A, lp_out, g_out, p.C);
   return hipGetLastError();
 }

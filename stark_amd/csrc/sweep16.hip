@@ -314,6 +314,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
 
 }  // namespace stk
 
+#include "launchers.h"
 using namespace stk;
 
 // LDS bytes of k_sweep16 at d (the main loop's slots + table + remainder scratch, or the block

@@ -241,6 +241,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
 
 }  // namespace stk
 
+#include "launchers.h"
 using namespace stk;
 
 bool stk_sweep16w_supported(int d) { return d > 128 && d <= 128 * SW_MAXW; }

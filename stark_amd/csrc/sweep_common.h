@@ -137,16 +137,3 @@ __device__ __forceinline__ double logit_resid4(double eta, uint32_t y, const dou
 }
 
 }  // namespace stk
-
-// The 16-chain sweep (sweep16.hip): shapes it covers, its LDS bytes, its launch.
-bool stk_sweep16_supported(int d);
-size_t stk_sweep16_lds_bytes(int family, int d);
-hipError_t stk_launch_sweep16(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
-
-// The wide 16-chain sweep (sweep16w.hip, 128 < d <= 1024): waves per block (= column slabs, passed
-// as SweepArgs.LD), chunks per shard, LDS bytes, launch.
-bool stk_sweep16w_supported(int d);
-int stk_sweep16w_waves(int d);
-int stk_sweep16w_chunks(int64_t n);
-size_t stk_sweep16w_lds_bytes(int family, int d);
-hipError_t stk_launch_sweep16w(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);

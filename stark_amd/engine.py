@@ -187,6 +187,17 @@ def chain_batches(chains: int, n_cols: int) -> list[int]:
     return [int(v) for v in sizes[:n]]
 
 
+def sweep_launch(n_rows: int, n_cols: int, chains: int) -> dict:
+    """The sweep that one batch of ``chains`` chains runs over a shard of ``n_rows`` x ``n_cols``
+    (stk_sweep_launch_info): its kernel ``kind`` (1 k_sweep, 2 k_sweep2, 3 k_sweep3, 4 k_sweep16, 5 the
+    64-chain GEMM passes, 6 k_sweep16w), rows per tile ``T``, the kernel's ``LD`` argument, chunks per
+    shard ``G``, ``lds_bytes`` and ``ws_bytes_per_shard``.  Raises STK_E_ARG where ``chains`` is not a
+    batch size or no sweep covers the shape.  Host only: needs no device."""
+    out = np.zeros(6, np.int64)
+    check(_lib.load().stk_sweep_launch_info(int(n_rows), int(n_cols), int(chains), out.ctypes.data))
+    return dict(zip(("kind", "T", "LD", "G", "lds_bytes", "ws_bytes_per_shard"), (int(v) for v in out)))
+
+
 def _host_shard(family, sh):
     """One shard dict ({"y", "sigma"} or {"x", "y"}) as a ``stk_shard`` of host pointers, plus the
     arrays that keep those pointers alive."""

@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 RTOL_LP = 1e-10   # the bars of test_gpu_kernels.py::test_regression_lpgrad
 
 # rows per shard: five groups of consecutive equal n, shard0 = 0, 2, 3, 4, 5.  Chunks per shard
-# (stk_sweep_geometry): G = 3, 1, 3, 1, 2 for v1 at T = 64, v2, v3 (ceil(ceil(n / 64) / 8)) and
+# (stk_sweep_plan; pinned by test_host_sweep_launch.py): G = 3, 1, 3, 1, 2 for v1 at T = 64, v2, v3 (ceil(ceil(n / 64) / 8)) and
 # k_sweep16, more for v1's smaller tiles, 6, 1, 6, 1, 3 for the 64-chain GEMM passes -- so every
 # variant runs groups whose own G is below the partial-sum stride Gs = max G.
 ROWS = [1500, 1500, 77, 1500, 1, 600]

@@ -173,10 +173,11 @@ int main(int argc, char** argv) {
   for (int g = 0; g < nsh * C; ++g) { qh[(size_t)g * Dp] = 0.01 * ((g % 5) - 2); for (int j = 0; j < d; ++j) qh[(size_t)g * Dp + 1 + j] = beta[j] * (0.9 + 0.002 * g); }
   double *q, *partial; CK(hipMalloc(&q, sizeof(double) * qh.size()));
   CK(hipMemcpy(q, qh.data(), sizeof(double) * qh.size(), hipMemcpyHostToDevice));
-  int T, LD, G; size_t lds; stk_sweep_geometry(rows, d, &T, &LD, &G, &lds, C);
+  const SweepLaunch P = stk_sweep_plan(rows, d, C, 0);
+  const int LD = stk_sweep_args_ld(P), G = P.G; const size_t lds = P.lds;
   CK(hipMalloc(&partial, sizeof(double) * (size_t)nsh * G * C * (d + 2)));
-  void* wsb; CK(hipMalloc(&wsb, stk_sweep_ws_bytes(rows, d, C, nsh)));
-  SweepWs ws = stk_sweep_ws(wsb, rows, d, nsh);
+  void* wsb; CK(hipMalloc(&wsb, P.ws_bytes * nsh));
+  SweepWs ws = stk_sweep_ws(wsb, P, nsh);
   SweepArgs A{sh_d, q, partial, nullptr, 0, C, Dp, G, LD, d + 2, 0, G, nullptr};
   A.Ct = C;
   A.qT = ws.qT; A.R = ws.R; A.Rrows = ws.Rrows;
@@ -271,7 +272,8 @@ int main(int argc, char** argv) {
         launch(*prodB);
       }
       CK(hipGetLastError());
-      CK(stk_launch_sweep_reduce(STK_LOGREG, sh_d, 0, nsh, d, G, G, q, C, Dp, partial, nullptr, 0, lp, grad, st));
+      const SweepCall call{sh_d, q, partial, nullptr, 0, nullptr, &ws, Dp, G, C, 0};
+      CK(stk_launch_sweep_reduce(STK_LOGREG, P, 0, nsh, call, lp, grad, st));
       std::vector<double> h((size_t)nsh * C * (Dp + 1));
       CK(hipMemcpy(h.data(), lp, sizeof(double) * nsh * C, hipMemcpyDeviceToHost));
       CK(hipMemcpy(h.data() + nsh * C, grad, sizeof(double) * nsh * C * Dp, hipMemcpyDeviceToHost));

@@ -22,8 +22,15 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "tools", "_bin")
-SRCS = ["capi.hip", "nuts.hip", "nuts_fused4.hip", "sweep.hip", "sweep16.hip", "datagen.hip", "combine.hip"]
 BASE_FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fvisibility=hidden"]
+
+
+def makefile_srcs(csrc):
+    """The library's sources: the SRCS line of the Makefile beside them (the tree's or the revision's)."""
+    for ln in open(os.path.join(csrc, "Makefile")):
+        if ln.startswith("SRCS :="):
+            return ln.split(":=", 1)[1].split()
+    sys.exit(f"no SRCS line in {csrc}/Makefile")
 
 
 def build(name, rev=None, flags=()):
@@ -48,7 +55,7 @@ def build(name, rev=None, flags=()):
         print("built", os.path.join(out, "libstark_hip.so"), "with the Makefile")
         return
     procs, objs = [], []
-    for s in SRCS:
+    for s in makefile_srcs(csrc):
         o = os.path.join(out, s.replace(".hip", ".o"))
         objs.append(o)
         procs.append(subprocess.Popen(["/opt/rocm/bin/hipcc", *BASE_FLAGS, *extra.get(s, []), "-c",
@@ -78,24 +85,26 @@ def one(arm, work):
         sys.exit(p.stderr[-2000:])
     ln = json.loads(p.stdout.strip().splitlines()[-1])
     if work == "schools":
-        return ln["value"] / 1e6, [ln[k] for k in ("posterior_mean_mu_tau", "min_ess", "divergent", "leapfrogs_per_transition")]
+        return ln["value"] / 1e6, ln["value"], [ln[k] for k in ("posterior_mean_mu_tau", "min_ess", "divergent", "leapfrogs_per_transition")]
     if work in ("sweep16", "sweep16lin"):
-        return ln["roofline"]["avg_launch_ms"], [round(ln["value"] * ln["ms_per_step"])]
-    return ln["roofline"]["avg_launch_ms"], [ln.get("chains_sha16_per_rank")]
+        return ln["roofline"]["avg_launch_ms"], ln["value"], [round(ln["value"] * ln["ms_per_step"])]
+    return ln["roofline"]["avg_launch_ms"], ln["value"], [ln.get("chains_sha16_per_rank")]
 
 
 def run(arms, work, rounds):
     res = {a: [] for a in arms}
+    rate = {a: [] for a in arms}    # the workload's own headline figure (grads/s)
     ident = {}
     for r in range(rounds):
         for a in (arms if r % 2 == 0 else arms[::-1]):
-            v, key = one(a, work)
+            v, rt, key = one(a, work)
             res[a].append(v)
+            rate[a].append(rt)
             ident.setdefault(a, key)
             print(f"[lib_ab] {work} round {r} {a}: {v:.4f}", file=sys.stderr, flush=True)
     med = {a: sorted(v)[len(v) // 2] for a, v in res.items()}
     out = {"work": work, "unit": "M grads/s" if work == "schools" else "ms per launch",
-           "arms": {a: {"values": res[a], "median": med[a],
+           "arms": {a: {"values": res[a], "median": med[a], "rate": rate[a],
                         "build": json.load(open(os.path.join(BIN, f"ab_{a}", "arm.json")))} for a in arms},
            "ratio_vs_first": {a: med[a] / med[arms[0]] for a in arms},
            "identical_to_first": {a: ident[a] == ident[arms[0]] for a in arms}}

@@ -87,9 +87,9 @@ int main(int argc, char** argv) {
   double *q, *partial, *lp, *grad;
   CK(hipMalloc(&q, sizeof(double) * qh.size()));
   CK(hipMemcpy(q, qh.data(), sizeof(double) * qh.size(), hipMemcpyHostToDevice));
-  int T, LD, G;
-  size_t lds;
-  stk_sweep_geometry(rows, d, &T, &LD, &G, &lds, C);
+  const SweepLaunch P = stk_sweep_plan(rows, d, C, 0);
+  const int LD = stk_sweep_args_ld(P), G = P.G;
+  const size_t lds = P.lds;
   CK(hipMalloc(&partial, sizeof(double) * (size_t)nsh * 2048 * C * (d + 2)));   // room for G <= 2048
   CK(hipMalloc(&lp, sizeof(double) * nsh * C));
   CK(hipMalloc(&grad, sizeof(double) * nsh * C * Dp));
@@ -137,7 +137,10 @@ int main(int argc, char** argv) {
     launch(arms[k]);
     CK(hipGetLastError());
     const int Gk = arms[k].G ? arms[k].G : G;
-    CK(stk_launch_sweep_reduce(fam, sh_d, 0, nsh, d, Gk, Gk, q, C, Dp, partial, nullptr, 0, lp, grad, st));
+    SweepLaunch Pk = P;
+    Pk.G = Gk;
+    const SweepCall call{sh_d, q, partial, nullptr, 0, nullptr, nullptr, Dp, Gk, C, 0};
+    CK(stk_launch_sweep_reduce(fam, Pk, 0, nsh, call, lp, grad, st));
     std::vector<double> h((size_t)nsh * C * (Dp + 1));
     CK(hipMemcpyAsync(h.data(), lp, sizeof(double) * nsh * C, hipMemcpyDeviceToHost, st));
     CK(hipMemcpyAsync(h.data() + nsh * C, grad, sizeof(double) * nsh * C * Dp, hipMemcpyDeviceToHost, st));

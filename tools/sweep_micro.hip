@@ -157,7 +157,8 @@ __global__ __launch_bounds__(512) void k_skel3(SweepArgs A, int NB, double* sink
 }  // namespace stk
 
 int main(int argc, char** argv) {
-  if (const char* e = getenv("STARK_SWEEP")) stk_sweep_force_variant = atoi(e);   // this tool only
+  const char* fe = getenv("STARK_SWEEP");
+  const int force = fe ? atoi(fe) : 0;   // this tool only: the library always plans with force = 0
   const int64_t rows = argc > 1 ? atoll(argv[1]) : 12500000;
   const int nsh = argc > 2 ? atoi(argv[2]) : 4;
   const int d = argc > 3 ? atoi(argv[3]) : 100;
@@ -188,18 +189,22 @@ int main(int argc, char** argv) {
   double *q, *partial, *lp, *grad, *sink;
   CK(hipMalloc(&q, sizeof(double) * qh.size()));
   CK(hipMemcpy(q, qh.data(), sizeof(double) * qh.size(), hipMemcpyHostToDevice));
-  int T, LD, G;
-  size_t lds;
-  stk_sweep_geometry(rows, d, &T, &LD, &G, &lds, C);
+  const SweepLaunch P = stk_sweep_plan(rows, d, C, force);
+  if (P.kind == SWEEP_NONE) {
+    fprintf(stderr, "no sweep covers %lld rows x %d at %d chains\n", (long long)rows, d, C);
+    return 2;
+  }
+  const int T = P.T, LD = stk_sweep_args_ld(P), G = P.G;
+  const size_t lds = P.lds;
   CK(hipMalloc(&partial, sizeof(double) * (size_t)nsh * G * C * (d + 2)));
-  const size_t wsb = stk_sweep_ws_bytes(rows, d, C, nsh);
+  const size_t wsb = P.ws_bytes * nsh;
   SweepWs ws{};
   if (wsb) {
     void* wp;
     CK(hipMalloc(&wp, wsb));
-    ws = stk_sweep_ws(wp, rows, d, nsh);
+    ws = stk_sweep_ws(wp, P, nsh);
   }
-  const SweepWs* wsp = wsb ? &ws : nullptr;
+  const SweepCall call{sh_d, q, partial, nullptr, 0, nullptr, wsb ? &ws : nullptr, Dp, G, C, 0};
   CK(hipMalloc(&lp, sizeof(double) * nsh * C));
   CK(hipMalloc(&grad, sizeof(double) * nsh * C * Dp));
   CK(hipMalloc(&sink, sizeof(double) * nsh * G));
@@ -249,7 +254,7 @@ int main(int argc, char** argv) {
       });
     }
   }
-  if (sweep_variant(rows, d, C) == 3) {
+  if (P.kind == SWEEP_V3) {
     SweepArgs A3{sh_d, q, partial, nullptr, 0, C, Dp, G, LD, d + 2, 0, G, nullptr};
     A3.Ct = C;
     auto abl = [&](const char* name, auto kern) {
@@ -263,7 +268,7 @@ int main(int argc, char** argv) {
     abl("v3 -t-b", k_sweep3<STK_LOGREG, 4, 3>);
     abl("v3 -all", k_sweep3<STK_LOGREG, 4, 7>);
   }
-  if (sweep_variant(rows, d, C) == 4 && d == 100) {
+  if (P.kind == SWEEP_16 && d == 100) {
     SweepArgs A4{sh_d, q, partial, nullptr, 0, C, Dp, G, LD, d + 2, 0, G, nullptr};
     A4.Ct = C;
     auto abl = [&](const char* name, auto kern) {
@@ -325,7 +330,7 @@ int main(int argc, char** argv) {
     }
     const double fl = 4.0 * d * C * (double)rows * nsh;   // algorithmic fp64 flops of one sweep
     timeit("v4 flops", fl, [&] {
-      CK(stk_launch_sweep(STK_LOGREG, sh_d, 0, nsh, rows, d, T, LD, G, G, lds, q, C, Dp, partial, nullptr, 0, nullptr, st, wsp));
+      CK(stk_launch_sweep(STK_LOGREG, P, 0, nsh, call, st));
     });
     printf("  (v4 flops line: 'GB/s' column = GFLOP/s of the sweep's 4*d*C flop per row)\n");
     for (int wpb = 1; wpb <= 4; wpb *= 2) {
@@ -337,19 +342,19 @@ int main(int argc, char** argv) {
       });
     }
   }
-  if (sweep_variant(rows, d, C) == 5) {
+  if (P.kind == SWEEP_GEMM64) {
     const double fl = 4.0 * d * C * (double)rows * nsh;
     timeit("v5 flops", fl, [&] {
-      CK(stk_launch_sweep(STK_LOGREG, sh_d, 0, nsh, rows, d, T, LD, G, G, lds, q, C, Dp, partial, nullptr, 0, nullptr, st, wsp));
+      CK(stk_launch_sweep(STK_LOGREG, P, 0, nsh, call, st));
     });
     printf("  (v5 flops line: 'GB/s' column = GFLOP/s of the two GEMMs, 4*d*C flop per row)\n");
   }
   timeit("sweep", bytes, [&] {
-    CK(stk_launch_sweep(STK_LOGREG, sh_d, 0, nsh, rows, d, T, LD, G, G, lds, q, C, Dp, partial, nullptr, 0, nullptr, st, wsp));
+    CK(stk_launch_sweep(STK_LOGREG, P, 0, nsh, call, st));
   });
   timeit("sweep+red", bytes, [&] {
-    CK(stk_launch_sweep(STK_LOGREG, sh_d, 0, nsh, rows, d, T, LD, G, G, lds, q, C, Dp, partial, nullptr, 0, nullptr, st, wsp));
-    CK(stk_launch_sweep_reduce(STK_LOGREG, sh_d, 0, nsh, d, G, G, q, C, Dp, partial, nullptr, 0, lp, grad, st));
+    CK(stk_launch_sweep(STK_LOGREG, P, 0, nsh, call, st));
+    CK(stk_launch_sweep_reduce(STK_LOGREG, P, 0, nsh, call, lp, grad, st));
   });
   CK(hipStreamSynchronize(st));
   return 0;
