@@ -68,12 +68,28 @@ enum {
 };
 
 /* Model families. */
-enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3 };
+enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4 };
+/* STK_POISSON: y ~ poisson_log(alpha + x * beta), the unconstrained parameters (alpha, beta[1..d]) in
+ * the logistic layout (D = d + 1, P = d + 2: alpha, beta, lp__).  With eta_i = alpha + x_i . beta and
+ * mu_i = exp(eta_i), lp = sum_i (y_i eta_i - mu_i) (+ the normal(0, s) prior terms of
+ * stk_model_set_prior), d lp / d alpha = sum_i (y_i - mu_i), d lp / d beta = sum_i x_i (y_i - mu_i):
+ * Stan 2.19's poisson_log_lpmf<propto = true>, which drops lgamma(y + 1) (parity unpinned at Stan).
+ * eta enters y_i eta_i as it is; mu overflows to +inf and underflows to 0 on its own, so where a
+ * row's exp overflows lp is -inf (NaN when y_i eta_i overflowed too), never a finite number, and a
+ * NaN eta stays NaN: the NUTS machine takes such a leaf as divergent, as Stan does.
+ * Everything a logistic model can do works for the family (every entry point below, the three
+ * metrics, both U-turn criteria, saved states), with two refusals, each STK_E_ARG with a message that
+ * names the family: stk_model_create_synthetic (the generator has no Poisson form) and
+ * stk_sampler_set_allreduce (full-data mode stays logistic-only). */
 
 /* One data shard (= one Spark partition, stark/stark.py:35).
  *   schools: n_rows = J, y[J], sigma[J]                   (example/stark_ex.py:8-11)
  *   linreg : x[n_rows * n_cols] row-major, y[n_rows]
- *   logreg : x[n_rows * n_cols] row-major, y_int[n_rows] in {0, 1}                   */
+ *   logreg : x[n_rows * n_cols] row-major, y_int[n_rows] in {0, 1}
+ *   poisson: x[n_rows * n_cols] row-major, y_int[n_rows] >= 0 (checked on the device copy: the
+ *            first negative row is named in the error); y and sigma must be NULL -- counts
+ *            handed over as doubles as well as ints are refused (STK_E_ARG), here and by
+ *            stk_shard_fingerprint_host, instead of one of the two being ignored      */
 typedef struct {
   int64_t n_rows;
   int32_t n_cols;
@@ -172,13 +188,14 @@ STK_API void* stk_ctx_stream(stk_ctx* ctx);                /* hipStream_t of the
 /* ---- models: stark/stark.py:37-39 + :46 ---- */
 STK_API int stk_model_create(stk_ctx* ctx, int family, const stk_shard* shards, int nshards, stk_model** out);
 /* Synthetic shards generated on the device: global rows
- * [row_offset + s*rows_per_shard, row_offset + (s+1)*rows_per_shard) for shard s. */
+ * [row_offset + s*rows_per_shard, row_offset + (s+1)*rows_per_shard) for shard s.  STK_LINREG and
+ * STK_LOGREG only: STK_POISSON is refused (STK_E_ARG), the generator draws no counts. */
 STK_API int stk_model_create_synthetic(stk_ctx* ctx, int family, int nshards, int64_t rows_per_shard,
                                        int64_t row_offset, int32_t n_cols, uint64_t data_seed,
                                        double alpha, const double* beta, double noise_sigma,
                                        stk_model** out);
 STK_API int stk_gen_beta(uint64_t data_seed, int32_t n_cols, double* beta);   /* host, beta ~ N(0, 1/d) */
-/* Regressions: alpha ~ normal(0, alpha_scale), beta ~ normal(0, beta_scale) (each 0 or inf = flat,
+/* Regressions (linear, logistic, poisson): alpha ~ normal(0, alpha_scale), beta ~ normal(0, beta_scale) (each 0 or inf = flat,
  * the default) -- the priors of a `model` block the front end recognises (stark/stark.py:37-39
  * setStanModel of such a program).  Applies to every shard, before sampling. */
 STK_API int stk_model_set_prior(stk_model* m, double alpha_scale, double beta_scale);
@@ -206,10 +223,11 @@ STK_API int stk_model_device_bytes(const stk_model* m, int64_t* bytes);
  * words(a ++ b, t, i0) = words(a, t, i0) + words(b, t, i0 + len(a)), and an integer sum, so every
  * reduction order gives the same bits.
  *
- *   shard fingerprint = fmix( words([family, n_rows, n_cols], 0, 0)     n_cols = 0 for schools
+ *   shard fingerprint = fmix( words([family, n_rows, n_cols], 0, 0)     n_cols = 0 for schools; family is
+ *                                                                        the STK_* value (poisson: 4)
  *                           + words(x: n_rows * n_cols doubles, row-major, 1, 0)   regressions
  *                           + words(y doubles, 2, 0)                    linreg, schools
- *                           + words(y_int int32, 3, 0)                  logreg
+ *                           + words(y_int int32, 3, 0)                  logreg, poisson
  *                           + words(sigma doubles, 4, 0) )              schools
  *
  * Priors are not part of it (the saved state's geometry check covers them).
@@ -322,7 +340,8 @@ STK_API int stk_sampler_load_state(stk_sampler* s, const void* buf, int64_t byte
  * identical inputs, so chain states stay identical without any other exchange.  dev_block:
  * NULL (the library's block), or caller-allocated device memory of `count` doubles used in
  * its place -- e.g. a torch tensor that torch.distributed.all_reduce sums over RCCL.  Logistic
- * family with flat priors only (its log density is a pure sum over rows); call before the first run.
+ * family with flat priors only (its log density is a pure sum over rows; the Poisson family's is
+ * too, but it is refused here by name: full-data mode is logistic-only); call before the first run.
  * No reference counterpart (SURVEY.md 8e "full-data extension"). */
 typedef int (*stk_allreduce_fn)(void* user, double* block, int64_t count, void* stream);
 STK_API int stk_sampler_grad_block(stk_sampler* s, int64_t* count);

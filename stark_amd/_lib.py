@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("STARK_HIP_LIB", os.path.join(_HERE, "_lib", "libstark
 STK_OK = 0
 ERRORS = {-1: "STK_E_ARG", -2: "STK_E_HIP", -3: "STK_E_NOMEM", -4: "STK_E_STATE",
           -5: "STK_E_NUMERIC", -6: "STK_E_NAN", -7: "STK_E_LINALG"}
-STK_SCHOOLS, STK_LINREG, STK_LOGREG = 1, 2, 3
+STK_SCHOOLS, STK_LINREG, STK_LOGREG, STK_POISSON = 1, 2, 3, 4
 N_STATS = 6
 STAT_NAMES = ("accept_stat__", "stepsize__", "treedepth__", "n_leapfrog__", "divergent__", "energy__")
 

@@ -333,11 +333,24 @@ int stk_ctx_set_profiling(stk_ctx* c, int on) {
 void* stk_ctx_stream(stk_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 // ---------------------------------------------------------------- models
+static const char* family_name(int family) {
+  switch (family) {
+    case STK_SCHOOLS: return "schools";
+    case STK_LINREG: return "linear";
+    case STK_LOGREG: return "logistic";
+    case STK_POISSON: return "poisson";
+  }
+  return "unknown";
+}
+
+static bool is_regression(int family) { return family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON; }
+
 static int family_dims(int family, int64_t n, int d, int* D, int* P) {
   switch (family) {
     case STK_SCHOOLS: *D = (int)n + 2; *P = 2 * (int)n + 3; return STK_OK;
     case STK_LINREG: *D = d + 2; *P = d + 3; return STK_OK;
     case STK_LOGREG: *D = d + 1; *P = d + 2; return STK_OK;
+    case STK_POISSON: *D = d + 1; *P = d + 2; return STK_OK;   // the logistic layout: alpha, beta, lp__
   }
   stk_set_error("unknown model family %d", family);
   return STK_E_ARG;
@@ -402,17 +415,24 @@ int stk_model_create(stk_ctx* ctx, int family, const stk_shard* shards, int nsha
       if (!stk_sweep_supported(1, in.n_cols)) { stk_set_error("n_cols %d unsupported (1..1024)", in.n_cols); rc = STK_E_ARG; break; }
       if ((rc = upload(m, in.x, sizeof(double) * in.n_rows * in.n_cols, &p))) break;
       sd.x = (const double*)p;
-      if (family == STK_LOGREG) {
-        if (!in.y_int) { stk_set_error("shard %d: logreg needs y_int", s); rc = STK_E_ARG; break; }
+      if (family == STK_LOGREG || family == STK_POISSON) {
+        const bool pois = family == STK_POISSON;
+        if (!in.y_int) { stk_set_error("shard %d: %s needs y_int", s, pois ? "poisson" : "logreg"); rc = STK_E_ARG; break; }
+        if (pois && (in.y || in.sigma)) {   // counts handed over as doubles too: say so, do not pick one of the two
+          stk_set_error("shard %d: poisson takes its counts in y_int alone; y and sigma must be NULL", s);
+          rc = STK_E_ARG;
+          break;
+        }
         if ((rc = upload(m, in.y_int, sizeof(int32_t) * in.n_rows, &p))) break;
         sd.yi = (const int32_t*)p;
-        {   // bernoulli_logit: y in {0, 1} (the sweeps read y as a sign bit), checked on the device
-            // copy by a reduction that returns the first bad row (8 bytes back, not the shard)
+        {   // bernoulli_logit: y in {0, 1} (the sweeps read y as a sign bit); poisson_log: y >= 0.  Checked
+            // on the device copy by a reduction that returns the first bad row (8 bytes back, not the shard)
           DevBuf flag;
           if ((rc = flag.ensure(sizeof(int64_t)))) break;
           int64_t bad = -1;
           int32_t v = 0;
-          hipError_t e = stk_launch_check_y01(sd.yi, in.n_rows, flag.as<int64_t>(), m->ctx->stream);
+          hipError_t e = pois ? stk_launch_check_ynonneg(sd.yi, in.n_rows, flag.as<int64_t>(), m->ctx->stream)
+                              : stk_launch_check_y01(sd.yi, in.n_rows, flag.as<int64_t>(), m->ctx->stream);
           if (e == hipSuccess) e = hipMemcpyAsync(&bad, flag.p, sizeof(int64_t), hipMemcpyDeviceToHost, m->ctx->stream);
           if (e == hipSuccess) e = hipStreamSynchronize(m->ctx->stream);
           if (e == hipSuccess && bad >= 0 && bad < in.n_rows)
@@ -424,15 +444,20 @@ int stk_model_create(stk_ctx* ctx, int family, const stk_shard* shards, int nsha
             break;
           }
           if (bad >= 0 && bad < in.n_rows) {
-            stk_set_error("shard %d: y_int[%lld] = %d; bernoulli_logit needs 0 or 1", s, (long long)bad, v);
+            if (pois) stk_set_error("shard %d: y_int[%lld] = %d; poisson_log needs y >= 0", s, (long long)bad, v);
+            else stk_set_error("shard %d: y_int[%lld] = %d; bernoulli_logit needs 0 or 1", s, (long long)bad, v);
             rc = STK_E_ARG;
             break;
           }
         }
-      } else {
+      } else if (family == STK_LINREG) {
         if (!in.y) { stk_set_error("shard %d: linreg needs y", s); rc = STK_E_ARG; break; }
         if ((rc = upload(m, in.y, sizeof(double) * in.n_rows, &p))) break;
         sd.y = (const double*)p;
+      } else {   // family_dims knows every family: a new one must say here which y it takes
+        stk_set_error("shard %d: model family %d has no data layout", s, family);
+        rc = STK_E_ARG;
+        break;
       }
     }
     m->sh.push_back(sd);
@@ -457,7 +482,9 @@ int stk_model_create_synthetic(stk_ctx* ctx, int family, int nshards, int64_t ro
                                int32_t n_cols, uint64_t data_seed, double alpha, const double* beta,
                                double noise_sigma, stk_model** out) {
   ARG_CHECK(ctx && out && nshards > 0 && rows_per_shard > 0 && n_cols > 0, "stk_model_create_synthetic: bad arguments");
-  ARG_CHECK(family == STK_LOGREG || family == STK_LINREG, "synthetic shards exist for linreg/logreg only");
+  ARG_CHECK(family == STK_LOGREG || family == STK_LINREG,
+            "synthetic shards exist for linreg/logreg only, not for the %s family (%d): the generator draws nothing "
+            "else, build such shards from host rows with stk_model_create", family_name(family), family);
   ARG_CHECK(stk_sweep_supported(1, n_cols), "n_cols %d unsupported (1..1024)", n_cols);
   STK_HIP_CHECK(hipSetDevice(ctx->device));
   std::vector<double> b(n_cols);
@@ -594,7 +621,7 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
 // group's own G.
 int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_shards: bad arguments");
-  ARG_CHECK(m->family == STK_LOGREG || m->family == STK_LINREG, "stk_log_density_grad_shards: regression families only");
+  ARG_CHECK(is_regression(m->family), "stk_log_density_grad_shards: regression families only");
   ARG_CHECK(hook_single_launch(C, m->d), "points per shard must be a single batch size here: 1, 2, 4, 8, 16 (d <= 128) or 64");
   return hook_every_shard(m, {C}, q, lp, grad);
 }
@@ -603,7 +630,7 @@ int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double
 // run at chains = C.
 int stk_log_density_grad_chains(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_chains: bad arguments");
-  ARG_CHECK(m->family == STK_LOGREG || m->family == STK_LINREG, "stk_log_density_grad_chains: regression families only");
+  ARG_CHECK(is_regression(m->family), "stk_log_density_grad_chains: regression families only");
   ARG_CHECK(!chain_batches(C, m->d).empty(), "no sweep covers %d covariates (1..1024)", m->d);
   return hook_every_shard(m, chain_batches(C, m->d), q, lp, grad);
 }
@@ -705,7 +732,7 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
             "chains_per_wave must be 0, 1, 2 or 4");
   ARG_CHECK(cfg->metric >= 0 && cfg->metric <= 2, "metric must be 0 (diag_e), 1 (dense_e) or 2 (unit_e)");
   ARG_CHECK(cfg->metric != 1 || m->family != STK_SCHOOLS,
-            "metric dense_e is for the regression families (linear, logistic): the fused 8-schools kernel "
+            "metric dense_e is for the regression families (linear, logistic, poisson): the fused 8-schools kernel "
             "has no dense form; use diag_e or unit_e");
   stk_ctx* ctx = m->ctx;
   STK_HIP_CHECK(hipSetDevice(ctx->device));
@@ -988,7 +1015,7 @@ int stk_sampler_run(stk_sampler* s, int32_t target_iter, int64_t max_steps) {
 
 int stk_model_set_prior(stk_model* m, double alpha_scale, double beta_scale) {
   ARG_CHECK(m, "stk_model_set_prior: NULL model");
-  ARG_CHECK(m->family == STK_LOGREG || m->family == STK_LINREG, "priors apply to the regression families");
+  ARG_CHECK(is_regression(m->family), "priors apply to the regression families");
   ARG_CHECK(alpha_scale >= 0.0 && beta_scale >= 0.0, "prior scales must be >= 0 (0 or inf: flat)");
   auto prec = [](double sc) { return (sc == 0.0 || std::isinf(sc)) ? 0.0 : 1.0 / (sc * sc); };
   for (auto& sd : m->sh) {
@@ -1009,7 +1036,8 @@ int stk_sampler_grad_block(stk_sampler* s, int64_t* count) {
 int stk_sampler_set_allreduce(stk_sampler* s, stk_allreduce_fn fn, void* user, double* dev_block) {
   ARG_CHECK(s, "stk_sampler_set_allreduce: NULL sampler");
   ARG_CHECK(s->m->family == STK_LOGREG,
-            "full-data mode needs a purely additive log density (logistic: flat priors, no Jacobian term)");
+            "full-data mode is logistic-only (a purely additive log density: flat priors, no Jacobian term), not for "
+            "the %s family (%d)", family_name(s->m->family), s->m->family);
   ARG_CHECK(s->step == 0, "stk_sampler_set_allreduce: call before the first stk_sampler_run");
   for (const auto& sd : s->m->sh)
     ARG_CHECK(sd.pa == 0.0 && sd.pb == 0.0, "full-data mode: flat priors only (a prior would be summed once per rank)");
@@ -1635,7 +1663,8 @@ int stk_fingerprint_words(stk_ctx* ctx, const void* buf, int64_t count, int32_t 
 
 int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
   ARG_CHECK(sh && out, "stk_shard_fingerprint_host: bad arguments");
-  ARG_CHECK(family == STK_SCHOOLS || family == STK_LINREG || family == STK_LOGREG, "unknown model family %d", family);
+  ARG_CHECK(family == STK_SCHOOLS || family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON,
+            "unknown model family %d", family);
   ARG_CHECK(sh->n_rows > 0, "stk_shard_fingerprint_host: n_rows must be positive");
   uint64_t acc = fp_shard_header(family, sh->n_rows, sh->n_cols);
   if (family == STK_SCHOOLS) {
@@ -1644,8 +1673,10 @@ int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
   } else {
     ARG_CHECK(sh->x && sh->n_cols > 0, "stk_shard_fingerprint_host: regression needs x");
     acc += stk_fp_words_host(sh->x, sh->n_rows * sh->n_cols, 8, 1, 0);
-    if (family == STK_LOGREG) {
-      ARG_CHECK(sh->y_int, "stk_shard_fingerprint_host: logreg needs y_int");
+    if (family == STK_LOGREG || family == STK_POISSON) {
+      ARG_CHECK(sh->y_int, "stk_shard_fingerprint_host: %s needs y_int", family == STK_POISSON ? "poisson" : "logreg");
+      ARG_CHECK(family != STK_POISSON || (!sh->y && !sh->sigma),
+                "stk_shard_fingerprint_host: poisson takes its counts in y_int alone; y and sigma must be NULL");
       acc += stk_fp_words_host(sh->y_int, sh->n_rows, 4, 3, 0);
     } else {
       ARG_CHECK(sh->y, "stk_shard_fingerprint_host: linreg needs y");

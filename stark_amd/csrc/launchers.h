@@ -62,10 +62,17 @@ hipError_t stk_launch_sweep(int family, const stk::SweepLaunch& p, int shard0, i
 hipError_t stk_launch_sweep_reduce(int family, const stk::SweepLaunch& p, int shard0, int nsh, const stk::SweepCall& c,
                                    double* lp_out, double* g_out, hipStream_t st);
 
+// ---- sweep_pois.hip (sweep.hip's Poisson translation unit): the VALU sweeps, pass F and the reduce
+hipError_t stk_launch_sweep_poisson(const stk::SweepLaunch& p, const stk::SweepArgs& A, int nblocks, hipStream_t st);
+hipError_t stk_launch_gemm_fwd_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
+hipError_t stk_launch_sweep_reduce_poisson(const stk::SweepArgs& A, int nblocks_x, int nblocks_y, double* lp_out,
+                                           double* g_out, int C, hipStream_t st);
+
 // ---- sweep16.hip: shapes k_sweep16 covers, its LDS bytes, its launch
 bool stk_sweep16_supported(int d);
 size_t stk_sweep16_lds_bytes(int family, int d);
 hipError_t stk_launch_sweep16(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
+hipError_t stk_launch_sweep16_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16_pois.hip
 
 // ---- sweep16w.hip (128 < d <= 1024): waves per block, chunks per shard, LDS bytes, launch
 bool stk_sweep16w_supported(int d);
@@ -73,6 +80,7 @@ int stk_sweep16w_waves(int d);
 int stk_sweep16w_chunks(int64_t n);
 size_t stk_sweep16w_lds_bytes(int family, int d);
 hipError_t stk_launch_sweep16w(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
+hipError_t stk_launch_sweep16w_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16w_pois.hip
 
 // ---- nuts.hip (and its nuts_fused4.hip / nuts_dense.hip translation units)
 int stk_nch_for(int Dmax);
@@ -88,6 +96,7 @@ hipError_t stk_launch_schools_lpgrad(const stk::ShardDev* shards, int shard, int
 
 // ---- datagen.hip
 hipError_t stk_launch_check_y01(const int32_t* y, int64_t n, int64_t* first, hipStream_t st);
+hipError_t stk_launch_check_ynonneg(const int32_t* y, int64_t n, int64_t* first, hipStream_t st);
 hipError_t stk_launch_gen_shard(double* X, double* yd, int32_t* yi, int64_t nrows, int d, int64_t grow0,
                                 uint64_t seed, double alpha, const double* beta, double noise_sigma, int family,
                                 hipStream_t st);

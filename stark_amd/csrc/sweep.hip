@@ -2,7 +2,8 @@
 //
 // Replaces the gradient Stan's reverse-mode autodiff computes for every leapfrog inside
 // `sm.sampling` (stark/stark.py:48) for the build's regression programs
-// (stark_amd/models/logistic.stan, linear.stan; oracle: orc_logreg_lpgrad / orc_linreg_lpgrad).
+// (stark_amd/models/logistic.stan, linear.stan, poisson.stan; oracle: orc_logreg_lpgrad /
+// orc_linreg_lpgrad; poisson_log: the numpy restatement in tests/test_gpu_poisson.py).
 //
 // One pass over a shard's X serves all C chains of the shard: a 256-thread workgroup
 // streams a chunk of rows in tiles of T rows (T*d*8 <= 64 KB), staged through LDS with a
@@ -12,7 +13,7 @@
 //   residual  d eta[r][c] and the lp terms            (Stan's +-20 cutoff for bernoulli_logit)
 //   backward  g[j][c]  += sum_r x_r[j] * d eta[r][c]  (lanes over columns, rows split RG ways)
 // so X crosses HBM exactly once per leapfrog: algorithmic bytes per sweep = n*(8d + 4)
-// (logreg, int32 y) or n*(8d + 8) (linreg).  Each shard is cut into G chunks that depend
+// (logreg and poisson, int32 y) or n*(8d + 8) (linreg).  Each shard is cut into G chunks that depend
 // only on (n, d); per-chunk partial sums are reduced in chunk order by k_sweep_reduce, so
 // results are bitwise independent of how many shards share a GPU.
 #include "sweep_common.h"
@@ -25,7 +26,11 @@
 
 namespace stk {
 
-
+// A family is a residual, not a kernel: every sweep takes FAM and must know it.
+template <int FAM>
+constexpr bool fam_known = FAM == STK_LINREG || FAM == STK_LOGREG || FAM == STK_POISSON;
+template <int FAM>
+constexpr bool fam_yint = FAM == STK_LOGREG || FAM == STK_POISSON;   // y is the shard's int32 y_int
 
 template <int FAM, int C, int T, int JPT, int VEC>
 __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
@@ -148,7 +153,13 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
             if (nt > 20.0) { lpa[c] -= e; de = sgn * e; }
             else if (nt < -20.0) { lpa[c] += nt; de = sgn; }
             else { lpa[c] -= log1p(e); de = sgn * e / (e + 1.0); }
+          } else if constexpr (FAM == STK_POISSON) {
+            const double yc = (double)gp(sh.yi)[row];
+            const double mu = exp(eta);
+            lpa[c] = fma(yc, eta, lpa[c] - mu);
+            de = yc - mu;
           } else {
+            static_assert(fam_known<FAM>, "k_sweep: unknown family");
             const double is = Al[C + c];
             const double z = (gp(sh.y)[row] - eta) * is;
             lpa[c] += z * z;          // linreg: sum of squares, finished in the reduce
@@ -223,7 +234,8 @@ __global__ __launch_bounds__(256, 2) void k_sweep2(SweepArgs A) {
   constexpr int T = 64, NT = 256, JPT = 2;
   constexpr int CP = (T * C + NT - 1) / NT;       // residual pairs per thread
   constexpr int NVMAX = (T * 128 / 2 + NT - 1) / NT;
-  using yv_t = typename std::conditional<FAM == STK_LOGREG, int32_t, double>::type;
+  static_assert(fam_known<FAM>, "k_sweep2: unknown family");
+  using yv_t = typename std::conditional<fam_yint<FAM>, int32_t, double>::type;
   const int shard = A.shard0 + blockIdx.x / A.G;
   const int chunk = blockIdx.x % A.G;
   if (A.req_step && A.req_step[shard] != A.step_id - 1) return;
@@ -233,7 +245,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep2(SweepArgs A) {
   const int64_t r0 = sh.n * chunk / A.G, r1 = sh.n * (chunk + 1) / A.G;
   const cptr_t<double> qs = cp(A.q) + chain_row(A, shard) * A.Dp;   // chain c: (alpha, beta, [u])
   const gptr_t<double> X = gp(sh.x);
-  const gptr_t<yv_t> Y = (gptr_t<yv_t>)(FAM == STK_LOGREG ? (const void*)sh.yi : (const void*)sh.y);
+  const gptr_t<yv_t> Y = (gptr_t<yv_t>)(fam_yint<FAM> ? (const void*)sh.yi : (const void*)sh.y);
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* Xs = lds;                    // T * LD
@@ -334,6 +346,11 @@ __global__ __launch_bounds__(256, 2) void k_sweep2(SweepArgs A) {
             if (nt > 20.0) { lpa[i] -= e; de = sgn * e; }
             else if (nt < -20.0) { lpa[i] += nt; de = sgn; }
             else { lpa[i] -= log1p(e); de = sgn * e / (e + 1.0); }
+          } else if constexpr (FAM == STK_POISSON) {
+            const double yc = (double)ycur;
+            const double mu = exp(eta);
+            lpa[i] = fma(yc, eta, lpa[i] - mu);
+            de = yc - mu;
           } else {
             const double z = (ycur - eta) * is;
             lpa[i] += z * z;
@@ -414,7 +431,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep2(SweepArgs A) {
 //             and keeps its beta pieces in registers for the whole launch; 3 xor steps sum
 //             the row;
 //   residual  lane i < C of each row group finishes chain i (Stan's bernoulli_logit cutoffs /
-//             normal residual), d eta -> a per-wave LDS scratch;
+//             normal residual / poisson_log's y - exp(eta)), d eta -> a per-wave LDS scratch;
 //   backward  lane k = piece k (2 columns), 8 rows, d eta read as broadcasts.
 // Chunks are whole tiles ([64*t0, 64*t1) rows, a function of (n, d) only) and all sums run in
 // a fixed order, so the result is bitwise independent of shard placement, as for v1/v2.
@@ -479,7 +496,8 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
   const int64_t t0 = nt * chunk / A.G, t1 = nt * (chunk + 1) / A.G;
   const int64_t r0 = t0 * T, r1 = std::min<int64_t>(sh.n, t1 * T);
   const int ntiles = (int)(t1 - t0);
-  constexpr int YB = (FAM == STK_LOGREG) ? 4 : 8;   // y bytes per row
+  static_assert(fam_known<FAM>, "k_sweep3: unknown family");
+  constexpr int YB = fam_yint<FAM> ? 4 : 8;         // y bytes per row
   const int SB = 8 * 16 * K;                        // X bytes of one wave's 8-row sub-tile
   const int SS = sweep3_slot_bytes(K);              // slot: X [0, SB), y [SB, SB + 8*YB)
 
@@ -509,7 +527,7 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
   // nx 1-KiB X pieces (the last one partial) + one size-4 piece for y; buffer descriptors cover
   // exactly the chunk, so a partial last tile reads zeros past its end instead of faulting.
   const __amdgpu_buffer_rsrc_t xr = uniform_rsrc(sh.x + r0 * d, (r1 - r0) * d * 8);
-  const void* ybase = (FAM == STK_LOGREG) ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
+  const void* ybase = fam_yint<FAM> ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
   const __amdgpu_buffer_rsrc_t yr = uniform_rsrc(ybase, (r1 - r0) * YB);
   const int nx = (SB + 1023) >> 10;
   const int last_lanes = (SB - ((nx - 1) << 10)) >> 4;
@@ -583,6 +601,11 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
           if (ntt > 20.0) { const double e = exp(-ntt); lpa -= e; de = sgn * e; }
           else if (ntt < -20.0) { lpa += ntt; de = sgn; }
           else { double lt, wt; softplus_terms(ntt, &lt, &wt); lpa -= lt; de = sgn * wt; }
+        } else if constexpr (FAM == STK_POISSON) {
+          const double yc = (double)*reinterpret_cast<const int32_t*>(ys + frow * 4);
+          const double mu = exp(eta);
+          lpa = fma(yc, eta, lpa - mu);
+          de = yc - mu;
         } else {
           const double yv = *reinterpret_cast<const double*>(ys + frow * 8);
           const double z = (yv - eta) * inv_s;
@@ -674,6 +697,8 @@ __host__ __device__ inline int g5_kp(int d) { return (d + G5_KC - 1) / G5_KC * G
 __device__ __forceinline__ int g5_chain_off(int r, int c) { return r * 512 + ((((c >> 1) ^ ((r & 1) << 3))) << 4) + ((c & 1) << 3); }
 
 // beta^T images for pass F: qT[shard][k][.] = beta_c[k] (0 for k >= d), swizzled as g5_chain_off.
+// (Not a template: defined once, in sweep.hip itself.)
+#ifndef STK_SWEEP_POISSON_TU
 __global__ __launch_bounds__(256) void k_qt_swizzle(SweepArgs A, int d) {
   const int shard = A.shard0 + blockIdx.y;
   if (A.req_step && A.req_step[shard] != A.step_id - 1) return;
@@ -685,6 +710,7 @@ __global__ __launch_bounds__(256) void k_qt_swizzle(SweepArgs A, int d) {
   char* img = reinterpret_cast<char*>(A.qT + (size_t)shard * KP * G5_C);
   *reinterpret_cast<double*>(img + g5_chain_off(k, c)) = v;
 }
+#endif
 
 // A barrier that leaves LDS-DMAs in flight: __syncthreads() makes hipcc drain vmcnt(0) first
 // (an LDS-DMA is a pending LDS write on the VM counter), which would empty the stage ring at
@@ -754,7 +780,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   char* const stg = reinterpret_cast<char*>(lds);      // NS stages of STG bytes
   double* const sptab = reinterpret_cast<double*>(stg + NS * STG);
-  if constexpr (FAM == STK_LOGREG) exp_table_init(sptab);
+  static_assert(fam_known<FAM>, "k_gemm_fwd: unknown family");
+  if constexpr (FAM == STK_LOGREG || FAM == STK_POISSON) exp_table_init(sptab);
   // per-lane chain constants: chain 16 c2 + lr
   const double* qb = A.q + chain_row(A, shard) * A.Dp;
   double alpha[NCT], inv_s[NCT];
@@ -785,7 +812,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
     for (int i = 0; i < NDB; ++i) dma16_lds(br, b + XB + (w * NDB + i) * 1024, lane * 16, kc * KCF * 512 + (w * NDB + i) * 1024);
   };
   // per chain tile: logistic lm = sum(t - |t|) - 2 sum(flushed log1p(sp)), sp = prod(1 + e) - 1
-  // (residual v4, sweep_common.h); linear: lm = sum z^2
+  // (residual v4, sweep_common.h); linear: lm = sum z^2; poisson: lm = sum (y eta - mu), the lp itself
   double lm[NCT], sp[NCT], gaa[NCT];
 #pragma unroll
   for (int c2 = 0; c2 < NCT; ++c2) lm[c2] = sp[c2] = gaa[c2] = 0.0;
@@ -796,6 +823,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
   double pend[RT][NCT][4];                              // the parked tile's eta
   uint32_t ybit = 0u, pybit = 0u;                       // logistic y of this lane's 8 rows of the tile, one bit each
   double yt[RT][4] = {}, pyt[RT][4] = {};               // linear y
+  int32_t yc[RT][4] = {}, pyc[RT][4] = {};              // poisson y: the whole counts, carried as the linear y is
   int ptile = -1;
   auto epi = [&](const int p) {                         // part p = (row tile p / NCT, chain tile p % NCT);
     const int rt = p / NCT, c2 = p % NCT;                // called from unrolled loops: p is a constant
@@ -810,6 +838,10 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
         dv = -logit_resid4(eta, (pybit >> (4 * rt + i)) & 1u, sptab, lm2, sp2);
         lm[c2] = valid ? lm2 : lm[c2];
         sp[c2] = valid ? sp2 : sp[c2];
+      } else if constexpr (FAM == STK_POISSON) {
+        double lm2 = lm[c2];
+        dv = pois_resid(eta, pyc[rt][i], sptab, lm2);
+        lm[c2] = valid ? lm2 : lm[c2];
       } else {
         const double z = (pyt[rt][i] - eta) * inv_s[c2];
         lm[c2] += valid ? z * z : 0.0;
@@ -851,6 +883,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
         for (int i = 0; i < 4; ++i) {
           const int64_t grow = (int64_t)(st / NKC) * TR + 16 * RT * w + 16 * rt + lh + 4 * i;
           if constexpr (FAM == STK_LOGREG) ybit |= (grow < nrows ? (uint32_t)sh.yi[r0 + grow] & 1u : 0u) << (4 * rt + i);
+          else if constexpr (FAM == STK_POISSON) yc[rt][i] = grow < nrows ? sh.yi[r0 + grow] : 0;
           else yt[rt][i] = grow < nrows ? sh.y[r0 + grow] : 0.0;
         }
     }
@@ -882,6 +915,10 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
         for (int i = 0; i < 4; ++i) pend[rt][c2][i] = acc[rt][c2][i] + alpha[c2];
 #pragma unroll
       for (int i = 0; i < 4; ++i) pyt[rt][i] = yt[rt][i];
+      if constexpr (FAM == STK_POISSON) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pyc[rt][i] = yc[rt][i];
+      }
     }
     pybit = ybit;
     ptile = tile;
@@ -906,7 +943,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
 #pragma unroll
     for (int p = 0; p < NPART; ++p) epi(p);
   }
-  double lpa[NCT];
+  double lpa[NCT];   // logistic: the lp pieces joined; linear: sum z^2 and poisson: the lp, both lm as it is
 #pragma unroll
   for (int c2 = 0; c2 < NCT; ++c2) lpa[c2] = (FAM == STK_LOGREG) ? 0.5 * lm[c2] - log1p(sp[c2]) : lm[c2];
 
@@ -1088,10 +1125,11 @@ __global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce(SweepArgs A, double*
       prior_lp = -0.5 * (sh.pa * qc[0] * qc[0] + sh.pb * sb);
     }
   }
-  if (FAM == STK_LOGREG) {
+  static_assert(fam_known<FAM>, "k_sweep_reduce: unknown family");
+  if (FAM == STK_LOGREG || FAM == STK_POISSON) {   // the sums are lp and the gradient themselves
     if (o == d + 1) lp_out[gid] = t + prior_lp;
     else g[o] = t + prior_g;
-  } else {
+  } else {                                         // linear: sigma = exp(u) and its Jacobian
     const double u = qc[d + 1];
     const double N = (double)sh.n;
     if (o == d + 1) {
@@ -1108,6 +1146,13 @@ __global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce(SweepArgs A, double*
 #include "launchers.h"
 using namespace stk;
 
+// In the library (the Makefile's -DSTK_POISSON_OWN_TU) the Poisson instantiations of every kernel
+// above live in their own translation unit, sweep_pois.hip (this file with STK_SWEEP_POISSON_TU: the
+// launch templates below and the three stk_launch_*_poisson entry points), so this file's code
+// object holds the logistic and linear kernels it always did.  Built on its own, without either
+// macro -- the stand-alone tools under tools/ include this file as one translation unit -- it
+// defines the three entry points itself and links as before.
+#ifndef STK_SWEEP_POISSON_TU
 // The single-launch chain counts a sweep covers at d covariates (the batch sizes of the sampler).
 bool stk_sweep_supported(int C, int d) {
   if (C == G5_C) return d >= 1 && d <= 4096;
@@ -1156,7 +1201,7 @@ SweepLaunch stk_sweep_plan(int64_t n, int d, int C, int force) {
     if (stk_sweep16_supported(d)) {
       p.kind = SWEEP_16;
       p.G = sweep_chunks(nt, 8);
-      p.lds = stk_sweep16_lds_bytes(STK_LOGREG, d);   // the larger of the two families
+      p.lds = stk_sweep16_lds_bytes(STK_LOGREG, d);   // the largest of the families (poisson's equals it)
     } else {
       p.kind = SWEEP_16W;
       p.waves = stk_sweep16w_waves(d);
@@ -1229,6 +1274,7 @@ static SweepArgs sweep_args(const SweepLaunch& p, int shard0, const SweepCall& c
   A.c0 = c.c0;
   return A;
 }
+#endif  // STK_SWEEP_POISSON_TU
 
 template <int FAM, int C, int T, int JPT>
 static hipError_t pick_vec(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
@@ -1281,9 +1327,40 @@ static hipError_t pick_c(const SweepLaunch& p, const SweepArgs& A, int nblocks, 
   return hipErrorInvalidValue;
 }
 
+// Pass F of the 64-chain sweep; the split stage schedule needs a tile's NKC = ceil(d / 16) stages to
+// hold its 8 epilogue parts.
+template <int FAM>
+static hipError_t launch_gemm_fwd(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  const bool split = (d + G5_FKC - 1) / G5_FKC >= 8;
+  auto kf = split ? k_gemm_fwd<FAM, G5_FW, 2, G5_FKC, G5_FS, 1> : k_gemm_fwd<FAM>;
+  if (const hipError_t e = allow_big_lds((const void*)kf)) return e;
+  hipLaunchKernelGGL(kf, dim3(nblocks), dim3(64 * G5_FW), lds, st, A);
+  return hipGetLastError();
+}
+
+template <int FAM>
+static hipError_t launch_reduce(const SweepArgs& A, dim3 grid, double* lp_out, double* g_out, int C, hipStream_t st) {
+  hipLaunchKernelGGL(k_sweep_reduce<FAM>, grid, dim3(64 * RD_W), 0, st, A, lp_out, g_out, C);
+  return hipGetLastError();
+}
+
+#if defined(STK_SWEEP_POISSON_TU) || !defined(STK_POISSON_OWN_TU)
+hipError_t stk_launch_sweep_poisson(const SweepLaunch& p, const SweepArgs& A, int nblocks, hipStream_t st) {
+  return pick_c<STK_POISSON>(p, A, nblocks, st);
+}
+hipError_t stk_launch_gemm_fwd_poisson(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  return launch_gemm_fwd<STK_POISSON>(A, d, nblocks, lds, st);
+}
+hipError_t stk_launch_sweep_reduce_poisson(const SweepArgs& A, int nblocks_x, int nblocks_y, double* lp_out, double* g_out,
+                                           int C, hipStream_t st) {
+  return launch_reduce<STK_POISSON>(A, dim3(nblocks_x, nblocks_y), lp_out, g_out, C, st);
+}
+#endif
+#ifndef STK_SWEEP_POISSON_TU
 // Launch the plan's sweep over `nsh` shards starting at shard0 (all of the plan's n) for the batch
 // of p.C chains that starts at chain c.c0 of every shard's c.Ct.
 hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int nsh, const SweepCall& c, hipStream_t st) {
+  if (family != STK_LOGREG && family != STK_LINREG && family != STK_POISSON) return hipErrorInvalidValue;
   SweepArgs A = sweep_args(p, shard0, c, stk_sweep_args_ld(p));
   const int nblocks = nsh * p.G, d = p.d;
   if (p.kind == SWEEP_GEMM64) {
@@ -1293,12 +1370,10 @@ hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int ns
     A.Rrows = c.ws->Rrows;
     const int bjb = g5_bjb(d), njb = (d + bjb - 1) / bjb;
     hipLaunchKernelGGL(k_qt_swizzle, dim3((g5_kp(d) * G5_C + 255) / 256, nsh), dim3(256), 0, st, A, d);
-    // the split stage schedule needs a tile's NKC = ceil(d / 16) stages to hold its 8 epilogue parts
-    const bool split = (d + G5_FKC - 1) / G5_FKC >= 8;
-    auto kf = family == STK_LOGREG ? (split ? k_gemm_fwd<STK_LOGREG, G5_FW, 2, G5_FKC, G5_FS, 1> : k_gemm_fwd<STK_LOGREG>)
-                                   : (split ? k_gemm_fwd<STK_LINREG, G5_FW, 2, G5_FKC, G5_FS, 1> : k_gemm_fwd<STK_LINREG>);
-    if (const hipError_t e = allow_big_lds((const void*)kf)) return e;
-    hipLaunchKernelGGL(kf, dim3(nblocks), dim3(64 * G5_FW), p.lds, st, A);
+    const hipError_t ef = family == STK_LOGREG   ? launch_gemm_fwd<STK_LOGREG>(A, d, nblocks, p.lds, st)
+                          : family == STK_LINREG ? launch_gemm_fwd<STK_LINREG>(A, d, nblocks, p.lds, st)
+                                                 : stk_launch_gemm_fwd_poisson(A, d, nblocks, p.lds, st);
+    if (ef != hipSuccess) return ef;
     auto kb = bjb == 64 ? k_gemm_bwd<64> : bjb == 128 ? k_gemm_bwd<128> : k_gemm_bwd<256>;
     if (const hipError_t e = allow_big_lds((const void*)kb)) return e;
     hipLaunchKernelGGL(kb, dim3(nblocks * njb), dim3(64 * G5_BW), G5_BNS * g5_bstage_bytes(bjb), st, A, njb);
@@ -1306,7 +1381,7 @@ hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int ns
   }
   if (family == STK_LOGREG) return pick_c<STK_LOGREG>(p, A, nblocks, st);
   if (family == STK_LINREG) return pick_c<STK_LINREG>(p, A, nblocks, st);
-  return hipErrorInvalidValue;
+  return stk_launch_sweep_poisson(p, A, nblocks, st);
 }
 
 hipError_t stk_launch_sweep_reduce(int family, const SweepLaunch& p, int shard0, int nsh, const SweepCall& c,
@@ -1314,9 +1389,9 @@ hipError_t stk_launch_sweep_reduce(int family, const SweepLaunch& p, int shard0,
   SweepArgs A = sweep_args(p, shard0, c, 0);
   A.ran = nullptr;
   dim3 grid(nsh * p.C, (p.d + 2 + 63) / 64);
-  if (family == STK_LOGREG)
-    hipLaunchKernelGGL(k_sweep_reduce<STK_LOGREG>, grid, dim3(64 * RD_W), 0, st, A, lp_out, g_out, p.C);
-  else
-    hipLaunchKernelGGL(k_sweep_reduce<STK_LINREG>, grid, dim3(64 * RD_W), 0, st, A, lp_out, g_out, p.C);
-  return hipGetLastError();
+  if (family == STK_LOGREG) return launch_reduce<STK_LOGREG>(A, grid, lp_out, g_out, p.C, st);
+  if (family == STK_LINREG) return launch_reduce<STK_LINREG>(A, grid, lp_out, g_out, p.C, st);
+  if (family == STK_POISSON) return stk_launch_sweep_reduce_poisson(A, grid.x, grid.y, lp_out, g_out, p.C, st);
+  return hipErrorInvalidValue;
 }
+#endif  // STK_SWEEP_POISSON_TU

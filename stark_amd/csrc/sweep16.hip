@@ -3,7 +3,7 @@
 //
 // Replaces the gradient Stan's reverse-mode autodiff computes for every leapfrog inside
 // `sm.sampling` (stark/stark.py:48) for the regression programs (oracle: orc_logreg_lpgrad /
-// orc_linreg_lpgrad).  With 16 chains sharing a shard, X . [beta_1 .. beta_16] is a dense GEMM
+// orc_linreg_lpgrad; poisson_log: the numpy restatement in tests/test_gpu_poisson.py).  With 16 chains sharing a shard, X . [beta_1 .. beta_16] is a dense GEMM
 // (8 flop per byte of X at d = 100) and the sweep is bound by the fp64 pipe at the clock the
 // chip holds under it, not by HBM: every vector instruction takes the issue slot an fp64 MFMA
 // needs (tools/valu_mix.hip), so the design goal is the fewest vector instructions per row
@@ -22,7 +22,8 @@
 //             slot takes the DMA of the next sub-tile (d <= 108 logistic, every d linear; past
 //             that the slot is released after the backward: registers);
 //   residual  on the MFMA output registers (lane: rows lh + 4i, chain lane&15) -- logistic:
-//             logit_resid4 below; linear: z = (y - eta)/sigma;
+//             logit_resid4 below; linear: z = (y - eta)/sigma; poisson: pois_resid (the whole
+//             int32 count from the slot, the same exp table);
 //   backward  G[16 cols][16 chains] += X_tile^T . d_eta: the D layout of the forward is the B
 //             layout of the backward (k-step s = rows 4s..4s+3 = register s), one MFMA per
 //             (16-column tile, k-step); a last tile of <= 4 columns runs on the VALU (16 DPP
@@ -54,6 +55,8 @@ __host__ __device__ constexpr S16Geom s16_geom(int KF) {
 // SIMD's other wave only).  beta in registers instead of a block image in LDS: 14.00 -> 13.84 and
 // 14.24 -> 14.05 ms at d = 100 on two boxes, 7.03 -> 6.92 and 7.15 -> 7.04 ms at d = 50 linear
 // (profiles/r04q_*, r04s_*).
+// Poisson keeps the logistic rule: its residual is lighter (KF = 27: 248 VGPRs against 256), but
+// beta and the operands are the same 4 JTM + KF doubles.
 __host__ __device__ constexpr bool s16_pre(int FAM, int KF) { return FAM == STK_LINREG || KF <= 27; }
 constexpr int S16_FLUSH = 64;                   // sub-tiles between log1p flushes (4 elements each)
 
@@ -61,7 +64,8 @@ template <int FAM, int KF, bool PRE = s16_pre(FAM, KF), int NACC = 2>
 __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   constexpr S16Geom g = s16_geom(KF);
   constexpr int C = SM_C, NW = SM_W, JTM = g.JTM;
-  constexpr bool LOGI = FAM == STK_LOGREG;
+  constexpr bool LOGI = FAM == STK_LOGREG, POIS = FAM == STK_POISSON;
+  static_assert(LOGI || POIS || FAM == STK_LINREG, "k_sweep16: unknown family");
   const int shard = A.shard0 + blockIdx.x / A.G;
   const int chunk = blockIdx.x % A.G;
   if (A.req_step && A.req_step[shard] != A.step_id - 1) return;
@@ -76,14 +80,14 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   const int nrows = (int)(r1 - r0);
   const int nsub = (nrows + SM_R - 1) / SM_R;
   const int mine = nsub > w ? (nsub - w + NW - 1) / NW : 0;   // own sub-tiles u = w + NW k
-  constexpr int YB = LOGI ? 4 : 8;
+  constexpr int YB = (LOGI || POIS) ? 4 : 8;       // int32 y (logistic, poisson) or double y
   const int SBX = SM_R * d * 8;
   const int SS = sweepm_slot_bytes(d);
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
   char* const slot = reinterpret_cast<char*>(lds) + (size_t)w * SS;
   double* const tab = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + (size_t)NW * SS);
-  if constexpr (LOGI) exp_table_init(tab);
+  if constexpr (LOGI || POIS) exp_table_init(tab);
   const double* qs = A.q + chain_row(A, shard) * A.Dp;
   double bf[KF];                   // beta_{lr} at the column k-step s of lane group lh takes (forward)
 #pragma unroll
@@ -92,12 +96,12 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
     bf[s] = col < d ? qs[(size_t)lr * A.Dp + 1 + col] : 0.0;
   }
   const double alpha = qs[(size_t)lr * A.Dp];
-  const double inv_s = LOGI ? 0.0 : exp(-qs[(size_t)lr * A.Dp + d + 1]);
+  const double inv_s = FAM == STK_LINREG ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : 0.0;
   __syncthreads();
   __builtin_amdgcn_s_waitcnt(0xF70);
 
   const __amdgpu_buffer_rsrc_t xr = uniform_rsrc(sh.x + r0 * d, (int64_t)nrows * d * 8);
-  const void* ybase = LOGI ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
+  const void* ybase = (LOGI || POIS) ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
   const __amdgpu_buffer_rsrc_t yr = uniform_rsrc(ybase, (int64_t)nrows * YB);
   const int nx = (SBX + 1023) >> 10;
   const int last_lanes = (SBX - ((nx - 1) << 10)) >> 4;
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
 #pragma unroll
   for (int t = 0; t < JTM; ++t) gacc[t] = dbl4{0.0, 0.0, 0.0, 0.0};
   double gv[4] = {0.0, 0.0, 0.0, 0.0};
-  double lm = 0.0, sp = 0.0, ll = 0.0, ga = 0.0;   // logistic lp pieces (linear: lm = sum z^2)
+  double lm = 0.0, sp = 0.0, ll = 0.0, ga = 0.0;   // logistic lp pieces (linear: lm = sum z^2; poisson: lm = lp)
   const double* xs = reinterpret_cast<const double*>(slot);
   // column of the backward's A operand in tile t: only a last MFMA tile (no VALU remainder) can
   // reach past d - 1 (VREM: 16 JTM = 4 KF - 4 <= d), so only it is clamped -- a clamp with the
@@ -173,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
     double yv[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if constexpr (LOGI)   // y in {0, 1}
+      if constexpr (LOGI || POIS)   // int32 y: {0, 1} (logistic), the whole count (poisson)
         ym[i] = *reinterpret_cast<const uint32_t*>(slot + SBX + (lh + 4 * i) * 4);
       else
         yv[i] = *reinterpret_cast<const double*>(slot + SBX + (lh + 4 * i) * 8);
@@ -198,6 +202,8 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
       for (int i = 0; i < 4; ++i) {
         if constexpr (LOGI) {
           de[i] = logit_resid4(eta4[i], ym[i], tab, lm, sp);
+        } else if constexpr (POIS) {
+          de[i] = pois_resid(eta4[i], (int32_t)ym[i], tab, lm);
         } else {
           const double z = (yv[i] - eta4[i]) * inv_s;
           lm = fma(z, z, lm);
@@ -212,6 +218,8 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
         double lm2 = lm, sp2 = sp, dv;
         if constexpr (LOGI) {
           dv = logit_resid4(eta4[i], ym[i], tab, lm2, sp2);
+        } else if constexpr (POIS) {
+          dv = pois_resid(eta4[i], (int32_t)ym[i], tab, lm2);
         } else {
           const double z = (yv[i] - eta4[i]) * inv_s;
           lm2 = fma(z, z, lm);
@@ -268,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
     for (int t = 0; t < JTM; ++t) gacc[t] = -gacc[t];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) gv[jj] = -gv[jj];
-  } else {
+  } else {   // linear: sum z^2, finished in the reduce; poisson: lp itself (pois_resid returns dv)
     lpa = lm;
   }
 
@@ -317,15 +325,17 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
 #include "launchers.h"
 using namespace stk;
 
+#ifndef STK_SWEEP16_POISSON_TU
 // LDS bytes of k_sweep16 at d (the main loop's slots + table + remainder scratch, or the block
 // reduction's area, whichever is larger).
 size_t stk_sweep16_lds_bytes(int family, int d) {
   const int KF = (d + 3) / 4;
   const S16Geom g = s16_geom(KF);
-  size_t main = (size_t)SM_W * sweepm_slot_bytes(d) + (family == STK_LOGREG ? EX_TAB * 8 : 0);
+  size_t main = (size_t)SM_W * sweepm_slot_bytes(d) + (family == STK_LINREG ? 0 : EX_TAB * 8);   // logistic, poisson: the exp table
   const size_t red = ((size_t)SM_W * g.JT * 16 * 16 + (size_t)SM_W * 64 * 2 + (size_t)SM_W * 4 * 4 * 16) * 8;
   return std::max(main, red);
 }
+#endif
 
 template <int FAM, int KF>
 static hipError_t go16(const SweepArgs& A, int nblocks, size_t lds, hipStream_t st) {
@@ -348,10 +358,22 @@ static hipError_t launch16(const SweepArgs& A, int d, int nblocks, size_t lds, h
   return hipErrorInvalidValue;
 }
 
+// In the library (-DSTK_POISSON_OWN_TU) the Poisson instantiations of k_sweep16 live in their own
+// translation unit, sweep16_pois.hip (this file with STK_SWEEP16_POISSON_TU), so the logistic and
+// linear ones compile as before; built on its own (the tools under tools/) this file defines the
+// Poisson launcher itself.
+#if defined(STK_SWEEP16_POISSON_TU) || !defined(STK_POISSON_OWN_TU)
+hipError_t stk_launch_sweep16_poisson(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  return launch16<STK_POISSON>(A, d, nblocks, lds, st);
+}
+#endif
+#ifndef STK_SWEEP16_POISSON_TU
 bool stk_sweep16_supported(int d) { return d >= 1 && d <= 128; }
 
 hipError_t stk_launch_sweep16(int family, const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
   if (family == STK_LOGREG) return launch16<STK_LOGREG>(A, d, nblocks, lds, st);
   if (family == STK_LINREG) return launch16<STK_LINREG>(A, d, nblocks, lds, st);
+  if (family == STK_POISSON) return stk_launch_sweep16_poisson(A, d, nblocks, lds, st);
   return hipErrorInvalidValue;
 }
+#endif

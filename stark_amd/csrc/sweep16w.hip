@@ -20,7 +20,7 @@
 //             exchange area and y for the next sub-tile.  No DMA is in flight at either barrier
 //             (the slab is waited for at the top of the sub-tile and reissued at its end), so
 //             both are plain __syncthreads(): its vmcnt drain has nothing to wait for;
-//   residual  logit_resid4 / the linear z on the summed eta, redundantly in every wave; wave 0's
+//   residual  logit_resid4 / the linear z / pois_resid on the summed eta, redundantly in every wave; wave 0's
 //             lp terms and d/d alpha are the ones written out;
 //   backward  G[slab columns][16 chains] += X_slab^T . d_eta from the wave's own slot, one MFMA per
 //             (16-column tile, k-step); then the wave reissues its slab's DMA for the next sub-tile
@@ -58,8 +58,9 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   constexpr int RSB = sw_row_bytes(DW), SLOTB = sw_slot_bytes(DW);
   constexpr int PPR = DW / 2 + 1;                   // 16-B pieces per padded row
   constexpr int NI = (SM_R * PPR + 63) / 64;        // DMA instructions per slot; the last one has 16 lanes
-  constexpr bool LOGI = FAM == STK_LOGREG;
-  constexpr int YB = LOGI ? 4 : 8;
+  constexpr bool LOGI = FAM == STK_LOGREG, POIS = FAM == STK_POISSON;
+  static_assert(LOGI || POIS || FAM == STK_LINREG, "k_sweep16w: unknown family");
+  constexpr int YB = (LOGI || POIS) ? 4 : 8;        // int32 y (logistic, poisson) or double y
   static_assert(KF % 4 == 0 && DW <= 128 && (SM_R * PPR) % 64 == 16, "slab geometry");
   const int NW = A.LD;                              // waves per block = column slabs
   const int shard = A.shard0 + blockIdx.x / A.G;
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   char* const ybuf = reinterpret_cast<char*>(lds) + (size_t)NW * SLOTB;
   double* const exch = reinterpret_cast<double*>(ybuf + SW_YB);   // [NW][4 registers][64 lanes]
   double* const tab = exch + (size_t)NW * 256;
-  if constexpr (LOGI) exp_table_init(tab);
+  if constexpr (LOGI || POIS) exp_table_init(tab);
   const double* qs = A.q + chain_row(A, shard) * A.Dp;
   double bf[KF];                   // beta_{lr} at column j0 + lh KF + s (k-step s of lane group lh)
 #pragma unroll
@@ -92,12 +93,12 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
     bf[s] = col < d ? qs[(size_t)lr * A.Dp + 1 + col] : 0.0;
   }
   const double alpha = w == 0 ? qs[(size_t)lr * A.Dp] : 0.0;   // wave 0's partial starts at alpha
-  const double inv_s = LOGI ? 0.0 : exp(-qs[(size_t)lr * A.Dp + d + 1]);
+  const double inv_s = FAM == STK_LINREG ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : 0.0;
   __syncthreads();
   __builtin_amdgcn_s_waitcnt(0xF70);
 
   const __amdgpu_buffer_rsrc_t xr = uniform_rsrc(sh.x + r0 * d, (int64_t)nrows * d * 8);
-  const void* ybase = LOGI ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
+  const void* ybase = (LOGI || POIS) ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
   const __amdgpu_buffer_rsrc_t yr = uniform_rsrc(ybase, (int64_t)nrows * YB);
   // piece p = 64 j + lane of the slot image is piece p % PPR of row p / PPR; the pad piece and the
   // pieces past column d - 1 repeat the row's last valid piece (finite data under a zero beta)
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   dbl4 gacc[JT];
 #pragma unroll
   for (int t = 0; t < JT; ++t) gacc[t] = dbl4{0.0, 0.0, 0.0, 0.0};
-  double lm = 0.0, sp = 0.0, ll = 0.0, ga = 0.0;   // logistic lp pieces (linear: lm = sum z^2)
+  double lm = 0.0, sp = 0.0, ll = 0.0, ga = 0.0;   // logistic lp pieces (linear: lm = sum z^2; poisson: lm = lp)
   const char* const xfw = slot + lr * RSB + lh * KF * 8;    // forward A: row lr, columns lh KF + s
   const char* const xbw = slot + lh * RSB + lr * 8;         // backward A: row lh + 4s, column 16t + lr
 
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
     double yv[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if constexpr (LOGI)   // y in {0, 1}
+      if constexpr (LOGI || POIS)   // int32 y: {0, 1} (logistic), the whole count (poisson)
         ym[i] = *reinterpret_cast<const uint32_t*>(ybuf + (lh + 4 * i) * 4);
       else
         yv[i] = *reinterpret_cast<const double*>(ybuf + (lh + 4 * i) * 8);
@@ -165,6 +166,8 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
       for (int i = 0; i < 4; ++i) {
         if constexpr (LOGI) {
           de[i] = logit_resid4(eta4[i], ym[i], tab, lm, sp);
+        } else if constexpr (POIS) {
+          de[i] = pois_resid(eta4[i], (int32_t)ym[i], tab, lm);
         } else {
           const double z = (yv[i] - eta4[i]) * inv_s;
           lm = fma(z, z, lm);
@@ -179,6 +182,8 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
         double lm2 = lm, sp2 = sp, dv;
         if constexpr (LOGI) {
           dv = logit_resid4(eta4[i], ym[i], tab, lm2, sp2);
+        } else if constexpr (POIS) {
+          dv = pois_resid(eta4[i], (int32_t)ym[i], tab, lm2);
         } else {
           const double z = (yv[i] - eta4[i]) * inv_s;
           lm2 = fma(z, z, lm);
@@ -213,7 +218,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
     ga = -ga;
 #pragma unroll
     for (int t = 0; t < JT; ++t) gacc[t] = -gacc[t];
-  } else {
+  } else {   // linear: sum z^2, finished in the reduce; poisson: lp itself (pois_resid returns dv)
     lpa = lm;
   }
 
@@ -244,6 +249,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
 #include "launchers.h"
 using namespace stk;
 
+#ifndef STK_SWEEP16W_POISSON_TU
 bool stk_sweep16w_supported(int d) { return d > 128 && d <= 128 * SW_MAXW; }
 int stk_sweep16w_waves(int d) { return sw_waves(d); }
 int stk_sweep16w_chunks(int64_t n) {                  // >= SW_TILES tiles of 64 rows per chunk
@@ -252,8 +258,10 @@ int stk_sweep16w_chunks(int64_t n) {                  // >= SW_TILES tiles of 64
 }
 size_t stk_sweep16w_lds_bytes(int family, int d) {
   const int nw = sw_waves(d);
-  return (size_t)nw * sw_slot_bytes(sw_slab(d)) + SW_YB + (size_t)nw * 256 * 8 + (family == STK_LOGREG ? EX_TAB * 8 : 0);
+  return (size_t)nw * sw_slot_bytes(sw_slab(d)) + SW_YB + (size_t)nw * 256 * 8 +
+         (family == STK_LINREG ? 0 : EX_TAB * 8);   // logistic, poisson: the exp table
 }
+#endif
 
 template <int FAM, int KF>
 static hipError_t go16w(const SweepArgs& A, int nblocks, size_t lds, hipStream_t st) {
@@ -274,10 +282,22 @@ static hipError_t launch16w(const SweepArgs& A, int d, int nblocks, size_t lds, 
   return hipErrorInvalidValue;
 }
 
+// In the library (-DSTK_POISSON_OWN_TU) the Poisson instantiations of k_sweep16w live in their own
+// translation unit, sweep16w_pois.hip (this file with STK_SWEEP16W_POISSON_TU), so the logistic and
+// linear ones compile as before; built on its own (the tools under tools/) this file defines the
+// Poisson launcher itself.
+#if defined(STK_SWEEP16W_POISSON_TU) || !defined(STK_POISSON_OWN_TU)
+hipError_t stk_launch_sweep16w_poisson(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  return launch16w<STK_POISSON>(A, d, nblocks, lds, st);   // the caller (stk_launch_sweep16w) checked the shape
+}
+#endif
+#ifndef STK_SWEEP16W_POISSON_TU
 hipError_t stk_launch_sweep16w(int family, const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
   if (!stk_sweep16w_supported(d) || A.LD != sw_waves(d) || lds < stk_sweep16w_lds_bytes(family, d) || lds > BIG_LDS_BYTES)
     return hipErrorInvalidValue;
   if (family == STK_LOGREG) return launch16w<STK_LOGREG>(A, d, nblocks, lds, st);
   if (family == STK_LINREG) return launch16w<STK_LINREG>(A, d, nblocks, lds, st);
+  if (family == STK_POISSON) return stk_launch_sweep16w_poisson(A, d, nblocks, lds, st);
   return hipErrorInvalidValue;
 }
+#endif

@@ -14,10 +14,10 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_SCHOOLS, Config, RunInfo, Shard,
+from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_POISSON, STK_SCHOOLS, Config, RunInfo, Shard,
                    StarkHipError, check)
 
-FAMILIES = {"schools": STK_SCHOOLS, "linear": STK_LINREG, "logistic": STK_LOGREG}
+FAMILIES = {"schools": STK_SCHOOLS, "linear": STK_LINREG, "logistic": STK_LOGREG, "poisson": STK_POISSON}
 
 # Live library handles, closed in dependency order (samplers, models, contexts) before the
 # HIP runtime's own exit handlers run; after that every close() is a no-op.
@@ -215,6 +215,12 @@ def _host_shard(family, sh):
         if np.any((y != 0) & (y != 1)):
             raise ValueError("bernoulli_logit: y must be 0 or 1")
         shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, None, y.ctypes.data, None)
+    elif family == STK_POISSON:
+        y = np.asarray(sh["y"])
+        if y.dtype.kind not in "iuf" or not np.all(y == np.round(y)) or np.any(y < 0) or np.any(y > np.iinfo(np.int32).max):
+            raise ValueError("poisson_log: y must hold integers in 0 .. 2^31 - 1")
+        y = np.ascontiguousarray(y, np.int32)
+        shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, None, y.ctypes.data, None)
     else:
         y = np.ascontiguousarray(sh["y"], np.float64)
         shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, y.ctypes.data, None, None)
@@ -305,7 +311,8 @@ class Model:
     @classmethod
     def synthetic(cls, ctx: Context, family, nshards: int, rows_per_shard: int, n_cols: int, data_seed: int = 20240,
                   row_offset: int = 0, alpha: float = 0.0, beta=None, noise_sigma: float = 1.0):
-        """Shards generated in HBM by the Philox generator."""
+        """Shards generated in HBM by the Philox generator: linear and logistic only
+        (the library refuses "poisson": the generator draws no counts)."""
         fam = FAMILIES.get(family, family)
         b = None
         if beta is not None:
@@ -348,7 +355,7 @@ class Model:
     def device_arrays(self, shard: int) -> dict:
         """Device addresses of the shard's arrays with their word counts (stk_model_shard_arrays):
         {"x": (ptr, n * d), "y": (ptr, n), ...} for the arrays the family has ("y" of a logistic
-        shard is int32).  Read-only, valid while the model lives."""
+        or poisson shard is int32).  Read-only, valid while the model lives."""
         sh = Shard()
         check(_lib.load().stk_model_shard_arrays(self._h, int(shard), ctypes.byref(sh)))
         out = {}
@@ -367,9 +374,10 @@ class Model:
             y = np.empty(n)
             check(lib.stk_model_copy_data(self._h, shard, None, y.ctypes.data, None))
             return {"y": y}
-        d = D - (1 if self.family == STK_LOGREG else 2)
+        yint = self.family in (STK_LOGREG, STK_POISSON)
+        d = D - (1 if yint else 2)
         x = np.empty((n, d))
-        if self.family == STK_LOGREG:
+        if yint:
             y = np.empty(n, np.int32)
             check(lib.stk_model_copy_data(self._h, shard, x.ctypes.data, None, y.ctypes.data))
         else:

@@ -76,15 +76,15 @@ def program_info(model_code: str):
         fam = None
     if fam is None:
         raise NotImplementedError(
-            "stark_amd runs a fixed set of model families on the GPU (8 schools, Bayesian linear and logistic "
-            "regression with flat or normal(0, s) priors on alpha and beta; see stark_amd/models/*.stan).  This "
-            "Stan program is not one of them; pass family='schools'|'linear'|'logistic' if it is an equivalent "
-            "program.")
+            "stark_amd runs a fixed set of model families on the GPU (8 schools, Bayesian linear, logistic and "
+            "Poisson (poisson_log) regression with flat or normal(0, s) priors on alpha and beta; see "
+            "stark_amd/models/*.stan).  This Stan program is not one of them; pass "
+            "family='schools'|'linear'|'logistic'|'poisson' if it is an equivalent program.")
     return fam, priors
 
 
 def recognise(model_code: str) -> str:
-    """Return 'schools', 'linear' or 'logistic' for a supported Stan program."""
+    """Return 'schools', 'linear', 'logistic' or 'poisson' for a supported Stan program."""
     return program_info(model_code)[0]
 
 
@@ -103,6 +103,11 @@ def _recognise_blocks(b: dict, stm: list):
         if stm in (["y~bernoulli_logit(alpha+x*beta)"], ["y~bernoulli_logit(x*beta+alpha)"]):
             if not _decl(params, r"sigma"):
                 return "logistic"
+        if stm in (["y~poisson_log(alpha+x*beta)"], ["y~poisson_log(x*beta+alpha)"]):
+            # counts: int<lower=0> y[N] or array[N] int<lower=0> y (poisson(exp(...)) and poisson_log_glm
+            # are other programs to this recogniser)
+            if not _decl(params, r"sigma") and _decl(b.get("data", ""), r"(int<lower=0>y\[N\]|array\[N\]int<lower=0>y)(;|$)"):
+                return "poisson"
         if stm in (["y~normal(alpha+x*beta,sigma)"], ["y~normal(x*beta+alpha,sigma)"]):
             if _decl(params, r"real<lower=0>sigma"):
                 return "linear"
@@ -113,7 +118,7 @@ def load_program_info(file=None, model_code=None, family=None, priors=None, **_i
     """Mirror of pystan.StanModel(file=..., model_code=...) argument handling -> (family, priors).
     family= (and priors={'alpha': s, 'beta': s}) override recognition."""
     if family is not None:
-        if family not in ("schools", "linear", "logistic"):
+        if family not in ("schools", "linear", "logistic", "poisson"):
             raise ValueError(f"unknown family {family!r}")
         return family, dict(priors or {})
     if model_code is None:
@@ -151,6 +156,15 @@ def pack_data(family: str, data: dict) -> dict:
         yf = y.astype(np.float64)
         if not np.all(yf == np.round(yf)) or np.any((yf != 0) & (yf != 1)):
             raise ValueError("bernoulli_logit data: y must hold the integers 0 and 1")
+        return {"x": x, "y": yf.astype(np.int32)}
+    if family == "poisson":
+        y = np.asarray(data["y"]).reshape(-1)
+        if y.shape[0] != N:
+            raise ValueError("y must have N entries")
+        # int<lower=0> y[N]: pystan rejects non-integer or negative values; the shard stores int32
+        yf = y.astype(np.float64)
+        if not np.all(yf == np.round(yf)) or np.any(yf < 0) or np.any(yf > 2147483647):
+            raise ValueError("poisson_log data: y must hold integers >= 0 (and <= 2^31 - 1)")
         return {"x": x, "y": yf.astype(np.int32)}
     y = np.asarray(data["y"], np.float64).reshape(-1)
     if y.shape[0] != N:

@@ -13,6 +13,7 @@ without a host sync).  All ranks then run the NUTS step on bitwise-identical inp
 chain states never diverge and no other exchange is needed.
 
 The log density must be a pure sum over rows: the logistic family (flat priors, no Jacobian).
+The Poisson family's is one too, but full-data mode stays logistic-only: it is refused by name.
 """
 from __future__ import annotations
 
