@@ -29,6 +29,11 @@
  *   stk_consensus_solve         stark/stark.py:66-70  inv(sum W) . sum W theta
  *   stk_consensus               stark/stark.py:66-70  reduce + solve over all shards
  *   stk_consensus_blocked       the same with block-diagonal weights (lp__ in its own block)
+ *   stk_log_density_hessian /   the analytic Hessian of a regression shard's log density at one point, and the
+ *   stk_hessian_launch_info /   combine with the caller's weights -- e.g. every shard's Laplace precision
+ *   stk_consensus_weighted      W_s = -H_s, the exact consensus weights.  No reference counterpart: on the
+ *                               product path they supersede tools/laplace.py's central difference of the
+ *                               gradient (2 D gradient points per Hessian)
  *
  * Conventions
  *   - Return 0 on success, a negative STK_E_* code on failure; stk_last_error() gives a
@@ -279,6 +284,24 @@ STK_API int stk_chain_batches(int32_t C, int32_t d, int32_t* sizes, int32_t cap)
  * the stk_log_density_grad* hooks refuse with the same code before they launch anything. */
 STK_API int stk_sweep_launch_info(int64_t n_rows, int32_t d, int32_t C, int64_t out[6]);
 
+/* ---- analytic Hessian (regression families, 1 <= d <= 128): one weighted Gram matrix
+ * X~^T diag(w) X~, X~ = [1 | X], accumulated on the fp64 MFMA in a single pass over the shard ----
+ * Hessian of the log density of shard `shard` at q[D] -> hess[D][D] (row-major, symmetric to the bit),
+ * with respect to the unconstrained parameters in the gradient's layout ((alpha, beta) for logistic and
+ * poisson, (alpha, beta, u = log sigma) for linear); the normal(0, s) priors of stk_model_set_prior add
+ * -1/s^2 on the diagonal entries they cover.
+ * shard == -1: every shard at its own point, q [nshards][D], hess [nshards][D][D], lp [nshards],
+ * grad [nshards][D], the Hessians in one grouped launch.  lp / grad may be NULL; when given they are what
+ * stk_log_density_grad returns at q, bit for bit (they ARE its C = 1 sweep, one per shard).  The result is bitwise independent of how many shards
+ * share the call and of the device.  A NaN eta or an overflowing poisson mu gives non-finite entries and
+ * still STK_OK: the caller decides.  Regressions with d <= 128; STK_E_ARG (the message names the family
+ * or the limit) for 8 schools and for d > 128. */
+STK_API int stk_log_density_hessian(stk_model* m, int shard, const double* q, double* lp, double* grad, double* hess);
+/* host only, like stk_sweep_launch_info: out[0] rows per tile, out[1] chunks per shard, out[2] waves per
+ * block, out[3] dynamic LDS bytes, out[4] bytes of chunk-partial workspace per shard.  The three families
+ * share one geometry (d + 2 live columns: x, the ones column, linear's residual column). */
+STK_API int stk_hessian_launch_info(int64_t n_rows, int32_t d, int64_t out[5]);
+
 /* ---- sampling: stark/stark.py:43-56 for every shard of the model ---- */
 STK_API int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out);
 /* Advance every chain until it has completed `target_iter` transitions (warmup counted),
@@ -387,6 +410,13 @@ STK_API int stk_consensus(stk_ctx* ctx, const double* draws, int32_t nshards, in
  * taken as 0, so each block is combined from its own covariance. */
 STK_API int stk_consensus_blocked(stk_ctx* ctx, const double* draws, int32_t nshards, int32_t P, int32_t S,
                                   const int32_t* row_block, double* out, int32_t* shard_used);
+/* (sum_s W_s)^-1 sum_s W_s theta_s with the CALLER's weights: weights [nshards][P][P], symmetric positive
+ * definite (host or device memory); draws / out / shard_used as stk_consensus, any S >= 1.  Shards with
+ * NaN draws are left out (weights too).  A non-finite weight of a used shard: STK_E_ARG naming the shard.
+ * A singular sum: STK_E_LINALG.  The NaN mask, sum W, sum W theta and the final SPD solve are
+ * stk_consensus's stages; the covariance and the per-shard inverse are skipped. */
+STK_API int stk_consensus_weighted(stk_ctx* ctx, const double* draws, const double* weights, int32_t nshards,
+                                   int32_t P, int32_t S, double* out, int32_t* shard_used);
 
 #ifdef __cplusplus
 }

@@ -116,6 +116,9 @@ SIGNATURES = [
     ("stk_consensus_solve", ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
     ("stk_consensus", ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     ("stk_consensus_blocked", ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    ("stk_log_density_hessian", ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    ("stk_hessian_launch_info", ctypes.c_int, [_i64, _i32, _vp]),
+    ("stk_consensus_weighted", ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
 ]
 
 # int (*stk_allreduce_fn)(void* user, double* block, int64_t count, void* stream)

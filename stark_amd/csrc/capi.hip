@@ -648,6 +648,55 @@ int stk_sweep_launch_info(int64_t n_rows, int32_t d, int32_t C, int64_t out[6]) 
   return STK_OK;
 }
 
+// ---------------------------------------------------------------- analytic Hessian (hessian.hip)
+// The Hessian sweep's launch shape over a shard of n_rows x d (host only: no device).
+// out: rows per tile, chunks per shard, waves per block, LDS bytes, chunk-partial workspace bytes per shard.
+int stk_hessian_launch_info(int64_t n_rows, int32_t d, int64_t out[5]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_hessian_launch_info: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(stk_hessian_supported(d), "the Hessian sweep covers 1 <= d <= 128 covariates, not d = %d", d);
+  const int64_t v[5] = {stk_hessian_rows_per_tile(), stk_hessian_chunks(n_rows), stk_hessian_waves(),
+                        (int64_t)stk_hessian_lds_bytes(d), (int64_t)stk_hessian_ws_bytes(n_rows, d)};
+  memcpy(out, v, sizeof(v));
+  return STK_OK;
+}
+
+// One point per shard.  lp / grad come from stk_log_density_grad itself (one C = 1 sweep per shard), so
+// they are its bits; the Hessians of all the call's shards are one sweep launch and one reduce launch.
+int stk_log_density_hessian(stk_model* m, int shard, const double* q, double* lp, double* grad, double* hess) {
+  ARG_CHECK(m && q && hess && shard >= -1 && shard < m->nshards, "stk_log_density_hessian: bad arguments");
+  ARG_CHECK(is_regression(m->family), "stk_log_density_hessian: no Hessian sweep for the %s family (regressions only)",
+            family_name(m->family));
+  ARG_CHECK(stk_hessian_supported(m->d), "stk_log_density_hessian: the Hessian sweep covers 1 <= d <= 128 covariates, not d = %d",
+            m->d);
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int D = m->Dmax, shard0 = shard < 0 ? 0 : shard, nsh = shard < 0 ? m->nshards : 1;
+  if (lp || grad) {
+    for (int s = 0; s < nsh; ++s) {
+      double lp1 = 0.0;   // stk_log_density_grad needs a place for lp
+      RC(stk_log_density_grad(m, shard0 + s, q + (size_t)s * D, 1, lp ? lp + s : &lp1,
+                              grad ? grad + (size_t)s * D : nullptr));
+    }
+  }
+  int Gs = 1;
+  size_t ws = 0;
+  for (int s = shard0; s < shard0 + nsh; ++s) {
+    Gs = std::max(Gs, stk_hessian_chunks(m->sh[s].n));
+    ws = std::max(ws, stk_hessian_ws_bytes(m->sh[s].n, m->d));
+  }
+  const size_t qn = (size_t)nsh * D, hn = qn * D;
+  RC(ctx->scratch[7].ensure(ws * nsh));
+  RC(ctx->scratch[11].ensure(sizeof(double) * (qn + hn)));
+  double* qb = ctx->scratch[11].as<double>();
+  double* hb = qb + qn;
+  STK_HIP_CHECK(hipMemcpyAsync(qb, q, sizeof(double) * qn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(stk_launch_hessian(m->family, m->sh_dev.as<ShardDev>(), shard0, nsh, m->d, D, Gs, qb,
+                                   ctx->scratch[7].as<double>(), hb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(hess, hb, sizeof(double) * hn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
 
 // The chain batches a regression shard's C chains run as at d covariates (host only: no device).
 int stk_chain_batches(int32_t C, int32_t d, int32_t* sizes, int32_t cap) {
@@ -1581,6 +1630,48 @@ int stk_consensus_blocked(stk_ctx* ctx, const double* draws, int32_t nshards, in
                           const int32_t* row_block, double* out, int32_t* shard_used) {
   ARG_CHECK(out && row_block, "stk_consensus_blocked: out / row_block is NULL");
   return consensus_run(ctx, draws, nshards, P, S, row_block, nullptr, nullptr, out, shard_used);
+}
+
+// The combine with the caller's weights: the NaN mask, sum W, sum W theta and the final solve of
+// stk_consensus; no covariance, no per-shard inverse (so S may be any count >= 1).
+int stk_consensus_weighted(stk_ctx* ctx, const double* draws, const double* weights, int32_t nshards, int32_t P,
+                           int32_t S, double* out, int32_t* shard_used) {
+  ARG_CHECK(ctx && draws && weights && out && nshards > 0 && P > 0 && S > 0, "stk_consensus_weighted: bad arguments");
+  ARG_CHECK(P <= 4096, "P = %d too large", P);
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t per = (size_t)P * S, pp = (size_t)P * P;
+  CombineBufs b;
+  RC(combine_bufs(ctx, nshards, P, S, &b));
+  const bool dev_in = is_device_ptr(draws, ctx->device), dev_out = is_device_ptr(out, ctx->device);
+  const double* X = dev_in ? draws : b.X;
+  if (!dev_in) STK_HIP_CHECK(hipMemcpyAsync(b.X, draws, sizeof(double) * per * nshards, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipMemcpyAsync(b.W, weights, sizeof(double) * pp * nshards, hipMemcpyDefault, st));   // masked in place
+  STK_HIP_CHECK(stk_launch_consensus_weighted(X, nshards, P, S, b.mean, b.rowbad, b.used, b.status, b.W, b.sw, b.swt, st));
+  STK_HIP_CHECK(stk_launch_consensus_solve(b.sw, b.swt, P, S, b.inv, b.work, b.status + nshards, dev_out ? out : b.out,
+                                           st, false));
+  std::vector<int32_t> h(2 * nshards + 1, 0);
+  STK_HIP_CHECK(hipMemcpyAsync(h.data(), b.used, sizeof(int32_t) * (2 * nshards + 1), hipMemcpyDeviceToHost, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  int nused = 0;
+  for (int s = 0; s < nshards; ++s) {
+    ARG_CHECK(!(h[s] && h[nshards + s]), "shard %d: non-finite weight", s);
+    nused += h[s];
+    if (shard_used) shard_used[s] = h[s];
+  }
+  if (nused == 0) {
+    stk_set_error("every shard holds NaN draws");
+    return STK_E_NAN;
+  }
+  if (h[2 * nshards]) {
+    stk_set_error("singular sum of weights (LinAlgError)");
+    return STK_E_LINALG;
+  }
+  if (!dev_out) {
+    STK_HIP_CHECK(hipMemcpyAsync(out, b.out, sizeof(double) * per, hipMemcpyDefault, st));
+    STK_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  return STK_OK;
 }
 
 }  // extern "C"

@@ -549,6 +549,22 @@ __global__ void k_sum_w(const double* src, int nshards, size_t n, double* dst) {
   }
 }
 
+// The caller's weights (stk_consensus_weighted), one block per shard: a shard left out for NaN
+// draws gets W = 0 (as k_spd_inverse leaves it) and no status; status[s] = 1 when a used shard's
+// weights hold a NaN or an infinity.
+__global__ __launch_bounds__(256) void k_weight_mask(double* W, size_t n, const int32_t* used, int32_t* status) {
+  const int s = blockIdx.x;
+  double* w = W + (size_t)s * n;
+  int bad = 0;
+  if (!used[s]) {
+    for (size_t i = threadIdx.x; i < n; i += 256) w[i] = 0.0;
+  } else {
+    for (size_t i = threadIdx.x; i < n; i += 256) bad |= isfinite(w[i]) ? 0 : 1;
+  }
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) status[s] = bad;
+}
+
 template <class LD, int NB, int CH, bool SYM>
 static hipError_t mgemm(const LD& L, int M, int N, int K, int batch, hipStream_t st) {
   const int tiles_m = (M + 15) / 16, tiles_n = SYM ? tiles_m : (N + 16 * NB - 1) / (16 * NB);
@@ -598,6 +614,22 @@ hipError_t stk_launch_consensus_products(const double* X, int nshards, int P, in
   const size_t pp = (size_t)P * P;
   hipLaunchKernelGGL(k_sum_w, dim3((unsigned)std::min<size_t>((pp + 255) / 256, 1024)), dim3(256), 0, st, W, nshards,
                      pp, sum_w);
+  return mgemm<WThetaLd, 2, 2, false>(WThetaLd{W, X, used, sum_wtheta, P, S}, P, S, nshards * P, 1, st);
+}
+
+// The same with the caller's W [nshards][P][P] in place of inv(cov_s): the NaN mask, the sum and the
+// W theta product are the stages above; the covariance and the per-shard inverse are skipped.
+hipError_t stk_launch_consensus_weighted(const double* X, int nshards, int P, int S, double* mean, int32_t* rowbad,
+                                         int32_t* used, int32_t* status, double* W, double* sum_w, double* sum_wtheta,
+                                         hipStream_t st) {
+  hipLaunchKernelGGL(k_row_stats, dim3(nshards * P), dim3(256), 0, st, X, S, mean, rowbad);
+  hipLaunchKernelGGL(k_shard_used, dim3((nshards + 63) / 64), dim3(64), 0, st, rowbad, P, nshards, used);
+  const size_t pp = (size_t)P * P;
+  hipLaunchKernelGGL(k_weight_mask, dim3(nshards), dim3(256), 0, st, W, pp, used, status);
+  hipLaunchKernelGGL(k_sum_w, dim3((unsigned)std::min<size_t>((pp + 255) / 256, 1024)), dim3(256), 0, st, W, nshards,
+                     pp, sum_w);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
   return mgemm<WThetaLd, 2, 2, false>(WThetaLd{W, X, used, sum_wtheta, P, S}, P, S, nshards * P, 1, st);
 }
 

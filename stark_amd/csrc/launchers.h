@@ -82,6 +82,16 @@ size_t stk_sweep16w_lds_bytes(int family, int d);
 hipError_t stk_launch_sweep16w(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
 hipError_t stk_launch_sweep16w_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16w_pois.hip
 
+// ---- hessian.hip (regressions, d <= 128): the analytic Hessian sweep's geometry and launch
+bool stk_hessian_supported(int d);
+int stk_hessian_chunks(int64_t n);
+int stk_hessian_rows_per_tile();
+int stk_hessian_waves();
+size_t stk_hessian_lds_bytes(int d);
+size_t stk_hessian_ws_bytes(int64_t n, int d);   // chunk-partial workspace of one shard
+hipError_t stk_launch_hessian(int family, const stk::ShardDev* shards, int shard0, int nsh, int d, int D, int Gs,
+                              const double* q, double* partial, double* hess, hipStream_t st);
+
 // ---- nuts.hip (and its nuts_fused4.hip / nuts_dense.hip translation units)
 int stk_nch_for(int Dmax);
 size_t stk_fused_lds_bytes(const stk::NutsArgs& A, int nch);
@@ -109,6 +119,10 @@ size_t stk_general_inverse_work_bytes(int P);
 hipError_t stk_launch_consensus_solve(const double* sum_w, const double* sum_wtheta, int P, int S, double* inv_buf,
                                       double* work, int32_t* status, double* out, hipStream_t st, bool general);
 size_t stk_spd_inverse_work_bytes(int P, int batch);
+// the caller's weights W [nshards][P][P] (device, modified: NaN-draw shards are zeroed) in place of inv(cov)
+hipError_t stk_launch_consensus_weighted(const double* X, int nshards, int P, int S, double* mean, int32_t* rowbad,
+                                         int32_t* used, int32_t* status, double* W, double* sum_w, double* sum_wtheta,
+                                         hipStream_t st);
 
 // ---- fingerprint.hip
 uint64_t stk_fp_fmix(uint64_t a);

@@ -421,6 +421,25 @@ class Model:
         check(_lib.load().stk_log_density_grad_chains(self._h, q.ctypes.data, C, lp.ctypes.data, g.ctypes.data))
         return lp, g
 
+    def hessian(self, shard=None, q=None):
+        """lp, grad lp and the Hessian of the log density at ONE point per shard, in the unconstrained
+        parameters of ``log_density_grad`` (stk_log_density_hessian: the analytic Hessian sweep;
+        regression families with d <= 128).  shard: an index (q of D values; returns lp, grad [D],
+        hess [D, D]) or None for every shard at its own point in one grouped launch (q [nshards, D];
+        returns lp [nshards], grad [nshards, D], hess [nshards, D, D]).  hess is symmetric to the bit;
+        a NaN eta or an overflowing Poisson mean gives non-finite entries, which the caller judges."""
+        every = shard is None
+        D = self.D[0 if every else shard]
+        q = np.ascontiguousarray(q, np.float64)
+        want = (self.nshards, D) if every else (D,)
+        if q.shape != want:
+            raise ValueError(f"q must have shape {want}, got {q.shape}")
+        ns = self.nshards if every else 1
+        lp, g, H = np.empty(ns), np.empty((ns, D)), np.empty((ns, D, D))
+        check(_lib.load().stk_log_density_hessian(self._h, -1 if every else int(shard), q.ctypes.data, lp.ctypes.data,
+                                                  g.ctypes.data, H.ctypes.data))
+        return (lp, g, H) if every else (lp[0], g[0], H[0])
+
     def set_prior(self, alpha=None, beta=None):
         """normal(0, s) priors on alpha and beta (regressions); None or 0: flat."""
         check(_lib.load().stk_model_set_prior(self._h, float(alpha or 0.0), float(beta or 0.0)))
@@ -653,9 +672,143 @@ def _device_stack(draws):
     return t.to(torch.float64).contiguous()
 
 
-def consensus(draws, ctx: Context | None = None, separate_lp: bool = False):
+def _block_weights(weights, nshards, P, S, dev, X):
+    """[nshards, P, P] block-diagonal weights: the caller's P' x P' precision of the rows other than
+    lp__ and, for lp__ (the last row), the inverse of its sample variance in that shard (the 1 x 1
+    block separate_lp=True gives it; NaN draws give a NaN here, and their shard is left out)."""
+    W = [np.asarray(w, np.float64) for w in weights]
+    if len(W) != nshards:
+        raise ValueError(f"weights holds {len(W)} matrices, the draws {nshards} shards")
+    for s, w in enumerate(W):
+        if w.shape != (P - 1, P - 1):
+            raise ValueError(f"weights[{s}] has shape {w.shape}; the {P} draw rows (lp__ last) need ({P - 1}, {P - 1})")
+    if S < 2:
+        raise ValueError("lp__'s own weight is its sample variance: at least 2 draws per shard")
+    if dev is not None:
+        lp_var = dev[:, -1, :].var(dim=1, unbiased=True).cpu().numpy()
+    else:
+        lp_var = X[:, -1, :].var(axis=1, ddof=1)
+    out = np.zeros((nshards, P, P))
+    for s, w in enumerate(W):
+        out[s, :P - 1, :P - 1] = w
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[s, -1, -1] = 1.0 / lp_var[s]
+    return out
+
+
+def hessian_launch(n_rows: int, n_cols: int) -> dict:
+    """The launch shape of the analytic Hessian sweep over a shard of ``n_rows`` x ``n_cols``
+    (stk_hessian_launch_info): rows per tile ``T``, chunks per shard ``G``, ``waves`` per block,
+    ``lds_bytes`` and ``ws_bytes_per_shard``.  Raises STK_E_ARG past 128 covariates.  Host only."""
+    out = np.zeros(5, np.int64)
+    check(_lib.load().stk_hessian_launch_info(int(n_rows), int(n_cols), out.ctypes.data))
+    return dict(zip(("T", "G", "waves", "lds_bytes", "ws_bytes_per_shard"), (int(v) for v in out)))
+
+
+def laplace(model, shards=None, q0=None, reduce=None, max_iter=50, tol=1e-8):
+    """Mode and covariance (-H)^-1 of the posterior formed by the SUM of ``shards`` (None: every
+    shard of the model), by a safeguarded Newton iteration on the analytic Hessian
+    (``Model.hessian``).  Returns (mode, cov, info), in the unconstrained parameters.
+
+    The meaning and the ``reduce=`` contract are those of ``tools.laplace.laplace``: with shards on
+    several ranks every rank calls this with its own shards, the same q0 and a ``reduce`` that sums
+    a float64 array over the ranks in place; all ranks then take identical steps.
+
+    Every iteration takes one Hessian of every shard and steps by a Cholesky factor of -H.  Where
+    -H is not positive definite (the linear family away from its mode, where the theta-u cross
+    terms dominate) the cross terms of the last parameter are dropped for that step: the
+    block-diagonal matrix is positive definite for full-rank X.  The step is halved until lp is
+    finite and does not decrease (within 1e-11 |lp|, the rounding of a sum over the rows).  It stops
+    when the largest step is below ``tol`` posterior sds.  info: ``steps_in_sd``, ``halvings`` and
+    ``kinds`` ("newton" | "block") per iteration, ``hessians`` (evaluations) and ``lp``.
+    Raises ValueError for a non-finite Hessian (the message names the shard) or without convergence."""
+    every = shards is None
+    ids = list(range(model.nshards)) if every else [int(s) for s in shards]
+    if q0 is None:
+        q0 = np.zeros(model.D[ids[0]])
+    q = np.array(q0, np.float64, copy=True).reshape(-1)
+    D = q.size
+
+    def total(parts):
+        v = np.concatenate([np.asarray(p, np.float64).reshape(-1) for p in parts])
+        if reduce is not None:
+            reduce(v)
+        return v
+
+    def density(p):
+        lp = 0.0
+        for s in ids:
+            l_, _ = model.log_density_grad(s, p[None])
+            lp += float(np.asarray(l_).reshape(-1)[0])
+        return float(total([[lp]])[0])
+
+    def curvature(p):
+        if every and model.nshards > 1:
+            lps, gs, Hs = model.hessian(None, np.tile(p, (model.nshards, 1)))
+        else:
+            lps, gs, Hs = zip(*(model.hessian(s, p) for s in ids))
+        for s, H in zip(ids, Hs):
+            if not np.all(np.isfinite(H)):
+                raise ValueError(f"shard {s}: the Hessian at the current point is not finite")
+        lp, g, H = 0.0, np.zeros(D), np.zeros((D, D))
+        for l_, g_, H_ in zip(lps, gs, Hs):      # shard order
+            lp, g, H = lp + float(l_), g + g_, H + H_
+        v = total([[lp], g, H])
+        return float(v[0]), v[1:1 + D].copy(), v[1 + D:].reshape(D, D).copy()
+
+    info = {"steps_in_sd": [], "halvings": [], "kinds": [], "hessians": 0}
+    where = f"shards {ids}" if len(ids) != 1 else f"shard {ids[0]}"
+    for _ in range(int(max_iter)):
+        lp, g, H = curvature(q)
+        info["hessians"] += 1
+        if not (np.isfinite(lp) and np.all(np.isfinite(g)) and np.all(np.isfinite(H))):
+            raise ValueError(f"{where}: the log density, its gradient or its Hessian is not finite at the current point")
+        A, kind = -H, "newton"
+        try:
+            np.linalg.cholesky(A)
+        except np.linalg.LinAlgError:
+            A, kind = A.copy(), "block"
+            A[-1, :-1] = 0.0
+            A[:-1, -1] = 0.0
+            try:
+                np.linalg.cholesky(A)
+            except np.linalg.LinAlgError:
+                raise ValueError(f"{where}: -H is not positive definite, with or without its cross terms "
+                                 "(rank-deficient rows?)") from None
+        cov = np.linalg.inv(A)
+        cov = 0.5 * (cov + cov.T)
+        dq = cov @ g
+        sd = np.sqrt(np.diag(cov))
+        a, halvings = 1.0, 0
+        while True:
+            trial = q + a * dq
+            lp_new = density(trial)
+            if np.isfinite(lp_new) and lp_new >= lp - 1e-11 * max(1.0, abs(lp)):
+                break
+            a *= 0.5
+            halvings += 1
+            if halvings > 60:
+                raise ValueError(f"{where}: no step along the Newton direction keeps the log density from decreasing")
+        q = trial
+        info["steps_in_sd"].append(float(np.abs(a * dq / sd).max()))
+        info["halvings"].append(halvings)
+        info["kinds"].append(kind)
+        info["lp"] = lp_new
+        if info["steps_in_sd"][-1] < tol:
+            if kind != "newton":
+                continue                                   # cov must be the full (-H)^-1
+            return q, cov, info
+    raise ValueError(f"{where}: no convergence in {max_iter} iterations (steps in sd: {info['steps_in_sd'][-3:]})")
+
+
+def consensus(draws, ctx: Context | None = None, separate_lp: bool = False, weights=None):
     """(sum_s W_s)^-1 sum_s W_s theta_s, W_s = inv(cov(theta_s)): stark/stark.py:66-70 over
     the reducer stark/stark.py:7-21.  Returns (P x S, shard_used).
+
+    weights: None (the sampled weights above), or one P' x P' precision matrix per shard for the
+    rows OTHER than lp__ (P' = P - 1), e.g. every shard's Laplace precision from ``laplace``: the
+    combine then uses them as they are (stk_consensus_weighted), and lp__ (the last row) gets its
+    own 1 x 1 block weighted by its sample variance, as separate_lp=True gives it.
 
     draws: a list of P x S host arrays, or device-resident draws -- a [nshards, P, S] cuda
     tensor (e.g. dist.all_gather_partitions(..., as_tensor=True)) or a list of P x S cuda
@@ -668,8 +821,17 @@ def consensus(draws, ctx: Context | None = None, separate_lp: bool = False):
     sample covariance, the noise in the lp__-parameter cross terms moves the parameter rows of
     the joint combine by a multiple of that offset.  Block weights are exact for a Gaussian
     posterior, where lp__ is uncorrelated with the parameters."""
-    ctx = ctx or default_context()
     dev = _device_stack(draws)
+    if dev is None and not isinstance(draws, (list, tuple)) and hasattr(draws, "numpy"):    # a host torch tensor
+        draws = list(draws.numpy())
+    W = None
+    if weights is not None:      # checked and assembled before a context (a device) is needed
+        if dev is not None:
+            W = _block_weights(weights, *(int(v) for v in dev.shape), dev, None)
+        else:
+            Xh, (Ph, Sh) = _stack(draws)
+            W = _block_weights(weights, len(draws), Ph, Sh, None, Xh)
+    ctx = ctx or default_context()
     if dev is not None:
         import torch
         ns, P, S = (int(v) for v in dev.shape)
@@ -679,6 +841,10 @@ def consensus(draws, ctx: Context | None = None, separate_lp: bool = False):
         out_t = torch.empty((P, S), dtype=torch.float64, device=dev.device)
         used = np.empty(ns, np.int32)
         torch.cuda.current_stream(dev.device).synchronize()    # the library runs on its own stream
+        if W is not None:
+            check(_lib.load().stk_consensus_weighted(ctx._h, _ptr(dev), W.ctypes.data, ns, P, S, _ptr(out_t),
+                                                     used.ctypes.data))
+            return out_t, used.astype(bool)
         if separate_lp:
             blk = np.zeros(P, np.int32)
             blk[-1] = 1
@@ -687,11 +853,13 @@ def consensus(draws, ctx: Context | None = None, separate_lp: bool = False):
         else:
             check(_lib.load().stk_consensus(ctx._h, _ptr(dev), ns, P, S, _ptr(out_t), used.ctypes.data))
         return out_t, used.astype(bool)
-    if not isinstance(draws, (list, tuple)) and hasattr(draws, "numpy"):    # a host torch tensor
-        draws = list(draws.numpy())
     X, (P, S) = _stack(draws)
     out = np.empty((P, S))
     used = np.empty(len(draws), np.int32)
+    if W is not None:
+        check(_lib.load().stk_consensus_weighted(ctx._h, X.ctypes.data, W.ctypes.data, len(draws), P, S,
+                                                 out.ctypes.data, used.ctypes.data))
+        return out, used.astype(bool)
     if separate_lp:
         # one call with block-diagonal weights: parameters in block 0, lp__ (last row) in block 1;
         # the NaN mask is per shard over all rows, so both blocks combine the same shard set
@@ -701,6 +869,39 @@ def consensus(draws, ctx: Context | None = None, separate_lp: bool = False):
                                                 out.ctypes.data, used.ctypes.data))
         return out, used.astype(bool)
     check(_lib.load().stk_consensus(ctx._h, X.ctypes.data, len(draws), P, S, out.ctypes.data, used.ctypes.data))
+    return out, used.astype(bool)
+
+
+def consensus_weighted(draws, weights, ctx: Context | None = None):
+    """(sum_s W_s)^-1 sum_s W_s theta_s with the caller's P x P weights, one per shard, over ALL the
+    draw rows (stk_consensus_weighted).  draws as ``consensus`` takes them (host arrays, or device
+    tensors combined where they lie); returns (P x S, shard_used).  Shards with NaN draws are left
+    out; a non-finite weight of a used shard raises StarkHipError (STK_E_ARG) naming the shard."""
+    dev = _device_stack(draws)
+    if dev is None and not isinstance(draws, (list, tuple)) and hasattr(draws, "numpy"):
+        draws = list(draws.numpy())
+    if dev is not None:
+        ns, P, S = (int(v) for v in dev.shape)
+    else:
+        X, (P, S) = _stack(draws)
+        ns = len(draws)
+    W = np.ascontiguousarray(np.stack([np.asarray(w, np.float64) for w in weights]))
+    if W.shape != (ns, P, P):
+        raise ValueError(f"weights must be {ns} matrices of ({P}, {P}), got shape {W.shape}")
+    ctx = ctx or default_context()
+    used = np.empty(ns, np.int32)
+    if dev is not None:
+        import torch
+        if dev.device.index != ctx.device:
+            raise ValueError(f"draws on {dev.device} but the context is on cuda:{ctx.device}")
+        out_t = torch.empty((P, S), dtype=torch.float64, device=dev.device)
+        torch.cuda.current_stream(dev.device).synchronize()
+        check(_lib.load().stk_consensus_weighted(ctx._h, _ptr(dev), W.ctypes.data, ns, P, S, _ptr(out_t),
+                                                 used.ctypes.data))
+        return out_t, used.astype(bool)
+    out = np.empty((P, S))
+    check(_lib.load().stk_consensus_weighted(ctx._h, X.ctypes.data, W.ctypes.data, ns, P, S, out.ctypes.data,
+                                             used.ctypes.data))
     return out, used.astype(bool)
 
 

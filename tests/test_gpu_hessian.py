@@ -1,0 +1,262 @@
+"""The analytic Hessian sweep (stk_log_density_hessian, hessian.hip) against a numpy restatement of
+the formulas in np.longdouble, for the three regression families.
+
+With eta = alpha + x . beta, X~ = [1 | X], theta = (alpha, beta) and r = y - eta:
+    logistic  H = -X~^T diag(w) X~,  w = s(eta)(1 - s(eta)) = t / (1 + t)^2, t = exp(-|eta|)
+    poisson   H = -X~^T diag(mu) X~, mu = exp(eta)
+    linear    H_tt = -e^-2u X~^T X~,  H_tu = -2 e^-2u X~^T r,  H_uu = -2 e^-2u sum r^2   (u = log sigma)
+and the normal(0, s) priors add -1/s^2 on the diagonal entries they cover.  The bar is the project's
+density bar, 1e-10 of max |H| per entry (the float64 restatement is within 1e-15 of the longdouble
+one at these shapes).  Every case prints its largest error as a MAXERR line.
+"""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+BAR = 1e-10
+DBL_MAX = np.finfo(np.float64).max
+FAMILIES = ("logistic", "poisson", "linear")
+# both sides of every 16-column padding edge of d + 1 (the issue's set) and of d + 2 live columns (the
+# kernel's: x, the ones column, linear's residual column)
+DS = (1, 3, 4, 14, 15, 16, 17, 100, 111, 112, 126, 127, 128)
+NS = (1, 15, 16, 17, 63, 64, 65)
+
+
+def ref_hessian(family, X, y, q, prior=(None, None)):
+    L = np.longdouble
+    n, d = X.shape
+    Xt = np.concatenate([np.ones((n, 1)), X], axis=1).astype(L)
+    ql = np.asarray(q).astype(L)
+    D = q.size
+    H = np.zeros((D, D), L)
+    with np.errstate(over="ignore", invalid="ignore"):
+        eta = Xt @ ql[:d + 1]
+        if family == "linear":
+            s = np.exp(-2 * ql[-1])
+            r = np.asarray(y).astype(L) - eta
+            H[:d + 1, :d + 1] = -s * (Xt.T @ Xt)
+            H[:d + 1, -1] = H[-1, :d + 1] = -2 * s * (Xt.T @ r)
+            H[-1, -1] = -2 * s * (r @ r)
+        else:
+            if family == "logistic":
+                t = np.exp(-np.abs(eta))
+                w = t / ((1 + t) * (1 + t))
+            else:
+                w = np.exp(eta)
+                w[w > DBL_MAX] = np.inf
+            H[:, :] = -((Xt.T * w) @ Xt)
+    pa, pb = (0.0 if s_ in (0.0, None) else 1 / (L(s_) * L(s_)) for s_ in prior)
+    H[0, 0] -= pa
+    for i in range(1, d + 1):
+        H[i, i] -= pb
+    return H
+
+
+def make_data(family, n, d, seed=None):
+    """X ~ U(-1.7, 1.7) with one all-zero row (n >= 3); y from the family at a true (alpha, beta[, sigma])."""
+    rng = np.random.default_rng(1000 * n + d if seed is None else seed)
+    X = rng.uniform(-1.7, 1.7, (n, d))
+    if n >= 3:
+        X[n // 2] = 0.0
+    beta = rng.normal(0, 1 / np.sqrt(d), d)
+    eta = 0.3 + X @ beta
+    if family == "logistic":
+        y = (rng.uniform(size=n) < 1 / (1 + np.exp(-eta))).astype(np.int32)
+        truth = np.concatenate([[0.3], beta])
+    elif family == "poisson":
+        y = rng.poisson(np.exp(eta)).astype(np.int32)
+        truth = np.concatenate([[0.3], beta])
+    else:
+        y = eta + 0.7 * rng.normal(size=n)
+        truth = np.concatenate([[0.3], beta, [np.log(0.7)]])
+    return rng, X, y, truth
+
+
+def multi_chunk_n(d):
+    """The smallest n of at least 3 chunks whose last 16-row tile is ragged, from the launch info."""
+    from stark_amd import engine
+    n = 17
+    while engine.hessian_launch(n, d)["G"] < 3 or n % 16 == 0:
+        n += 101
+    return n
+
+
+def shapes():
+    out = []
+    for d in DS:
+        out.append((37 + d % 7, d))       # ragged, one chunk
+        out.append((None, d))             # >= 3 chunks, ragged last tile
+    out += [(n, 100) for n in NS]
+    return out
+
+
+def rel_err(H, R):
+    R64 = R.astype(np.float64)
+    return float(np.abs(H - R64).max() / np.abs(R64).max())
+
+
+@pytest.mark.parametrize("n,d", shapes())
+@pytest.mark.parametrize("family", FAMILIES)
+def test_hessian_matches_the_restatement(ctx, family, n, d):
+    """Two shards (the first a third of the rows; the second is evaluated), q ~ N(0, 0.3), flat priors
+    and then normal(0, 2) / normal(0, 0.5): every entry within 1e-10 of max |H|, H == H.T to the bit,
+    lp and grad the bits of stk_log_density_grad."""
+    from stark_amd import engine
+    if n is None:
+        n = multi_chunk_n(d)
+        assert engine.hessian_launch(n, d)["G"] >= 3 and n % engine.hessian_launch(n, d)["T"] != 0
+    rng, X, y, _ = make_data(family, n, d)
+    k = max(1, n // 3)
+    m = engine.Model(ctx, family, [{"x": X[:k], "y": y[:k]}, {"x": X, "y": y}])
+    try:
+        q = rng.normal(0, 0.3, m.D[1])
+        worst = 0.0
+        for prior in ((None, None), (2.0, 0.5)):
+            if prior[0]:
+                m.set_prior(alpha=prior[0], beta=prior[1])
+            lp, g, H = m.hessian(1, q)
+            R = ref_hessian(family, X, y, q, prior)
+            assert np.isfinite(H).all()
+            err = rel_err(H, R)
+            worst = max(worst, err)
+            assert err < BAR, (family, n, d, prior, err)
+            assert np.array_equal(H, H.T)
+            lp0, g0 = m.log_density_grad(1, q[None])
+            assert lp == lp0[0] and np.array_equal(g, g0[0])
+        print(f"MAXERR hessian[{family}-{n}-{d}] {worst:.3e}")
+    finally:
+        m.close()
+
+
+def test_linear_border_from_the_oracle_gradient(ctx, orc):
+    """Linear: H_tu is -2 times the data part of the gradient and H_uu = -2 (d lp / du + N - 1), with the
+    gradient taken from oracle.Model.lpgrad (flat priors)."""
+    from stark_amd import engine
+    n, d = 333, 17
+    rng, X, y, _ = make_data("linear", n, d)
+    m = engine.Model(ctx, "linear", [{"x": X, "y": y}])
+    try:
+        q = rng.normal(0, 0.3, d + 2)
+        _, _, H = m.hessian(0, q)
+        _, og = orc.Model(orc.FAM_LINREG, X=X, y=y).lpgrad(q)
+        scale = np.abs(H).max()
+        assert np.abs(H[:-1, -1] + 2 * og[:-1]).max() < BAR * scale
+        assert abs(H[-1, -1] + 2 * (og[-1] + n - 1)) < BAR * scale
+    finally:
+        m.close()
+
+
+def test_logistic_extreme_eta_underflows_to_zero_weight(ctx):
+    """Rows with |eta| ~ 40 and ~ 750: the weight underflows, the entries equal the reference, no NaN."""
+    from stark_amd import engine
+    n, d = 70, 100
+    rng, X, y, _ = make_data("logistic", n, d)
+    q = rng.normal(0, 0.3, d + 1)
+    b = q[1:]
+    for row, eta in ((1, 40.0), (2, -40.0), (3, 750.0), (4, -750.0), (20, 745.0)):
+        X[row] = (eta - q[0]) * b / (b @ b)
+    m = engine.Model(ctx, "logistic", [{"x": X, "y": y}])
+    try:
+        _, _, H = m.hessian(0, q)
+        assert np.isfinite(H).all()
+        err = rel_err(H, ref_hessian("logistic", X, y, q))
+        print(f"MAXERR hessian[logistic-extreme-eta] {err:.3e}")
+        assert err < BAR
+    finally:
+        m.close()
+
+
+def test_non_finite_points_give_non_finite_entries(ctx):
+    """A Poisson mean that overflows, and a NaN coordinate: the call succeeds (STK_OK) and every entry
+    that depends on eta is non-finite -- never a finite wrong number."""
+    from stark_amd import engine
+    n, d = 40, 5
+    for family in FAMILIES:
+        rng, X, y, _ = make_data(family, n, d)
+        m = engine.Model(ctx, family, [{"x": X, "y": y}])
+        try:
+            q = rng.normal(0, 0.3, m.D[0])
+            if family == "poisson":
+                big = q.copy()
+                big[0] = 800.0                      # mu = exp(eta) overflows in every row
+                _, _, H = m.hessian(0, big)
+                assert not np.isfinite(H).any()
+            bad = q.copy()
+            bad[1] = np.nan
+            _, _, H = m.hessian(0, bad)
+            if family == "linear":                  # H_tt does not depend on eta; the u row and column do
+                assert not np.isfinite(H[-1]).any() and not np.isfinite(H[:, -1]).any()
+                assert np.isfinite(H[:-1, :-1]).all()
+            else:
+                assert not np.isfinite(H).any()
+        finally:
+            m.close()
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+def test_grouped_launch_and_position_change_no_bit(ctx, family):
+    """shard = -1 over 3 shards of different n is bit-identical to three single-shard calls; the same
+    rows as shard 0 or shard 2 of a model give the same bits."""
+    from stark_amd import engine
+    d = 17
+    parts = []
+    for n in (37, multi_chunk_n(d), 600):
+        rng, X, y, _ = make_data(family, n, d)
+        parts.append({"x": X, "y": y})
+    m = engine.Model(ctx, family, parts)
+    m2 = engine.Model(ctx, family, parts[::-1])
+    try:
+        Q = rng.normal(0, 0.3, (3, m.D[0]))
+        lp, g, H = m.hessian(None, Q)
+        for s in range(3):
+            lp1, g1, H1 = m.hessian(s, Q[s])
+            assert lp1 == lp[s] and np.array_equal(g1, g[s]) and np.array_equal(H1, H[s])
+            assert np.array_equal(H[s], H[s].T)
+            _, _, H2 = m2.hessian(2 - s, Q[s])
+            assert np.array_equal(H2, H[s])
+            assert rel_err(H[s], ref_hessian(family, parts[s]["x"], parts[s]["y"], Q[s])) < BAR
+    finally:
+        m.close()
+        m2.close()
+
+
+def test_refusals_name_the_family_or_the_limit(ctx):
+    from stark_amd import engine
+    from stark_amd._lib import StarkHipError
+    m = engine.Model(ctx, "schools", [{"y": [28.0, 8.0, -3.0], "sigma": [15.0, 10.0, 16.0]}])
+    try:
+        with pytest.raises(StarkHipError, match="schools") as e:
+            m.hessian(0, np.zeros(m.D[0]))
+        assert e.value.code == -1
+    finally:
+        m.close()
+    rng = np.random.default_rng(3)
+    m = engine.Model(ctx, "logistic", [{"x": rng.normal(size=(20, 129)), "y": rng.integers(0, 2, 20)}])
+    try:
+        with pytest.raises(StarkHipError, match="128") as e:
+            m.hessian(0, np.zeros(130))
+        assert e.value.code == -1
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("n,d", [(333, 5), (1030, 100)])
+@pytest.mark.parametrize("family", FAMILIES)
+def test_agrees_with_the_difference_hessian(ctx, family, n, d):
+    """Against the library's own gradient: tools.laplace.hessian at h = 0.1 posterior sd, within 1e-4
+    of max |H| (the difference Hessian's own truncation error at these shapes is <= 1.6e-5)."""
+    from stark_amd import engine
+    from tools import laplace as L
+    _, X, y, truth = make_data(family, n, d)
+    m = engine.Model(ctx, family, [{"x": X, "y": y}])
+    try:
+        _, _, H = m.hessian(0, truth)
+        sd = np.sqrt(np.diag(np.linalg.inv(-H)))
+        assert np.isfinite(sd).all()
+        Hd = L.hessian(m, [0], truth, 0.1 * sd)
+        err = float(np.abs(H - Hd).max() / np.abs(H).max())
+        print(f"MAXERR difference_hessian[{family}-{n}-{d}] {err:.3e}")
+        assert err < 1e-4
+    finally:
+        m.close()
