@@ -34,6 +34,8 @@
  *   stk_consensus_weighted      W_s = -H_s, the exact consensus weights.  No reference counterpart: on the
  *                               product path they supersede tools/laplace.py's central difference of the
  *                               gradient (2 D gradient points per Hessian)
+ *   stk_log_predictive /        per-row statistics over S draws (lppd, WAIC penalty, fitted mean) and their
+ *   stk_predictive_launch_info  per-shard totals.  No reference counterpart
  *
  * Conventions
  *   - Return 0 on success, a negative STK_E_* code on failure; stk_last_error() gives a
@@ -301,6 +303,39 @@ STK_API int stk_log_density_hessian(stk_model* m, int shard, const double* q, do
  * block, out[3] dynamic LDS bytes, out[4] bytes of chunk-partial workspace per shard.  The three families
  * share one geometry (d + 2 live columns: x, the ones column, linear's residual column). */
 STK_API int stk_hessian_launch_info(int64_t n_rows, int32_t d, int64_t out[5]);
+
+/* ---- pointwise log-predictive sweep (regression families, 1 <= d <= 128): for every ROW, statistics
+ * over S draws -- the reduction the log-density hooks do not form (they reduce over rows for each draw) ----
+ * A draw is an unconstrained point q_s[D] in the layout of stk_log_density_grad: (alpha, beta[1..d]) for
+ * logistic and poisson, with u = log sigma appended for linear.  With eta_is = alpha_s + x_i . beta_s the
+ * pointwise log likelihood is the NORMALISED one (nothing dropped; no prior and no Jacobian enter):
+ *   logistic  z = (2 y_i - 1) eta, ll = min(z, 0) - log1p(exp(-|z|)),              g = 1 / (1 + exp(-eta))
+ *   poisson   ll = y_i eta - exp(eta) - lgamma(y_i + 1),                           g = exp(eta)
+ *   linear    r = y_i - eta, ll = -log(2 pi)/2 - u_s - r^2 e^{-2 u_s} / 2,         g = eta
+ * Per row i, over the S draws (S >= 1):
+ *   lppd_i = logsumexp_s(ll_is) - log S          mean_i = (1/S) sum_s ll_is
+ *   var_i  = the sample variance of ll_is with denominator S - 1, and 0 at S = 1
+ *   mu_i   = (1/S) sum_s g_is                    elpd_i = lppd_i - var_i
+ * Per shard, eight doubles of totals: [0] n, [1] sum lppd_i, [2] sum var_i (p_waic), [3] sum elpd_i,
+ * [4] sum elpd_i^2, [5] the number of rows with var_i > 0.4 (the usual WAIC reliability flag), [6] the
+ * number of rows where any of the four statistics is non-finite, [7] 0.  The totals are plain sums: a
+ * non-finite row makes its sums non-finite, and slot 6 says how many there were.
+ * Non-finite values propagate as IEEE arithmetic on the definitions gives them, never as a finite wrong
+ * number: a NaN eta makes the row's statistics NaN; a poisson exp(eta) that overflows gives ll = -inf for
+ * that draw, which adds 0 to the lppd sum (every draw -inf: lppd_i = -inf, not NaN), and mean_i is then
+ * -inf and var_i NaN.
+ * q [S][D]: the same draws for every shard.  shard == -1: every shard in one grouped launch; totals is
+ * then [nshards][8] and rows NULL or [sum n_rows][4], shard-major, (lppd, mean, var, mu) per row.  Either
+ * output may be NULL, not both.  Row i's statistics depend only on (x_i, y_i) and the draws: they carry
+ * the same bits whatever the shard's length, its position in the model and the number of shards in the
+ * call; the totals are bitwise independent of how many shards share the call and of the device.
+ * STK_E_ARG (the message names the family or the offending d) for 8 schools, d > 128, S < 1, a NULL q
+ * and both outputs NULL. */
+STK_API int stk_log_predictive(stk_model* m, int shard, const double* q, int32_t S, double* rows, double* totals);
+/* host only, like stk_sweep_launch_info: out[0] rows per tile, out[1] chunks per shard, out[2] waves per
+ * block, out[3] dynamic LDS bytes, out[4] bytes of the draw image (16-draw tiles of ceil(d / 4) k-steps x
+ * 64 lanes plus 64 per-draw scalars), out[5] bytes of chunk-partial workspace per shard. */
+STK_API int stk_predictive_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]);
 
 /* ---- sampling: stark/stark.py:43-56 for every shard of the model ---- */
 STK_API int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out);

@@ -70,7 +70,7 @@ struct stk_ctx {
   bool own_stream = true;     // false: a caller's stream (stk_ctx_create_on_stream), not destroyed here
   int profiling = 0;
   int refs = 1;
-  DevBuf scratch[12];
+  DevBuf scratch[15];
 };
 
 struct stk_model {
@@ -694,6 +694,80 @@ int stk_log_density_hessian(stk_model* m, int shard, const double* q, double* lp
   STK_HIP_CHECK(stk_launch_hessian(m->family, m->sh_dev.as<ShardDev>(), shard0, nsh, m->d, D, Gs, qb,
                                    ctx->scratch[7].as<double>(), hb, st));
   STK_HIP_CHECK(hipMemcpyAsync(hess, hb, sizeof(double) * hn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
+// ---------------------------------------------------------------- pointwise log-predictive sweep (predictive.hip)
+// The sweep's launch shape over a shard of n_rows x d against S draws (host only: no device).
+// out: rows per tile, chunks per shard, waves per block, LDS bytes, draw-image bytes, chunk-partial
+// workspace bytes per shard.
+int stk_predictive_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_predictive_launch_info: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(stk_predictive_supported(d), "the log-predictive sweep covers 1 <= d <= 128 covariates, not d = %d", d);
+  ARG_CHECK(S >= 1, "the log-predictive sweep needs S >= 1 draws, not S = %d", S);
+  const int64_t v[6] = {stk_predictive_rows_per_tile(), stk_predictive_chunks(n_rows), stk_predictive_waves(),
+                        (int64_t)stk_predictive_lds_bytes(d), (int64_t)stk_predictive_image_bytes(d, S),
+                        (int64_t)stk_predictive_ws_bytes(n_rows)};
+  memcpy(out, v, sizeof(v));
+  return STK_OK;
+}
+
+// The same S draws against one shard or (shard == -1) every shard: one preparation launch, one sweep
+// launch and one reduce launch for all of them.  Per-row output goes straight to `rows` when that is
+// device memory, else through a staging buffer.
+int stk_log_predictive(stk_model* m, int shard, const double* q, int32_t S, double* rows, double* totals) {
+  ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_log_predictive: bad model or shard");
+  ARG_CHECK(is_regression(m->family), "stk_log_predictive: no log-predictive sweep for the %s family (regressions only)",
+            family_name(m->family));
+  ARG_CHECK(stk_predictive_supported(m->d),
+            "stk_log_predictive: the log-predictive sweep covers 1 <= d <= 128 covariates, not d = %d (%s family)", m->d,
+            family_name(m->family));
+  ARG_CHECK(S >= 1, "stk_log_predictive: S = %d draws; the %s family at d = %d needs S >= 1", S, family_name(m->family), m->d);
+  ARG_CHECK(q, "stk_log_predictive: q is NULL (%s family, d = %d)", family_name(m->family), m->d);
+  ARG_CHECK(rows || totals, "stk_log_predictive: rows and totals are both NULL (%s family, d = %d)", family_name(m->family),
+            m->d);
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int D = m->Dmax, shard0 = shard < 0 ? 0 : shard, nsh = shard < 0 ? m->nshards : 1;
+  int Gs = 1;
+  std::vector<int64_t> off(nsh);
+  int64_t nrows = 0;
+  for (int s = 0; s < nsh; ++s) {
+    Gs = std::max(Gs, stk_predictive_chunks(m->sh[shard0 + s].n));
+    off[s] = nrows;
+    nrows += m->sh[shard0 + s].n;
+  }
+  const size_t qn = (size_t)S * D, img_bytes = stk_predictive_image_bytes(m->d, S);
+  RC(ctx->scratch[12].ensure(img_bytes + sizeof(double) * qn));
+  RC(ctx->scratch[13].ensure(sizeof(double) * 8 * ((size_t)nsh * Gs + nsh) + sizeof(int64_t) * nsh));
+  double* img = ctx->scratch[12].as<double>();
+  double* qb = img + img_bytes / sizeof(double);
+  double* partial = ctx->scratch[13].as<double>();
+  double* tb = partial + (size_t)nsh * Gs * 8;
+  int64_t* offb = reinterpret_cast<int64_t*>(tb + (size_t)nsh * 8);
+  double* rb = nullptr;
+  bool staged = false;
+  if (rows) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, rows) == hipSuccess && at.type == hipMemoryTypeDevice) {
+      rb = rows;
+    } else {
+      (void)hipGetLastError();   // a plain host pointer is no error here
+      RC(ctx->scratch[14].ensure(sizeof(double) * 4 * (size_t)nrows));
+      rb = ctx->scratch[14].as<double>();
+      staged = true;
+    }
+  }
+  STK_HIP_CHECK(hipMemcpyAsync(qb, q, sizeof(double) * qn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipMemcpyAsync(offb, off.data(), sizeof(int64_t) * nsh, hipMemcpyHostToDevice, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));   // off is a local
+  STK_HIP_CHECK(stk_launch_predictive_prep(m->family, m->d, D, S, qb, img, st));
+  STK_HIP_CHECK(stk_launch_predictive(m->family, m->sh_dev.as<ShardDev>(), shard0, nsh, m->d, Gs, S, img, partial, rb,
+                                      offb, tb, st));
+  if (totals) STK_HIP_CHECK(hipMemcpyAsync(totals, tb, sizeof(double) * 8 * nsh, hipMemcpyDefault, st));
+  if (staged) STK_HIP_CHECK(hipMemcpyAsync(rows, rb, sizeof(double) * 4 * (size_t)nrows, hipMemcpyDefault, st));
   STK_HIP_CHECK(hipStreamSynchronize(st));
   return STK_OK;
 }

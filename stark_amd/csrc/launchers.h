@@ -92,6 +92,20 @@ size_t stk_hessian_ws_bytes(int64_t n, int d);   // chunk-partial workspace of o
 hipError_t stk_launch_hessian(int family, const stk::ShardDev* shards, int shard0, int nsh, int d, int D, int Gs,
                               const double* q, double* partial, double* hess, hipStream_t st);
 
+// ---- predictive.hip (regressions, d <= 128): the pointwise log-predictive sweep's geometry and launches
+bool stk_predictive_supported(int d);
+int stk_predictive_chunks(int64_t n);
+int stk_predictive_rows_per_tile();
+int stk_predictive_waves();
+int stk_predictive_tiles(int S);                   // 16-draw tiles
+size_t stk_predictive_lds_bytes(int d);
+size_t stk_predictive_image_bytes(int d, int S);
+size_t stk_predictive_ws_bytes(int64_t n);         // chunk-partial workspace of one shard
+hipError_t stk_launch_predictive_prep(int family, int d, int D, int S, const double* q, double* img, hipStream_t st);
+hipError_t stk_launch_predictive(int family, const stk::ShardDev* shards, int shard0, int nsh, int d, int Gs, int S,
+                                 const double* img, double* partial, double* rows, const int64_t* rowoff,
+                                 double* totals, hipStream_t st);
+
 // ---- nuts.hip (and its nuts_fused4.hip / nuts_dense.hip translation units)
 int stk_nch_for(int Dmax);
 size_t stk_fused_lds_bytes(const stk::NutsArgs& A, int nch);

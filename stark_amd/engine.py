@@ -440,6 +440,31 @@ class Model:
                                                   g.ctypes.data, H.ctypes.data))
         return (lp, g, H) if every else (lp[0], g[0], H[0])
 
+    def log_predictive(self, q, shard=None, rows=False):
+        """Per-row statistics of the normalised pointwise log likelihood over the S draws ``q`` [S, D]
+        (unconstrained, the layout of ``log_density_grad``), and their per-shard totals
+        (stk_log_predictive: the pointwise log-predictive sweep; regression families with d <= 128).
+        shard: an index (totals [8]) or None for every shard in one grouped launch (totals
+        [nshards, 8]); ``waic(totals)`` turns either into the WAIC summary.  rows=True also returns a
+        dict of per-row arrays ``lppd``, ``mean``, ``var``, ``mu`` (shard-major when shard is None).
+        Non-finite values are what IEEE arithmetic on the definitions gives (include/stark_hip.h);
+        totals[..., 6] counts the rows that have one."""
+        every = shard is None
+        q = np.ascontiguousarray(np.atleast_2d(q), np.float64)
+        D = self.D[0 if every else shard]
+        if q.ndim != 2 or q.shape[1] != D:
+            raise ValueError(f"q must be [S, D = {D}], got {q.shape}")
+        ns = self.nshards if every else 1
+        n = sum(self.n_rows) if every else self.n_rows[shard]
+        tot = np.empty((ns, 8))
+        out = np.empty((n, 4)) if rows else None
+        check(_lib.load().stk_log_predictive(self._h, -1 if every else int(shard), q.ctypes.data, q.shape[0],
+                                             _ptr(out), tot.ctypes.data))
+        tot = tot if every else tot[0]
+        if not rows:
+            return tot
+        return tot, {k: np.ascontiguousarray(out[:, j]) for j, k in enumerate(("lppd", "mean", "var", "mu"))}
+
     def set_prior(self, alpha=None, beta=None):
         """normal(0, s) priors on alpha and beta (regressions); None or 0: flat."""
         check(_lib.load().stk_model_set_prior(self._h, float(alpha or 0.0), float(beta or 0.0)))
@@ -703,6 +728,53 @@ def hessian_launch(n_rows: int, n_cols: int) -> dict:
     out = np.zeros(5, np.int64)
     check(_lib.load().stk_hessian_launch_info(int(n_rows), int(n_cols), out.ctypes.data))
     return dict(zip(("T", "G", "waves", "lds_bytes", "ws_bytes_per_shard"), (int(v) for v in out)))
+
+
+def predictive_launch(n_rows: int, n_cols: int, S: int) -> dict:
+    """The launch shape of the pointwise log-predictive sweep over a shard of ``n_rows`` x ``n_cols``
+    against ``S`` draws (stk_predictive_launch_info): rows per tile ``T``, chunks per shard ``G``,
+    ``waves`` per block, ``lds_bytes``, ``image_bytes`` of the draw image and ``ws_bytes_per_shard``.
+    Raises STK_E_ARG past 128 covariates.  Host only."""
+    out = np.zeros(6, np.int64)
+    check(_lib.load().stk_predictive_launch_info(int(n_rows), int(n_cols), int(S), out.ctypes.data))
+    return dict(zip(("T", "G", "waves", "lds_bytes", "image_bytes", "ws_bytes_per_shard"), (int(v) for v in out)))
+
+
+def waic(totals) -> dict:
+    """WAIC from the ``[..., 8]`` totals of ``Model.log_predictive``, summed over shards in the order
+    given: ``n``, ``lppd``, ``p_waic``, ``elpd_waic`` = lppd - p_waic summed per row, its standard
+    error ``se`` = sqrt(n / (n - 1) (sum e^2 - (sum e)^2 / n)) (0 at n = 1), ``waic`` = -2 elpd_waic,
+    ``n_high_var`` (rows with var > 0.4, where WAIC is unreliable) and ``n_non_finite``."""
+    t = np.asarray(totals, np.float64)
+    if t.shape[-1] != 8:
+        raise ValueError(f"totals must be [..., 8], got shape {t.shape}")
+    acc = np.zeros(8)
+    for row in t.reshape(-1, 8):         # shard order
+        acc = acc + row
+    n, lppd, p, e, e2 = (float(v) for v in acc[:5])
+    se = 0.0
+    if n > 1:
+        v = e2 - e * e / n               # rounding can leave a tiny negative; a non-finite row gives NaN
+        se = float(np.sqrt(n / (n - 1.0) * max(v, 0.0))) if np.isfinite(v) else float("nan")
+    return {"n": int(n), "lppd": lppd, "p_waic": p, "elpd_waic": e, "se": se, "waic": -2.0 * e,
+            "n_high_var": int(acc[5]), "n_non_finite": int(acc[6])}
+
+
+def fitted_mean(ctx, family, x, q):
+    """The posterior mean of E[y | x] for new rows ``x`` [n, d] over the draws ``q`` [S, D]: ``mu`` of
+    ``Model.log_predictive`` on a model of these rows with zero ``y`` (logistic: the probability;
+    poisson: the rate; linear: the linear predictor)."""
+    fam = FAMILIES.get(family, family)
+    if fam not in (STK_LINREG, STK_LOGREG, STK_POISSON):
+        raise ValueError("fitted_mean needs a regression family (linear, logistic, poisson)")
+    x = np.ascontiguousarray(x, np.float64)
+    if x.ndim != 2:
+        raise ValueError("x must be n x d")
+    m = Model(ctx, fam, [{"x": x, "y": np.zeros(x.shape[0], np.float64 if fam == STK_LINREG else np.int32)}])
+    try:
+        return m.log_predictive(q, 0, rows=True)[1]["mu"]
+    finally:
+        m.close()
 
 
 def laplace(model, shards=None, q0=None, reduce=None, max_iter=50, tol=1e-8):

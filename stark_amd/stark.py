@@ -114,6 +114,35 @@ def _unconstrain(family, data, init_dict):
     return np.asarray(v)
 
 
+def unconstrain_draws(family, samples, n_cols=None):
+    """The P x S constrained matrix ``concensusWeight`` returns (rows alpha, beta[1..d], [sigma], lp__)
+    as the [S][D] unconstrained draws ``engine.Model.log_predictive`` scores: lp__ is dropped and
+    linear's sigma becomes u = log sigma.  n_cols: the model's covariate count d, when known
+    (``Stark.waic`` passes it); None takes it from the row count.
+    ValueError for 8 schools (no log-predictive sweep), for P != D + 1 -- the draws of a ``pars=``
+    selection cannot be scored: every parameter is needed -- and for a sigma <= 0 (names the draw)."""
+    if family not in ("linear", "logistic", "poisson"):
+        raise ValueError(f"draws of the {family} family cannot be scored: the log-predictive sweep covers the "
+                         "regression families (linear, logistic, poisson), not 8 schools")
+    m = np.asarray(samples, np.float64)
+    if m.ndim != 2:
+        raise ValueError(f"samples must be the P x S draw matrix, got shape {m.shape}")
+    extra = 2 if family == "linear" else 1              # parameters besides beta
+    d = int(n_cols) if n_cols is not None else m.shape[0] - 1 - extra
+    D = d + extra
+    if d < 1 or m.shape[0] != D + 1:
+        raise ValueError(f"samples has {m.shape[0]} rows, the {family} model with {max(d, 0)} covariates has D + 1 = "
+                         f"{D + 1} (alpha, beta, {'sigma, ' if family == 'linear' else ''}lp__): the draws of a pars= "
+                         "selection cannot be scored")
+    q = np.ascontiguousarray(m[:D].T)
+    if family == "linear":
+        bad = np.flatnonzero(~(q[:, -1] > 0))
+        if bad.size:
+            raise ValueError(f"draw {int(bad[0])}: sigma = {q[bad[0], -1]!r} is not positive")
+        q[:, -1] = np.log(q[:, -1])
+    return q
+
+
 def thin_draws(draws, chains, thin):
     """Stan's num_thin: of each chain's post-warmup iterations m = 0, 1, ... keep those with
     m % thin == 0 (ceil(S / thin) draws per chain; services/util/generate_transitions), columns
@@ -363,6 +392,44 @@ class Stark:
             return out
         subposteriors = self._run_distributed(parts, **kwargs)
         out, _ = engine.consensus(subposteriors, separate_lp=separate_lp)
+        return out
+
+    def _partition_totals(self, datas, q):
+        """One model of this rank's partitions; their [8] totals of the pointwise log-predictive sweep
+        over the draws q [S][D] (engine.Model.log_predictive, no per-row output), one per data dict."""
+        shards = [frontend.pack_data(self.family, d) for d in datas]
+        model = engine.Model(engine.default_context(), self.family, shards)
+        try:
+            return list(model.log_predictive(q))
+        finally:
+            model.close()
+
+    def waic(self, samples):
+        """WAIC of a P x S matrix of draws -- what ``concensusWeight`` returns, with either kind of
+        weights, or one subposterior -- against EVERY partition's rows, without a full-data run.
+        Every rank scores the partitions ``_run_distributed`` places on it (partition p on rank
+        p % world) in one grouped launch; the [1, 8] totals are all-gathered and summed in partition
+        order, so every rank returns the same bits on 1 or N ranks.  Returns ``engine.waic``'s dict
+        (n, lppd, p_waic, elpd_waic, se, waic, n_high_var, n_non_finite) plus ``partition_totals``
+        [n_partitions, 8].  Regression families with at most 128 covariates; ``unconstrain_draws``
+        says which draws cannot be scored."""
+        if self.family is None:
+            raise RuntimeError("call setStanModel() first")
+        if self.family == "schools":
+            unconstrain_draws(self.family, samples)       # raises: names the family
+        parts = _rdd.partitions_of(self.rdd)
+        rank, ws = dist.world()
+        mine = dist.local_partitions(len(parts), rank, ws)
+        datas = [self.prepare_data_callback(list(parts[p])) for p in mine]
+        q = unconstrain_draws(self.family, samples, n_cols=int(datas[0]["K"]) if datas else None)
+        local = {}
+        if datas:
+            tots = self._partition_totals(datas, q)
+            local = {p: np.asarray(t, np.float64).reshape(1, 8) for p, t in zip(mine, tots)}
+        totals = np.concatenate([np.asarray(t, np.float64).reshape(1, 8)
+                                 for t in dist.all_gather_partitions(local, len(parts))])
+        out = engine.waic(totals)
+        out["partition_totals"] = totals
         return out
 
     def distribute(self, n=2, reference_union=False, **kwargs):
