@@ -329,6 +329,9 @@ STK_API int stk_hessian_launch_info(int64_t n_rows, int32_t d, int64_t out[5]);
  * output may be NULL, not both.  Row i's statistics depend only on (x_i, y_i) and the draws: they carry
  * the same bits whatever the shard's length, its position in the model and the number of shards in the
  * call; the totals are bitwise independent of how many shards share the call and of the device.
+ * rows may be host or device memory.  Memory of the context's own device is written in place by the
+ * sweep; anything else -- host memory, or memory of ANOTHER device, which a kernel here must not
+ * dereference -- is filled through a staging buffer of the context and one copy.
  * STK_E_ARG (the message names the family or the offending d) for 8 schools, d > 128, S < 1, a NULL q
  * and both outputs NULL. */
 STK_API int stk_log_predictive(stk_model* m, int shard, const double* q, int32_t S, double* rows, double* totals);

@@ -1,0 +1,312 @@
+// C ABI of libstark_hip.so: the chain plan, the lp / grad parity hooks, the host-only launch-info
+// calls, the analytic Hessian and the pointwise log-predictive sweep.
+#include "capi_internal.h"
+
+// The chain counts that are ONE sweep launch in the two single-launch parity hooks (stk_log_density_grad's
+// own batching and stk_log_density_grad_shards): their acceptance set stays as it was before the
+// sampler batched chains -- 16 only where k_sweep16 itself runs (d <= 128).
+static bool hook_single_launch(int C, int d) { return stk_sweep_supported(C, d) && (C != 16 || d <= 128); }
+
+// The chain batches of a regression shard's C chains: greedy, largest first, over the single-launch
+// sizes {64, 16, 8, 4, 2, 1} a sweep covers at d (stk_sweep_supported, sweep.hip, says whether 16
+// is a batch size at d; stk_sweep_plan then picks each batch's kernel).  A pure function of
+// (C, d) -- never of n, the shard count or the device -- so every rank derives the same plan.
+// No padding, no idle chains.
+std::vector<int> chain_batches(int C, int d) {
+  std::vector<int> b;
+  for (const int sz : {64, 16, 8, 4, 2, 1}) {
+    if (!stk_sweep_supported(sz, d)) continue;
+    for (; C >= sz; C -= sz) b.push_back(sz);
+  }
+  if (C != 0) b.clear();   // no sweep covers d
+  return b;
+}
+
+// Refuses, before anything is launched, a shard that no sweep covers at its n, d and batch size.
+int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int count, ChainPlan* cp) {
+  *cp = ChainPlan();
+  for (const int sz : sizes) {
+    ChainBatch b;
+    b.c0 = cp->Ct;
+    b.part_off = cp->partial_bytes / sizeof(double);
+    for (int sh = first; sh < first + count;) {
+      SweepGroup gr{sh, 1, stk_sweep_plan(m->sh[sh].n, m->d, sz, 0)};
+      ARG_CHECK(gr.launch.kind != SWEEP_NONE,
+                "shard %d: no sweep covers n = %lld rows of d = %d covariates at C = %d chains (a chunk of the shard "
+                "must fit a buffer descriptor: split the shard)", sh, (long long)m->sh[sh].n, m->d, sz);
+      while (sh + gr.nsh < first + count && m->sh[sh + gr.nsh].n == m->sh[sh].n) ++gr.nsh;
+      b.Gs = std::max(b.Gs, gr.launch.G);
+      if (gr.launch.ws_bytes > cp->ws_at.ws_bytes) cp->ws_at = gr.launch;
+      b.groups.push_back(gr);
+      sh += gr.nsh;
+    }
+    cp->partial_bytes += sizeof(double) * (size_t)m->nshards * b.Gs * sz * (m->d + 2);
+    cp->Ct += sz;
+    cp->batches.push_back(std::move(b));
+  }
+  cp->ws_bytes = cp->ws_at.ws_bytes * m->nshards;
+  return STK_OK;
+}
+// Every batch's sweep over every shard group; then (plan_reduces) every batch's reduction.  `run`
+// holds the run's buffers; a batch's partial-sum region, stride and first chain are filled in here.
+static SweepCall batch_call(const ChainPlan& cp, const ChainBatch& b, SweepCall c) {
+  c.partial += b.part_off;
+  c.Gs = b.Gs;
+  c.Ct = cp.Ct;
+  c.c0 = b.c0;
+  return c;
+}
+hipError_t plan_sweeps(const stk_model* m, const ChainPlan& cp, const SweepCall& run, hipStream_t st) {
+  for (const auto& b : cp.batches) {
+    const SweepCall c = batch_call(cp, b, run);
+    for (const auto& gr : b.groups)
+      if (const hipError_t e = stk_launch_sweep(m->family, gr.launch, gr.shard0, gr.nsh, c, st)) return e;
+  }
+  return hipSuccess;
+}
+hipError_t plan_reduces(const stk_model* m, const ChainPlan& cp, const SweepCall& run, double* lp, double* g,
+                        hipStream_t st) {
+  for (const auto& b : cp.batches) {
+    const SweepCall c = batch_call(cp, b, run);
+    for (const auto& gr : b.groups)
+      if (const hipError_t e = stk_launch_sweep_reduce(m->family, gr.launch, gr.shard0, gr.nsh, c, lp, g, st)) return e;
+  }
+  return hipSuccess;
+}
+
+// The body of the regression parity hooks.  np points of D doubles at q go to rows [row0, row0 +
+// nrows) of the [nshards * plan.Ct][Dp] point buffer (the last point repeated to fill), the plan's
+// sweeps and reductions run, and lp / grad of the first np rows come back.  The caller synchronises.
+static int hook_eval(stk_model* m, const ChainPlan& plan, size_t row0, size_t nrows, const double* q, size_t np,
+                     double* lp, double* grad) {
+  stk_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->stream;
+  const int D = m->Dmax, Dp = (m->Dmax + 7) / 8 * 8;   // one d for every shard of a regression model
+  const size_t rows = (size_t)m->nshards * plan.Ct, pitch = sizeof(double) * Dp, width = sizeof(double) * D;
+  SweepWs ws{};
+  if (plan.ws_bytes) {
+    RC(ctx->scratch[SCR_HOOK_WS].ensure(plan.ws_bytes));
+    ws = stk_sweep_ws(ctx->scratch[SCR_HOOK_WS].p, plan.ws_at, m->nshards);
+  }
+  RC(ctx->scratch[SCR_HOOK_Q].ensure(rows * pitch));
+  RC(ctx->scratch[SCR_HOOK_LP].ensure(sizeof(double) * rows));
+  RC(ctx->scratch[SCR_HOOK_GRAD].ensure(rows * pitch));
+  RC(ctx->scratch[SCR_HOOK_PARTIAL].ensure(plan.partial_bytes));
+  double* qb = ctx->scratch[SCR_HOOK_Q].as<double>();
+  double* lpb = ctx->scratch[SCR_HOOK_LP].as<double>();
+  double* gb = ctx->scratch[SCR_HOOK_GRAD].as<double>();
+  STK_HIP_CHECK(hipMemcpy2DAsync(qb + row0 * Dp, pitch, q, width, width, np, hipMemcpyDefault, st));
+  for (size_t r = np; r < nrows; ++r)
+    STK_HIP_CHECK(hipMemcpyAsync(qb + (row0 + r) * Dp, q + (np - 1) * D, width, hipMemcpyDefault, st));
+  const SweepCall run{m->sh_dev.as<ShardDev>(), qb, ctx->scratch[SCR_HOOK_PARTIAL].as<double>(), nullptr, 0, nullptr,
+                      plan.ws_bytes ? &ws : nullptr, Dp, 0, 0, 0};
+  STK_HIP_CHECK(plan_sweeps(m, plan, run, st));
+  STK_HIP_CHECK(plan_reduces(m, plan, run, lpb, gb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(lp, lpb + row0, sizeof(double) * np, hipMemcpyDefault, st));
+  if (grad) STK_HIP_CHECK(hipMemcpy2DAsync(grad, width, gb + row0 * Dp, pitch, width, np, hipMemcpyDefault, st));
+  return STK_OK;
+}
+// Every shard at sum(sizes) points each, in those chain batches.
+static int hook_every_shard(stk_model* m, const std::vector<int>& sizes, const double* q, double* lp, double* grad) {
+  STK_HIP_CHECK(hipSetDevice(m->ctx->device));
+  ChainPlan plan;
+  RC(chain_plan(m, sizes, 0, m->nshards, &plan));
+  const size_t rows = (size_t)m->nshards * plan.Ct;
+  RC(hook_eval(m, plan, 0, rows, q, rows, lp, grad));
+  STK_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  return STK_OK;
+}
+
+extern "C" {
+
+// ---------------------------------------------------------------- lp / grad (parity hook)
+int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, double* lp, double* grad) {
+  ARG_CHECK(m && q && lp && C > 0 && shard >= 0 && shard < m->nshards, "stk_log_density_grad: bad arguments");
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  const ShardDev& s = m->sh[shard];
+  const int D = s.D;
+  hipStream_t st = ctx->stream;
+  if (m->family != STK_SCHOOLS) {
+    // the chain batch the sampler's sweep uses: 64 (two-pass fp64 MFMA GEMMs) from 64 points,
+    // 16 (fp64 MFMA) from 16 when d <= 128, else 4 / 2 / 1; this shard alone, the last point
+    // repeated to fill the last batch (the kernel reads rows shard * Cb + c of the point buffer)
+    const int Cb = C <= 1 ? 1 : (C <= 2 ? 2 : (C >= 64 ? 64 : (C < 16 || !hook_single_launch(16, s.d) ? 4 : 16)));
+    ChainPlan plan;
+    RC(chain_plan(m, {Cb}, shard, 1, &plan));
+    for (int c0 = 0; c0 < C; c0 += Cb)
+      RC(hook_eval(m, plan, (size_t)shard * Cb, Cb, q + (size_t)c0 * D, std::min(Cb, C - c0), lp + c0,
+                   grad ? grad + (size_t)c0 * D : nullptr));
+    STK_HIP_CHECK(hipStreamSynchronize(st));
+    return STK_OK;
+  }
+  // 8 schools: the hooks' point, lp and grad buffers, one launch
+  const int Dp = (m->Dmax + 7) / 8 * 8;
+  RC(ctx->scratch[SCR_HOOK_Q].ensure(sizeof(double) * (size_t)C * Dp));
+  RC(ctx->scratch[SCR_HOOK_LP].ensure(sizeof(double) * (size_t)C));
+  RC(ctx->scratch[SCR_HOOK_GRAD].ensure(sizeof(double) * (size_t)C * Dp));
+  double* qb = ctx->scratch[SCR_HOOK_Q].as<double>();
+  double* lpb = ctx->scratch[SCR_HOOK_LP].as<double>();
+  double* gb = ctx->scratch[SCR_HOOK_GRAD].as<double>();
+  STK_HIP_CHECK(hipMemcpy2DAsync(qb, sizeof(double) * Dp, q, sizeof(double) * D, sizeof(double) * D, C, hipMemcpyDefault, st));
+  STK_HIP_CHECK(stk_launch_schools_lpgrad(m->sh_dev.as<ShardDev>(), shard, stk_nch_for(m->Dmax), qb, C, Dp, lpb, gb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(lp, lpb, sizeof(double) * C, hipMemcpyDefault, st));
+  if (grad)
+    STK_HIP_CHECK(hipMemcpy2DAsync(grad, sizeof(double) * D, gb, sizeof(double) * Dp, sizeof(double) * D, C, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
+// Every shard at C points each through the sampler's grouped launches (chain_plan with the one
+// batch C): the parity hook for multi-shard grids, shard0 > 0 and a partial-sum stride Gs above a
+// group's own G.
+int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
+  ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_shards: bad arguments");
+  ARG_CHECK(is_regression(m->family), "stk_log_density_grad_shards: regression families only");
+  ARG_CHECK(hook_single_launch(C, m->d), "points per shard must be a single batch size here: 1, 2, 4, 8, 16 (d <= 128) or 64");
+  return hook_every_shard(m, {C}, q, lp, grad);
+}
+
+// The same at ANY C >= 1 points per shard: the chain batches and grouped launches of a sampling
+// run at chains = C.
+int stk_log_density_grad_chains(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
+  ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_chains: bad arguments");
+  ARG_CHECK(is_regression(m->family), "stk_log_density_grad_chains: regression families only");
+  ARG_CHECK(!chain_batches(C, m->d).empty(), "no sweep covers %d covariates (1..1024)", m->d);
+  return hook_every_shard(m, chain_batches(C, m->d), q, lp, grad);
+}
+
+// The chain batches a regression shard's C chains run as at d covariates (host only: no device).
+int stk_chain_batches(int32_t C, int32_t d, int32_t* sizes, int32_t cap) {
+  ARG_CHECK(C >= 1 && d >= 1 && cap >= 0 && (sizes || cap == 0), "stk_chain_batches: need C >= 1, d >= 1, cap >= 0");
+  const std::vector<int> b = chain_batches(C, d);
+  ARG_CHECK(!b.empty(), "no sweep covers %d covariates (1..1024)", d);
+  for (size_t i = 0; i < b.size() && (int32_t)i < cap; ++i) sizes[i] = b[i];
+  return (int)b.size();
+}
+
+// The sweep one batch of C chains runs over a shard of n_rows x d (host only: no device).
+// out: kind, T, the LD handed to the kernel, G, LDS bytes, 64-chain workspace bytes per shard.
+int stk_sweep_launch_info(int64_t n_rows, int32_t d, int32_t C, int64_t out[6]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_sweep_launch_info: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(stk_sweep_supported(C, d), "%d chains are not one batch at %d covariates (stk_chain_batches)", C, d);
+  const SweepLaunch p = stk_sweep_plan(n_rows, d, C, 0);
+  ARG_CHECK(p.kind != SWEEP_NONE, "no sweep covers n = %lld rows of d = %d covariates at C = %d chains",
+            (long long)n_rows, d, C);
+  const int64_t v[6] = {p.kind, p.T, stk_sweep_args_ld(p), p.G, (int64_t)p.lds, (int64_t)p.ws_bytes};
+  memcpy(out, v, sizeof(v));
+  return STK_OK;
+}
+
+// ---------------------------------------------------------------- analytic Hessian (hessian.hip)
+// The Hessian sweep's launch shape over a shard of n_rows x d (host only: no device).
+// out: rows per tile, chunks per shard, waves per block, LDS bytes, chunk-partial workspace bytes per shard.
+int stk_hessian_launch_info(int64_t n_rows, int32_t d, int64_t out[5]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_hessian_launch_info: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(stk_hessian_supported(d), "the Hessian sweep covers 1 <= d <= 128 covariates, not d = %d", d);
+  const int64_t v[5] = {stk_hessian_rows_per_tile(), stk_hessian_chunks(n_rows), stk_hessian_waves(),
+                        (int64_t)stk_hessian_lds_bytes(d), (int64_t)stk_hessian_ws_bytes(n_rows, d)};
+  memcpy(out, v, sizeof(v));
+  return STK_OK;
+}
+
+// One point per shard.  lp / grad come from stk_log_density_grad itself (one C = 1 sweep per shard), so
+// they are its bits; the Hessians of all the call's shards are one sweep launch and one reduce launch.
+int stk_log_density_hessian(stk_model* m, int shard, const double* q, double* lp, double* grad, double* hess) {
+  ARG_CHECK(m && q && hess && shard >= -1 && shard < m->nshards, "stk_log_density_hessian: bad arguments");
+  ARG_CHECK(is_regression(m->family), "stk_log_density_hessian: no Hessian sweep for the %s family (regressions only)",
+            family_name(m->family));
+  ARG_CHECK(stk_hessian_supported(m->d), "stk_log_density_hessian: the Hessian sweep covers 1 <= d <= 128 covariates, not d = %d",
+            m->d);
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int D = m->Dmax;
+  const ShardRange r = shard_range(m, shard, stk_hessian_chunks);
+  if (lp || grad) {
+    for (int s = 0; s < r.nsh; ++s) {
+      double lp1 = 0.0;   // stk_log_density_grad needs a place for lp
+      RC(stk_log_density_grad(m, r.shard0 + s, q + (size_t)s * D, 1, lp ? lp + s : &lp1,
+                              grad ? grad + (size_t)s * D : nullptr));
+    }
+  }
+  size_t ws = 0;
+  for (int s = r.shard0; s < r.shard0 + r.nsh; ++s) ws = std::max(ws, stk_hessian_ws_bytes(m->sh[s].n, m->d));
+  const size_t qn = (size_t)r.nsh * D, hn = qn * D;
+  RC(ctx->scratch[SCR_HESS_WS].ensure(ws * r.nsh));
+  RC(ctx->scratch[SCR_HESS_QH].ensure(sizeof(double) * (qn + hn)));
+  double* qb = ctx->scratch[SCR_HESS_QH].as<double>();
+  double* hb = qb + qn;
+  STK_HIP_CHECK(hipMemcpyAsync(qb, q, sizeof(double) * qn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(stk_launch_hessian(m->family, m->sh_dev.as<ShardDev>(), r.shard0, r.nsh, m->d, D, r.Gs, qb,
+                                   ctx->scratch[SCR_HESS_WS].as<double>(), hb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(hess, hb, sizeof(double) * hn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
+// ---------------------------------------------------------------- pointwise log-predictive sweep (predictive.hip)
+// The sweep's launch shape over a shard of n_rows x d against S draws (host only: no device).
+// out: rows per tile, chunks per shard, waves per block, LDS bytes, draw-image bytes, chunk-partial
+// workspace bytes per shard.
+int stk_predictive_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_predictive_launch_info: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(stk_predictive_supported(d), "the log-predictive sweep covers 1 <= d <= 128 covariates, not d = %d", d);
+  ARG_CHECK(S >= 1, "the log-predictive sweep needs S >= 1 draws, not S = %d", S);
+  const int64_t v[6] = {stk_predictive_rows_per_tile(), stk_predictive_chunks(n_rows), stk_predictive_waves(),
+                        (int64_t)stk_predictive_lds_bytes(d), (int64_t)stk_predictive_image_bytes(d, S),
+                        (int64_t)stk_predictive_ws_bytes(n_rows)};
+  memcpy(out, v, sizeof(v));
+  return STK_OK;
+}
+
+// The same S draws against one shard or (shard == -1) every shard: one preparation launch, one sweep
+// launch and one reduce launch for all of them.  Per-row output goes straight to `rows` when that is
+// memory of the context's device, else through a staging buffer.
+int stk_log_predictive(stk_model* m, int shard, const double* q, int32_t S, double* rows, double* totals) {
+  ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_log_predictive: bad model or shard");
+  ARG_CHECK(is_regression(m->family), "stk_log_predictive: no log-predictive sweep for the %s family (regressions only)",
+            family_name(m->family));
+  ARG_CHECK(stk_predictive_supported(m->d),
+            "stk_log_predictive: the log-predictive sweep covers 1 <= d <= 128 covariates, not d = %d (%s family)", m->d,
+            family_name(m->family));
+  ARG_CHECK(S >= 1, "stk_log_predictive: S = %d draws; the %s family at d = %d needs S >= 1", S, family_name(m->family), m->d);
+  ARG_CHECK(q, "stk_log_predictive: q is NULL (%s family, d = %d)", family_name(m->family), m->d);
+  ARG_CHECK(rows || totals, "stk_log_predictive: rows and totals are both NULL (%s family, d = %d)", family_name(m->family),
+            m->d);
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int D = m->Dmax;
+  const ShardRange r = shard_range(m, shard, stk_predictive_chunks);
+  const int shard0 = r.shard0, nsh = r.nsh, Gs = r.Gs;
+  std::vector<int64_t> off(nsh);
+  int64_t nrows = 0;
+  for (int s = 0; s < nsh; ++s) {
+    off[s] = nrows;
+    nrows += m->sh[shard0 + s].n;
+  }
+  const size_t qn = (size_t)S * D, img_bytes = stk_predictive_image_bytes(m->d, S);
+  RC(ctx->scratch[SCR_PRED_IMG].ensure(img_bytes + sizeof(double) * qn));
+  RC(ctx->scratch[SCR_PRED_PARTIAL].ensure(sizeof(double) * 8 * ((size_t)nsh * Gs + nsh) + sizeof(int64_t) * nsh));
+  double* img = ctx->scratch[SCR_PRED_IMG].as<double>();
+  double* qb = img + img_bytes / sizeof(double);
+  double* partial = ctx->scratch[SCR_PRED_PARTIAL].as<double>();
+  double* tb = partial + (size_t)nsh * Gs * 8;
+  int64_t* offb = reinterpret_cast<int64_t*>(tb + (size_t)nsh * 8);
+  const bool staged = rows && !is_device_ptr(rows, ctx->device);
+  if (staged) RC(ctx->scratch[SCR_PRED_ROWS].ensure(sizeof(double) * 4 * (size_t)nrows));
+  double* rb = staged ? ctx->scratch[SCR_PRED_ROWS].as<double>() : rows;
+  STK_HIP_CHECK(hipMemcpyAsync(qb, q, sizeof(double) * qn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipMemcpyAsync(offb, off.data(), sizeof(int64_t) * nsh, hipMemcpyHostToDevice, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));   // off is a local
+  STK_HIP_CHECK(stk_launch_predictive_prep(m->family, m->d, D, S, qb, img, st));
+  STK_HIP_CHECK(stk_launch_predictive(m->family, m->sh_dev.as<ShardDev>(), shard0, nsh, m->d, Gs, S, img, partial, rb,
+                                      offb, tb, st));
+  if (totals) STK_HIP_CHECK(hipMemcpyAsync(totals, tb, sizeof(double) * 8 * nsh, hipMemcpyDefault, st));
+  if (staged) STK_HIP_CHECK(hipMemcpyAsync(rows, rb, sizeof(double) * 4 * (size_t)nrows, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,382 @@
+// C ABI of libstark_hip.so: models -- creation from host rows or the generator, info, priors, data
+// copy-out -- and the data fingerprints.
+#include "capi_internal.h"
+
+const char* family_name(int family) {
+  switch (family) {
+    case STK_SCHOOLS: return "schools";
+    case STK_LINREG: return "linear";
+    case STK_LOGREG: return "logistic";
+    case STK_POISSON: return "poisson";
+  }
+  return "unknown";
+}
+
+bool is_regression(int family) { return family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON; }
+
+ShardRange shard_range(const stk_model* m, int shard, int (*chunks)(int64_t n)) {
+  ShardRange r{shard < 0 ? 0 : shard, shard < 0 ? m->nshards : 1, 1};
+  for (int s = r.shard0; s < r.shard0 + r.nsh; ++s) r.Gs = std::max(r.Gs, chunks(m->sh[s].n));
+  return r;
+}
+
+static int family_dims(int family, int64_t n, int d, int* D, int* P) {
+  switch (family) {
+    case STK_SCHOOLS: *D = (int)n + 2; *P = 2 * (int)n + 3; return STK_OK;
+    case STK_LINREG: *D = d + 2; *P = d + 3; return STK_OK;
+    case STK_LOGREG: *D = d + 1; *P = d + 2; return STK_OK;
+    case STK_POISSON: *D = d + 1; *P = d + 2; return STK_OK;   // the logistic layout: alpha, beta, lp__
+  }
+  stk_set_error("unknown model family %d", family);
+  return STK_E_ARG;
+}
+
+// ---------------------------------------------------------------- creation
+// A model of `family` on ctx (which it holds) with no shard yet.
+static stk_model* model_new(stk_ctx* ctx, int family, int nshards, int d) {
+  stk_model* m = new stk_model();
+  m->ctx = ctx;
+  ctx->refs++;
+  m->family = family;
+  m->nshards = nshards;
+  m->d = d;
+  return m;
+}
+
+static int upload_shard_table(stk_model* m) {
+  for (auto& s : m->sh) {
+    m->Dmax = std::max(m->Dmax, s.D);
+    m->Pmax = std::max(m->Pmax, s.P);
+  }
+  RC(m->sh_dev.ensure(sizeof(ShardDev) * m->sh.size()));
+  STK_HIP_CHECK(hipMemcpyAsync(m->sh_dev.p, m->sh.data(), sizeof(ShardDev) * m->sh.size(), hipMemcpyHostToDevice,
+                               m->ctx->stream));
+  STK_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  return STK_OK;
+}
+
+// The end of both constructors.  rc: the outcome of the shards; a partly built model is destroyed.
+static int model_finish(stk_model* m, int rc, stk_model** out) {
+  if (rc == STK_OK) rc = upload_shard_table(m);
+  if (rc != STK_OK) {
+    stk_model_destroy(m);
+    return rc;
+  }
+  *out = m;
+  return STK_OK;
+}
+
+template <class T>
+static int upload(stk_model* m, const T* src, size_t count, const T** dst) {
+  m->bufs.emplace_back();
+  DevBuf& b = m->bufs.back();
+  RC(b.ensure(sizeof(T) * count));
+  STK_HIP_CHECK(hipMemcpyAsync(b.p, src, sizeof(T) * count, hipMemcpyDefault, m->ctx->stream));
+  *dst = b.as<T>();
+  m->bytes += (int64_t)(sizeof(T) * count);
+  return STK_OK;
+}
+
+// bernoulli_logit: y in {0, 1} (the sweeps read y as a sign bit); poisson_log: y >= 0.  Checked on the
+// device copy by a reduction that returns the first bad row (8 bytes back, not the shard).
+static int check_y_int(stk_model* m, int s, const int32_t* yi, int64_t n, bool pois) {
+  hipStream_t st = m->ctx->stream;
+  DevBuf flag;
+  RC(flag.ensure(sizeof(int64_t)));
+  int64_t bad = -1;
+  int32_t v = 0;
+  hipError_t e = pois ? stk_launch_check_ynonneg(yi, n, flag.as<int64_t>(), st) : stk_launch_check_y01(yi, n, flag.as<int64_t>(), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, flag.p, sizeof(int64_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && bad >= 0 && bad < n) e = hipMemcpy(&v, yi + bad, sizeof(int32_t), hipMemcpyDeviceToHost);
+  flag.release();
+  if (e != hipSuccess) {
+    stk_set_error("shard %d: y_int check failed: %s", s, hipGetErrorString(e));
+    return STK_E_HIP;
+  }
+  ARG_CHECK(bad < 0 || bad >= n, "shard %d: y_int[%lld] = %d; %s", s, (long long)bad, v,
+            pois ? "poisson_log needs y >= 0" : "bernoulli_logit needs 0 or 1");
+  return STK_OK;
+}
+
+// Shard s of a model from the caller's rows: validated, copied to the device, appended to m->sh.
+static int upload_shard(stk_model* m, int s, const stk_shard& in) {
+  const int family = m->family;
+  const size_t n = (size_t)in.n_rows;
+  ShardDev sd{};
+  sd.n = in.n_rows;
+  sd.d = family == STK_SCHOOLS ? 0 : in.n_cols;
+  ARG_CHECK(in.n_rows > 0, "shard %d: n_rows must be positive", s);
+  ARG_CHECK(family == STK_SCHOOLS || in.n_cols == m->d, "shard %d: n_cols %d differs from shard 0 (%d)", s, in.n_cols, m->d);
+  RC(family_dims(family, in.n_rows, sd.d, &sd.D, &sd.P));
+  if (family == STK_SCHOOLS) {
+    ARG_CHECK(in.y && in.sigma, "shard %d: schools needs y and sigma", s);
+    RC(upload(m, in.y, n, &sd.y));
+    RC(upload(m, in.sigma, n, &sd.sigma));
+  } else {
+    ARG_CHECK(in.x && in.n_cols > 0, "shard %d: regression needs x", s);
+    ARG_CHECK(stk_sweep_supported(1, in.n_cols), "n_cols %d unsupported (1..1024)", in.n_cols);
+    RC(upload(m, in.x, n * in.n_cols, &sd.x));
+    if (family == STK_LOGREG || family == STK_POISSON) {
+      const bool pois = family == STK_POISSON;
+      ARG_CHECK(in.y_int, "shard %d: %s needs y_int", s, pois ? "poisson" : "logreg");
+      // counts handed over as doubles too: say so, do not pick one of the two
+      ARG_CHECK(!pois || (!in.y && !in.sigma), "shard %d: poisson takes its counts in y_int alone; y and sigma must be NULL", s);
+      RC(upload(m, in.y_int, n, &sd.yi));
+      RC(check_y_int(m, s, sd.yi, in.n_rows, pois));
+    } else {   // family_dims knows every family: a new one must say here which y it takes
+      ARG_CHECK(family == STK_LINREG, "shard %d: model family %d has no data layout", s, family);
+      ARG_CHECK(in.y, "shard %d: linreg needs y", s);
+      RC(upload(m, in.y, n, &sd.y));
+    }
+  }
+  m->sh.push_back(sd);
+  return STK_OK;
+}
+
+// Every shard of a synthetic model, generated in place.  beta_dev is the caller's: released by it
+// once the stream has drained.
+static int gen_shards(stk_model* m, DevBuf* beta_dev, const std::vector<double>& beta, int64_t rows, int64_t row_offset,
+                      uint64_t data_seed, double alpha, double noise_sigma) {
+  const int family = m->family, d = m->d;
+  RC(beta_dev->ensure(sizeof(double) * d));
+  if (hipMemcpy(beta_dev->p, beta.data(), sizeof(double) * d, hipMemcpyHostToDevice) != hipSuccess) {
+    stk_set_error("beta upload failed");
+    return STK_E_HIP;
+  }
+  for (int s = 0; s < m->nshards; ++s) {
+    ShardDev sd{};
+    sd.n = rows;
+    sd.d = d;
+    family_dims(family, rows, d, &sd.D, &sd.P);
+    m->bufs.emplace_back();
+    RC(m->bufs.back().ensure(sizeof(double) * rows * d));
+    double* X = m->bufs.back().as<double>();
+    m->bufs.emplace_back();
+    const size_t ybytes = family == STK_LOGREG ? sizeof(int32_t) * rows : sizeof(double) * rows;
+    RC(m->bufs.back().ensure(ybytes));
+    void* y = m->bufs.back().p;
+    m->bytes += (int64_t)(sizeof(double) * rows * d + ybytes);
+    const hipError_t e = stk_launch_gen_shard(X, family == STK_LINREG ? (double*)y : nullptr,
+                                              family == STK_LOGREG ? (int32_t*)y : nullptr, rows, d,
+                                              row_offset + (int64_t)s * rows, data_seed, alpha, beta_dev->as<double>(),
+                                              noise_sigma, family, m->ctx->stream);
+    if (e != hipSuccess) {
+      stk_set_error("gen_shard launch: %s", hipGetErrorString(e));
+      return STK_E_HIP;
+    }
+    sd.x = X;
+    if (family == STK_LOGREG) sd.yi = (const int32_t*)y;
+    else sd.y = (const double*)y;
+    m->sh.push_back(sd);
+  }
+  return STK_OK;
+}
+
+void model_release(stk_model* m) {
+  if (--m->refs > 0) return;
+  stk_ctx* c = m->ctx;
+  hipSetDevice(c->device);
+  hipStreamSynchronize(c->stream);
+  for (auto& b : m->bufs) b.release();
+  m->sh_dev.release();
+  delete m;
+  ctx_release(c);
+}
+
+// ---------------------------------------------------------------- data fingerprint
+// words() of the header: words([family, n_rows, n_cols], 0, 0).
+static uint64_t fp_shard_header(int family, int64_t n_rows, int n_cols) {
+  const uint64_t h[3] = {(uint64_t)family, (uint64_t)n_rows, (uint64_t)(family == STK_SCHOOLS ? 0 : n_cols)};
+  return stk_fp_words_host(h, 3, 8, 0, 0);
+}
+
+// One kernel per data array of the shard, all adding into one zeroed device word; cached.
+int model_fingerprint(stk_model* m, int shard, uint64_t* out) {
+  if (m->fp_ok.size() != (size_t)m->nshards) {
+    m->fp.assign(m->nshards, 0);
+    m->fp_ok.assign(m->nshards, 0);
+  }
+  if (!m->fp_ok[shard]) {
+    stk_ctx* ctx = m->ctx;
+    STK_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const ShardDev& s = m->sh[shard];
+    RC(ctx->scratch[SCR_FP_SUM].ensure(sizeof(unsigned long long)));
+    unsigned long long* sum = ctx->scratch[SCR_FP_SUM].as<unsigned long long>();
+    STK_HIP_CHECK(hipMemsetAsync(sum, 0, sizeof(*sum), st));
+    if (s.x) STK_HIP_CHECK(stk_launch_fp_words(s.x, s.n * s.d, 8, 1, 0, sum, st));
+    if (s.y) STK_HIP_CHECK(stk_launch_fp_words(s.y, s.n, 8, 2, 0, sum, st));
+    if (s.yi) STK_HIP_CHECK(stk_launch_fp_words(s.yi, s.n, 4, 3, 0, sum, st));
+    if (s.sigma) STK_HIP_CHECK(stk_launch_fp_words(s.sigma, s.n, 8, 4, 0, sum, st));
+    unsigned long long v = 0;
+    STK_HIP_CHECK(hipMemcpyAsync(&v, sum, sizeof(v), hipMemcpyDeviceToHost, st));
+    STK_HIP_CHECK(hipStreamSynchronize(st));
+    m->fp[shard] = stk_fp_fmix(fp_shard_header(m->family, s.n, s.d) + (uint64_t)v);
+    m->fp_ok[shard] = 1;
+  }
+  *out = m->fp[shard];
+  return STK_OK;
+}
+
+extern "C" {
+
+int stk_model_create(stk_ctx* ctx, int family, const stk_shard* shards, int nshards, stk_model** out) {
+  ARG_CHECK(ctx && shards && out && nshards > 0, "stk_model_create: bad arguments");
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  stk_model* m = model_new(ctx, family, nshards, family == STK_SCHOOLS ? 0 : shards[0].n_cols);
+  int rc = STK_OK;
+  for (int s = 0; s < nshards && rc == STK_OK; ++s) rc = upload_shard(m, s, shards[s]);
+  return model_finish(m, rc, out);
+}
+
+int stk_gen_beta(uint64_t seed, int32_t d, double* beta) {
+  ARG_CHECK(beta && d > 0, "stk_gen_beta: bad arguments");
+  const double s = 1.0 / sqrt((double)d);
+  for (int j = 0; j < d; ++j) beta[j] = normal_at(seed, (uint32_t)(j >> 1) & ~0u, 0u, 0u, (uint32_t)(j & 1), TAG_BETA) * s;
+  return STK_OK;
+}
+
+int stk_model_create_synthetic(stk_ctx* ctx, int family, int nshards, int64_t rows_per_shard, int64_t row_offset,
+                               int32_t n_cols, uint64_t data_seed, double alpha, const double* beta,
+                               double noise_sigma, stk_model** out) {
+  ARG_CHECK(ctx && out && nshards > 0 && rows_per_shard > 0 && n_cols > 0, "stk_model_create_synthetic: bad arguments");
+  ARG_CHECK(family == STK_LOGREG || family == STK_LINREG,
+            "synthetic shards exist for linreg/logreg only, not for the %s family (%d): the generator draws nothing "
+            "else, build such shards from host rows with stk_model_create", family_name(family), family);
+  ARG_CHECK(stk_sweep_supported(1, n_cols), "n_cols %d unsupported (1..1024)", n_cols);
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  std::vector<double> b(n_cols);
+  if (beta) memcpy(b.data(), beta, sizeof(double) * n_cols);
+  else stk_gen_beta(data_seed, n_cols, b.data());
+  stk_model* m = model_new(ctx, family, nshards, n_cols);
+  DevBuf beta_dev;
+  const int rc = model_finish(m, gen_shards(m, &beta_dev, b, rows_per_shard, row_offset, data_seed, alpha, noise_sigma), out);
+  beta_dev.release();
+  return rc;
+}
+
+int stk_model_destroy(stk_model* m) {
+  if (m) model_release(m);
+  return STK_OK;
+}
+
+int stk_model_info(const stk_model* m, int shard, int32_t* D, int32_t* P, int64_t* n_rows) {
+  ARG_CHECK(m && shard >= 0 && shard < m->nshards, "stk_model_info: bad shard");
+  if (D) *D = m->sh[shard].D;
+  if (P) *P = m->sh[shard].P;
+  if (n_rows) *n_rows = m->sh[shard].n;
+  return STK_OK;
+}
+
+int stk_model_device_bytes(const stk_model* m, int64_t* bytes) {
+  ARG_CHECK(m && bytes, "bad arguments");
+  *bytes = m->bytes;
+  return STK_OK;
+}
+
+int stk_model_copy_data(stk_model* m, int shard, double* x, double* y, int32_t* y_int) {
+  ARG_CHECK(m && shard >= 0 && shard < m->nshards, "stk_model_copy_data: bad shard");
+  STK_HIP_CHECK(hipSetDevice(m->ctx->device));
+  const ShardDev& s = m->sh[shard];
+  hipStream_t st = m->ctx->stream;
+  if (x && s.x) STK_HIP_CHECK(hipMemcpyAsync(x, s.x, sizeof(double) * s.n * s.d, hipMemcpyDefault, st));
+  if (y && s.y) STK_HIP_CHECK(hipMemcpyAsync(y, s.y, sizeof(double) * s.n, hipMemcpyDefault, st));
+  if (y_int && s.yi) STK_HIP_CHECK(hipMemcpyAsync(y_int, s.yi, sizeof(int32_t) * s.n, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
+int stk_model_set_prior(stk_model* m, double alpha_scale, double beta_scale) {
+  ARG_CHECK(m, "stk_model_set_prior: NULL model");
+  ARG_CHECK(is_regression(m->family), "priors apply to the regression families");
+  ARG_CHECK(alpha_scale >= 0.0 && beta_scale >= 0.0, "prior scales must be >= 0 (0 or inf: flat)");
+  auto prec = [](double sc) { return (sc == 0.0 || std::isinf(sc)) ? 0.0 : 1.0 / (sc * sc); };
+  for (auto& sd : m->sh) {
+    sd.pa = prec(alpha_scale);
+    sd.pb = prec(beta_scale);
+  }
+  STK_HIP_CHECK(hipSetDevice(m->ctx->device));
+  STK_HIP_CHECK(hipMemcpy(m->sh_dev.p, m->sh.data(), sizeof(ShardDev) * m->sh.size(), hipMemcpyHostToDevice));
+  return STK_OK;
+}
+
+int stk_model_shard_arrays(const stk_model* m, int shard, stk_shard* out) {
+  ARG_CHECK(m && out && shard >= 0 && shard < m->nshards, "stk_model_shard_arrays: bad arguments");
+  const ShardDev& s = m->sh[shard];
+  *out = stk_shard{s.n, s.d, s.x, s.y, s.yi, s.sigma};
+  return STK_OK;
+}
+
+int stk_model_fingerprint(stk_model* m, int shard, uint64_t* out) {
+  ARG_CHECK(m && out && shard >= 0 && shard < m->nshards, "stk_model_fingerprint: bad arguments");
+  return model_fingerprint(m, shard, out);
+}
+
+int stk_fingerprint_words(stk_ctx* ctx, const void* buf, int64_t count, int32_t word_bytes, int32_t tag,
+                          uint64_t index0, uint64_t* sum) {
+  ARG_CHECK(sum, "stk_fingerprint_words: sum is NULL");
+  ARG_CHECK(word_bytes == 4 || word_bytes == 8, "stk_fingerprint_words: word_bytes must be 4 or 8, got %d", word_bytes);
+  ARG_CHECK(tag >= 0 && tag <= 4, "stk_fingerprint_words: tag must be in 0..4, got %d", tag);
+  ARG_CHECK(count >= 0, "stk_fingerprint_words: count must be >= 0");
+  ARG_CHECK(buf || count == 0, "stk_fingerprint_words: buf is NULL");
+  ARG_CHECK(((uintptr_t)buf & (uintptr_t)(word_bytes - 1)) == 0, "stk_fingerprint_words: buf is not aligned to %d bytes",
+            word_bytes);
+  *sum = 0;
+  if (count == 0) return STK_OK;
+  if (!ctx) {   // the caller asked for the host twin: no device is touched
+    *sum = stk_fp_words_host(buf, count, word_bytes, tag, index0);
+    return STK_OK;
+  }
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  RC(ctx->scratch[SCR_FP_SUM].ensure(sizeof(unsigned long long)));
+  unsigned long long* acc = ctx->scratch[SCR_FP_SUM].as<unsigned long long>();
+  STK_HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(*acc), st));
+  if (is_device_ptr(buf, ctx->device)) {
+    STK_HIP_CHECK(stk_launch_fp_words(buf, count, word_bytes, tag, index0, acc, st));
+  } else {   // host (or another device's) memory: staged in pieces, words() is additive over index ranges
+    const int64_t piece = ((int64_t)64 << 20) / word_bytes;
+    DevBuf& stage = ctx->scratch[SCR_FP_STAGE];
+    RC(stage.ensure((size_t)std::min(count, piece) * word_bytes));
+    const char* src = static_cast<const char*>(buf);
+    for (int64_t i0 = 0; i0 < count; i0 += piece) {
+      const int64_t n = std::min(piece, count - i0);
+      STK_HIP_CHECK(hipMemcpyAsync(stage.p, src + i0 * word_bytes, (size_t)n * word_bytes, hipMemcpyDefault, st));
+      STK_HIP_CHECK(stk_launch_fp_words(stage.p, n, word_bytes, tag, index0 + (uint64_t)i0, acc, st));
+    }
+  }
+  unsigned long long v = 0;
+  STK_HIP_CHECK(hipMemcpyAsync(&v, acc, sizeof(v), hipMemcpyDeviceToHost, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  *sum = v;
+  return STK_OK;
+}
+
+int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
+  ARG_CHECK(sh && out, "stk_shard_fingerprint_host: bad arguments");
+  ARG_CHECK(family == STK_SCHOOLS || family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON,
+            "unknown model family %d", family);
+  ARG_CHECK(sh->n_rows > 0, "stk_shard_fingerprint_host: n_rows must be positive");
+  uint64_t acc = fp_shard_header(family, sh->n_rows, sh->n_cols);
+  if (family == STK_SCHOOLS) {
+    ARG_CHECK(sh->y && sh->sigma, "stk_shard_fingerprint_host: schools needs y and sigma");
+    acc += stk_fp_words_host(sh->y, sh->n_rows, 8, 2, 0) + stk_fp_words_host(sh->sigma, sh->n_rows, 8, 4, 0);
+  } else {
+    ARG_CHECK(sh->x && sh->n_cols > 0, "stk_shard_fingerprint_host: regression needs x");
+    acc += stk_fp_words_host(sh->x, sh->n_rows * sh->n_cols, 8, 1, 0);
+    if (family == STK_LOGREG || family == STK_POISSON) {
+      ARG_CHECK(sh->y_int, "stk_shard_fingerprint_host: %s needs y_int", family == STK_POISSON ? "poisson" : "logreg");
+      ARG_CHECK(family != STK_POISSON || (!sh->y && !sh->sigma),
+                "stk_shard_fingerprint_host: poisson takes its counts in y_int alone; y and sigma must be NULL");
+      acc += stk_fp_words_host(sh->y_int, sh->n_rows, 4, 3, 0);
+    } else {
+      ARG_CHECK(sh->y, "stk_shard_fingerprint_host: linreg needs y");
+      acc += stk_fp_words_host(sh->y, sh->n_rows, 8, 2, 0);
+    }
+  }
+  *out = stk_fp_fmix(acc);
+  return STK_OK;
+}
+
+}  // extern "C"

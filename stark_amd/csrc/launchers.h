@@ -1,5 +1,5 @@
 // Host-side launchers and helpers that cross translation units of libstark_hip.so: declared once
-// here, included by capi.hip (the caller) and by every file that defines one, so a signature
+// here, included by the capi*.hip units (the callers) and by every file that defines one, so a signature
 // that drifts is a compile error instead of a second overload that links and runs.
 #pragma once
 #include "common.h"
