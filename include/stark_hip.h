@@ -340,6 +340,45 @@ STK_API int stk_log_predictive(stk_model* m, int shard, const double* q, int32_t
  * 64 lanes plus 64 per-draw scalars), out[5] bytes of chunk-partial workspace per shard. */
 STK_API int stk_predictive_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]);
 
+/* ---- PSIS-LOO sweep (regression families, 1 <= d <= 128, 1 <= S <= 1024): for every ROW, Pareto-smoothed
+ * importance-sampling leave-one-out over S draws, with the Pareto shape khat of the row's importance
+ * ratios as its diagnostic ----
+ * ll_is is stk_log_predictive's normalised pointwise log likelihood of row i at draw s.  For one row:
+ *   1. lr_s = -ll_s, shifted: lr <- lr - max_s lr.
+ *   2. Tail length M = ceil(min(0.2 S, 3 sqrt S)).
+ *   3. M < 5 (S <= 20): no smoothing, khat = +inf.
+ *   4. Else sort lr ascending; the tail is the M largest, t_1 <= ... <= t_M; cut is the (S - M)-th
+ *      smallest, the largest value outside the tail; unless t_M - t_1 > 0: no smoothing, khat = +inf.
+ *   5. Exceedances x_j = exp(t_j) - exp(cut).
+ *   6. The Zhang-Stephens fit of the generalised Pareto distribution with the loo package's prior:
+ *      N = M, Mg = 30 + floor(sqrt N), xstar = x[floor(N / 4 + 0.5)] (1-based); for j = 1 .. Mg
+ *        theta_j = 1 / x_N + (1 - sqrt(Mg / (j - 0.5))) / 3 / xstar,   k_j = mean_i log1p(-theta_j x_i),
+ *        l_j = N (log(-theta_j / k_j) - k_j - 1),   w_j = 1 / sum_i exp(l_i - l_j) (an overflow gives 0);
+ *      theta = sum_j theta_j w_j, k = mean_i log1p(-theta x_i), sigma = -k / theta,
+ *      khat = (k N + 5) / (N + 10).
+ *   7. If khat is finite: t_j <- log(sigma expm1(-khat log1p(-p_j)) / khat + exp(cut)), p_j = (j - 0.5) / M.
+ *   8. Truncate: lw = min(lr, 0).            9. Normalise: lw <- lw - logsumexp(lw).
+ *  10. elpd_loo_i = logsumexp_s(ll_s + lw_s), ll paired with lw through the sort.
+ *  11. lppd_i = logsumexp_s ll_s - log S,   p_loo_i = lppd_i - elpd_loo_i.
+ * (r_eff = 1: no relative-efficiency correction of the tail length; no moment matching.)
+ * If any ll_is of a row is not finite, the row's elpd_loo, p_loo and khat are NaN; lppd_i stays what IEEE
+ * arithmetic gives (a -inf draw adds 0, a NaN draw gives NaN).  Never a finite wrong number.
+ * rows: (elpd_loo, khat, lppd, p_loo) per row.  Per shard, eight doubles of totals: [0] n, [1] sum lppd,
+ * [2] sum p_loo, [3] sum elpd_loo, [4] sum elpd_loo^2, [5] the number of rows with khat > 0.5, [6] with
+ * khat > 0.7 (+inf counts in both, NaN in neither), [7] the number of rows whose elpd_loo, lppd or p_loo is
+ * not finite or whose khat is NaN.  The totals are plain sums: a non-finite row makes its sums non-finite.
+ * q, shard, rows and totals follow stk_log_predictive's contract, word for word: shard == -1 is one grouped
+ * launch, rows may be host or device memory, either output may be NULL but not both, a row's bits depend
+ * only on (x_i, y_i) and the draws, the totals not on how many shards share the call nor on the device.
+ * S <= 1024: a 16-row tile's log ratios are kept in LDS (16 x 1024 doubles = 128 KB), never in HBM.
+ * STK_E_ARG (the message names the family, or the offending value as d = ... / S = ...) for 8 schools,
+ * d > 128, S < 1, S > 1024, a NULL q and both outputs NULL. */
+STK_API int stk_loo(stk_model* m, int shard, const double* q, int32_t S, double* rows, double* totals);
+/* host only: out[0] rows per tile, out[1] chunks per shard, out[2] waves per block, out[3] dynamic LDS
+ * bytes (a function of d and S), out[4] bytes of the draw image (stk_predictive_launch_info's), out[5]
+ * bytes of chunk-partial workspace per shard. */
+STK_API int stk_loo_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]);
+
 /* ---- sampling: stark/stark.py:43-56 for every shard of the model ---- */
 STK_API int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out);
 /* Advance every chain until it has completed `target_iter` transitions (warmup counted),

@@ -121,6 +121,8 @@ SIGNATURES = [
     ("stk_consensus_weighted", ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     ("stk_log_predictive", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _vp, _vp]),
     ("stk_predictive_launch_info", ctypes.c_int, [_i64, _i32, _i32, _vp]),
+    ("stk_loo", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _vp, _vp]),
+    ("stk_loo_launch_info", ctypes.c_int, [_i64, _i32, _i32, _vp]),
 ]
 
 # int (*stk_allreduce_fn)(void* user, double* block, int64_t count, void* stream)

@@ -1,5 +1,5 @@
 // C ABI of libstark_hip.so: the chain plan, the lp / grad parity hooks, the host-only launch-info
-// calls, the analytic Hessian and the pointwise log-predictive sweep.
+// calls, the analytic Hessian, the pointwise log-predictive sweep and the PSIS-LOO sweep.
 #include "capi_internal.h"
 
 // The chain counts that are ONE sweep launch in the two single-launch parity hooks (stk_log_density_grad's
@@ -303,6 +303,69 @@ int stk_log_predictive(stk_model* m, int shard, const double* q, int32_t S, doub
   STK_HIP_CHECK(stk_launch_predictive_prep(m->family, m->d, D, S, qb, img, st));
   STK_HIP_CHECK(stk_launch_predictive(m->family, m->sh_dev.as<ShardDev>(), shard0, nsh, m->d, Gs, S, img, partial, rb,
                                       offb, tb, st));
+  if (totals) STK_HIP_CHECK(hipMemcpyAsync(totals, tb, sizeof(double) * 8 * nsh, hipMemcpyDefault, st));
+  if (staged) STK_HIP_CHECK(hipMemcpyAsync(rows, rb, sizeof(double) * 4 * (size_t)nrows, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
+// ---------------------------------------------------------------- PSIS-LOO sweep (loo.hip)
+// The sweep's launch shape over a shard of n_rows x d against S draws (host only: no device).
+// out: rows per tile, chunks per shard, waves per block, LDS bytes, draw-image bytes, chunk-partial
+// workspace bytes per shard.
+int stk_loo_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_loo_launch_info: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(stk_loo_supported(d), "the PSIS-LOO sweep covers 1 <= d <= 128 covariates, not d = %d", d);
+  ARG_CHECK(S >= 1, "the PSIS-LOO sweep needs S >= 1 draws, not S = %d", S);
+  ARG_CHECK(S <= stk_loo_max_draws(), "the PSIS-LOO sweep keeps a row tile's draws in LDS: at most %d, not S = %d",
+            stk_loo_max_draws(), S);
+  const int64_t v[6] = {stk_loo_rows_per_tile(), stk_loo_chunks(n_rows), stk_loo_waves(S), (int64_t)stk_loo_lds_bytes(d, S),
+                        (int64_t)stk_predictive_image_bytes(d, S), (int64_t)stk_loo_ws_bytes(n_rows)};
+  memcpy(out, v, sizeof(v));
+  return STK_OK;
+}
+
+// stk_log_predictive's contract: the same S draws against one shard or (shard == -1) every shard, one
+// preparation launch (the log-predictive sweep's draw image), one sweep launch and one reduce launch.
+int stk_loo(stk_model* m, int shard, const double* q, int32_t S, double* rows, double* totals) {
+  ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_loo: bad model or shard");
+  ARG_CHECK(is_regression(m->family), "stk_loo: no PSIS-LOO sweep for the %s family (regressions only)", family_name(m->family));
+  ARG_CHECK(stk_loo_supported(m->d), "stk_loo: the PSIS-LOO sweep covers 1 <= d <= 128 covariates, not d = %d (%s family)",
+            m->d, family_name(m->family));
+  ARG_CHECK(S >= 1, "stk_loo: S = %d draws; the %s family at d = %d needs S >= 1", S, family_name(m->family), m->d);
+  ARG_CHECK(S <= stk_loo_max_draws(),
+            "stk_loo: S = %d draws; a row tile's draws are kept in LDS, at most %d (%s family, d = %d): pass a subset",
+            S, stk_loo_max_draws(), family_name(m->family), m->d);
+  ARG_CHECK(q, "stk_loo: q is NULL (%s family, d = %d)", family_name(m->family), m->d);
+  ARG_CHECK(rows || totals, "stk_loo: rows and totals are both NULL (%s family, d = %d)", family_name(m->family), m->d);
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int D = m->Dmax;
+  const ShardRange r = shard_range(m, shard, stk_loo_chunks);
+  const int shard0 = r.shard0, nsh = r.nsh, Gs = r.Gs;
+  std::vector<int64_t> off(nsh);
+  int64_t nrows = 0;
+  for (int s = 0; s < nsh; ++s) {
+    off[s] = nrows;
+    nrows += m->sh[shard0 + s].n;
+  }
+  const size_t qn = (size_t)S * D, img_bytes = stk_predictive_image_bytes(m->d, S);
+  RC(ctx->scratch[SCR_LOO_IMG].ensure(img_bytes + sizeof(double) * qn));
+  RC(ctx->scratch[SCR_LOO_PARTIAL].ensure(sizeof(double) * 8 * ((size_t)nsh * Gs + nsh) + sizeof(int64_t) * nsh));
+  double* img = ctx->scratch[SCR_LOO_IMG].as<double>();
+  double* qb = img + img_bytes / sizeof(double);
+  double* partial = ctx->scratch[SCR_LOO_PARTIAL].as<double>();
+  double* tb = partial + (size_t)nsh * Gs * 8;
+  int64_t* offb = reinterpret_cast<int64_t*>(tb + (size_t)nsh * 8);
+  const bool staged = rows && !is_device_ptr(rows, ctx->device);
+  if (staged) RC(ctx->scratch[SCR_LOO_ROWS].ensure(sizeof(double) * 4 * (size_t)nrows));
+  double* rb = staged ? ctx->scratch[SCR_LOO_ROWS].as<double>() : rows;
+  STK_HIP_CHECK(hipMemcpyAsync(qb, q, sizeof(double) * qn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipMemcpyAsync(offb, off.data(), sizeof(int64_t) * nsh, hipMemcpyHostToDevice, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));   // off is a local
+  STK_HIP_CHECK(stk_launch_predictive_prep(m->family, m->d, D, S, qb, img, st));
+  STK_HIP_CHECK(stk_launch_loo(m->family, m->sh_dev.as<ShardDev>(), shard0, nsh, m->d, Gs, S, img, partial, rb, offb, tb, st));
   if (totals) STK_HIP_CHECK(hipMemcpyAsync(totals, tb, sizeof(double) * 8 * nsh, hipMemcpyDefault, st));
   if (staged) STK_HIP_CHECK(hipMemcpyAsync(rows, rb, sizeof(double) * 4 * (size_t)nrows, hipMemcpyDefault, st));
   STK_HIP_CHECK(hipStreamSynchronize(st));

@@ -8,6 +8,11 @@ namespace stk {
 
 struct SweepArgs;   // sweep_common.h (device side)
 
+// The draw image of k_predictive_prep (predictive.hip), which loo.hip reads too: k-steps per draw tile,
+// and doubles per draw tile: the k-steps, 64 per-draw scalars, padded to a whole number of block-wide copies
+__host__ __device__ constexpr int pred_kf(int d) { return (d + 3) / 4; }
+__host__ __device__ constexpr int pred_slab(int kf) { return (kf * 64 + 64 + 255) / 256 * 256; }
+
 // Which regression sweep runs; the numbers are those of tests/golden/sweep_launch.json.
 enum SweepKind : int {
   SWEEP_NONE = 0,     // no sweep: the chunk bytes do not fit a buffer descriptor, or (C, d) has no kernel
@@ -105,6 +110,19 @@ hipError_t stk_launch_predictive_prep(int family, int d, int D, int S, const dou
 hipError_t stk_launch_predictive(int family, const stk::ShardDev* shards, int shard0, int nsh, int d, int Gs, int S,
                                  const double* img, double* partial, double* rows, const int64_t* rowoff,
                                  double* totals, hipStream_t st);
+
+// ---- loo.hip (regressions, d <= 128, S <= 1024): the PSIS-LOO sweep's geometry and launch; the draw
+// image is stk_launch_predictive_prep's
+bool stk_loo_supported(int d);
+int stk_loo_max_draws();
+int stk_loo_chunks(int64_t n);
+int stk_loo_rows_per_tile();
+int stk_loo_waves(int S);
+size_t stk_loo_lds_bytes(int d, int S);
+size_t stk_loo_ws_bytes(int64_t n);                // chunk-partial workspace of one shard
+hipError_t stk_launch_loo(int family, const stk::ShardDev* shards, int shard0, int nsh, int d, int Gs, int S,
+                          const double* img, double* partial, double* rows, const int64_t* rowoff, double* totals,
+                          hipStream_t st);
 
 // ---- nuts.hip (and its nuts_fused4.hip / nuts_dense.hip translation units)
 int stk_nch_for(int Dmax);

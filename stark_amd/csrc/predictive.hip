@@ -52,9 +52,6 @@ constexpr int PD_W = 4;           // waves per block
 constexpr int PD_GPC = 4;         // 64-row groups per chunk before the chunk count saturates
 constexpr int PD_GMAX = 256;      // chunks per shard at most
 
-__host__ __device__ constexpr int pred_kf(int d) { return (d + 3) / 4; }
-// doubles per draw tile: the k-steps, 64 per-draw scalars, padded to a whole number of block-wide copies
-__host__ __device__ constexpr int pred_slab(int kf) { return (kf * 64 + 64 + 255) / 256 * 256; }
 __host__ __device__ inline int pred_chunks(int64_t n) {
   const int64_t ng = (n + PD_R * PD_W - 1) / (PD_R * PD_W), g = (ng + PD_GPC - 1) / PD_GPC;
   return (int)(g < 1 ? 1 : (g > PD_GMAX ? PD_GMAX : g));

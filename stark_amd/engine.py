@@ -465,6 +465,30 @@ class Model:
             return tot
         return tot, {k: np.ascontiguousarray(out[:, j]) for j, k in enumerate(("lppd", "mean", "var", "mu"))}
 
+    def loo(self, q, shard=None, rows=False):
+        """PSIS-LOO of every row over the S <= 1024 draws ``q`` [S, D] (the layout of
+        ``log_predictive``), and the per-shard totals (stk_loo: the PSIS-LOO sweep; regression families
+        with d <= 128).  shard: an index (totals [8]) or None for every shard in one grouped launch
+        (totals [nshards, 8]); ``loo(totals)`` turns either into the summary.  rows=True also returns a
+        dict of per-row arrays ``elpd_loo``, ``khat``, ``lppd``, ``p_loo`` (shard-major when shard is
+        None).  khat is +inf where a row is not smoothed (S <= 20, or a constant tail); a row with a
+        non-finite log likelihood has NaN elpd_loo, p_loo and khat and is counted in totals[..., 7]."""
+        every = shard is None
+        q = np.ascontiguousarray(np.atleast_2d(q), np.float64)
+        D = self.D[0 if every else shard]
+        if q.ndim != 2 or q.shape[1] != D:
+            raise ValueError(f"q must be [S, D = {D}], got {q.shape}")
+        ns = self.nshards if every else 1
+        n = sum(self.n_rows) if every else self.n_rows[shard]
+        tot = np.empty((ns, 8))
+        out = np.empty((n, 4)) if rows else None
+        check(_lib.load().stk_loo(self._h, -1 if every else int(shard), q.ctypes.data, q.shape[0], _ptr(out),
+                                  tot.ctypes.data))
+        tot = tot if every else tot[0]
+        if not rows:
+            return tot
+        return tot, {k: np.ascontiguousarray(out[:, j]) for j, k in enumerate(("elpd_loo", "khat", "lppd", "p_loo"))}
+
     def set_prior(self, alpha=None, beta=None):
         """normal(0, s) priors on alpha and beta (regressions); None or 0: flat."""
         check(_lib.load().stk_model_set_prior(self._h, float(alpha or 0.0), float(beta or 0.0)))
@@ -758,6 +782,36 @@ def waic(totals) -> dict:
         se = float(np.sqrt(n / (n - 1.0) * max(v, 0.0))) if np.isfinite(v) else float("nan")
     return {"n": int(n), "lppd": lppd, "p_waic": p, "elpd_waic": e, "se": se, "waic": -2.0 * e,
             "n_high_var": int(acc[5]), "n_non_finite": int(acc[6])}
+
+
+def loo_launch(n_rows: int, n_cols: int, S: int) -> dict:
+    """The launch shape of the PSIS-LOO sweep over a shard of ``n_rows`` x ``n_cols`` against ``S`` draws
+    (stk_loo_launch_info): rows per tile ``T``, chunks per shard ``G``, ``waves`` per block,
+    ``lds_bytes`` (sized from S), ``image_bytes`` of the draw image and ``ws_bytes_per_shard``.
+    Raises STK_E_ARG past 128 covariates or 1024 draws.  Host only."""
+    out = np.zeros(6, np.int64)
+    check(_lib.load().stk_loo_launch_info(int(n_rows), int(n_cols), int(S), out.ctypes.data))
+    return dict(zip(("T", "G", "waves", "lds_bytes", "image_bytes", "ws_bytes_per_shard"), (int(v) for v in out)))
+
+
+def loo(totals) -> dict:
+    """PSIS-LOO from the ``[..., 8]`` totals of ``Model.loo``, summed over shards in the order given:
+    ``n``, ``lppd``, ``p_loo``, ``elpd_loo``, its standard error ``se`` (``waic``'s formula),
+    ``looic`` = -2 elpd_loo, ``n_k_gt_0.5`` and ``n_k_gt_0.7`` (rows whose Pareto khat is above the two
+    usual thresholds: above 0.7 the row's estimate is unreliable) and ``n_non_finite``."""
+    t = np.asarray(totals, np.float64)
+    if t.shape[-1] != 8:
+        raise ValueError(f"totals must be [..., 8], got shape {t.shape}")
+    acc = np.zeros(8)
+    for row in t.reshape(-1, 8):         # shard order
+        acc = acc + row
+    n, lppd, p, e, e2 = (float(v) for v in acc[:5])
+    se = 0.0
+    if n > 1:
+        v = e2 - e * e / n               # rounding can leave a tiny negative; a non-finite row gives NaN
+        se = float(np.sqrt(n / (n - 1.0) * max(v, 0.0))) if np.isfinite(v) else float("nan")
+    return {"n": int(n), "lppd": lppd, "p_loo": p, "elpd_loo": e, "se": se, "looic": -2.0 * e,
+            "n_k_gt_0.5": int(acc[5]), "n_k_gt_0.7": int(acc[6]), "n_non_finite": int(acc[7])}
 
 
 def fitted_mean(ctx, family, x, q):

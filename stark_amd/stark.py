@@ -432,6 +432,47 @@ class Stark:
         out["partition_totals"] = totals
         return out
 
+    LOO_MAX_DRAWS = 1024      # stk_loo keeps a row tile's S log ratios in LDS
+
+    def _partition_loo_totals(self, datas, q):
+        """``_partition_totals`` for the PSIS-LOO sweep (engine.Model.loo, no per-row output)."""
+        shards = [frontend.pack_data(self.family, d) for d in datas]
+        model = engine.Model(engine.default_context(), self.family, shards)
+        try:
+            return list(model.loo(q))
+        finally:
+            model.close()
+
+    def loo(self, samples):
+        """PSIS-LOO of a P x S matrix of draws against EVERY partition's rows, exchanged exactly as
+        ``waic`` does it: every rank scores its own partitions in one grouped launch, the [1, 8] totals
+        are all-gathered and summed in partition order, so every rank returns the same bits on 1 or N
+        ranks.  Returns ``engine.loo``'s dict (n, lppd, p_loo, elpd_loo, se, looic, n_k_gt_0.5,
+        n_k_gt_0.7, n_non_finite) plus ``partition_totals`` [n_partitions, 8].  Regression families
+        with at most 128 covariates and at most 1024 draws: more columns raise ValueError."""
+        if self.family is None:
+            raise RuntimeError("call setStanModel() first")
+        if self.family == "schools":
+            unconstrain_draws(self.family, samples)       # raises: names the family
+        S = np.asarray(samples).shape[-1] if np.ndim(samples) == 2 else 0
+        if S > self.LOO_MAX_DRAWS:
+            raise ValueError(f"samples has S = {S} draws; the PSIS-LOO sweep keeps every row's draws in LDS and covers "
+                             f"at most {self.LOO_MAX_DRAWS}: pass a column subset (e.g. samples[:, ::{-(-S // self.LOO_MAX_DRAWS)}])")
+        parts = _rdd.partitions_of(self.rdd)
+        rank, ws = dist.world()
+        mine = dist.local_partitions(len(parts), rank, ws)
+        datas = [self.prepare_data_callback(list(parts[p])) for p in mine]
+        q = unconstrain_draws(self.family, samples, n_cols=int(datas[0]["K"]) if datas else None)
+        local = {}
+        if datas:
+            tots = self._partition_loo_totals(datas, q)
+            local = {p: np.asarray(t, np.float64).reshape(1, 8) for p, t in zip(mine, tots)}
+        totals = np.concatenate([np.asarray(t, np.float64).reshape(1, 8)
+                                 for t in dist.all_gather_partitions(local, len(parts))])
+        out = engine.loo(totals)
+        out["partition_totals"] = totals
+        return out
+
     def distribute(self, n=2, reference_union=False, **kwargs):
         """stark/stark.py:73-85: naive parallel runs over the full data, draws stacked with
         ``concatenate_samples`` (row blocks of P x S)."""
