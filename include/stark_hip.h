@@ -36,6 +36,9 @@
  *                               gradient (2 D gradient points per Hessian)
  *   stk_log_predictive /        per-row statistics over S draws (lppd, WAIC penalty, fitted mean) and their
  *   stk_predictive_launch_info  per-shard totals.  No reference counterpart
+ *   stk_log_density_draws /     the log density of a shard at each of S draws in one pass over its rows, and the
+ *   stk_logdens_launch_info /   Gaussian proposal draws of a Laplace fit: together the importance ratios of
+ *   stk_laplace_draws           Laplace sampling (stark_amd.engine.laplace_sample).  No reference counterpart
  *
  * Conventions
  *   - Return 0 on success, a negative STK_E_* code on failure; stk_last_error() gives a
@@ -378,6 +381,34 @@ STK_API int stk_loo(stk_model* m, int shard, const double* q, int32_t S, double*
  * bytes (a function of d and S), out[4] bytes of the draw image (stk_predictive_launch_info's), out[5]
  * bytes of chunk-partial workspace per shard. */
 STK_API int stk_loo_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]);
+
+/* ---- per-draw log density and the Laplace proposal (regression families, d <= 128) ----
+ * stk_log_density_draws: lp[s] is, by definition, the lp stk_log_density_grad returns at q[s] -- Stan's
+ * log_prob (propto, with the Jacobian of sigma = e^u and the stk_model_set_prior terms) -- for S draws in ONE
+ * pass over the shard's rows, forward only (no gradient).  q is [S][D] unconstrained, the layout of
+ * stk_log_predictive; any S >= 1; host or device memory for q and lp.  shard == -1 runs every shard in one
+ * grouped launch against the same draws and fills lp[nshards][S]; else lp[S].
+ * The launch geometry is a function of n (and d) only, never of S, and every sum runs in an order fixed by
+ * them: lp of a draw depends on that draw and the shard alone, bit for bit -- the same at any position in
+ * q, with any companions, at any S, and in the grouped launch as in a single-shard one.  A non-finite draw
+ * (or one whose Poisson mean overflows) has a non-finite lp; the other draws of the call are untouched.
+ * The likelihood is the sweeps' propto one (no lgamma(y + 1) for poisson_log, no log(2 pi) / 2 for normal).
+ * STK_E_ARG (the message names the family, or the offending value as d = ... / S = ...) for 8 schools,
+ * d > 128, S < 1 and a NULL q or lp. */
+STK_API int stk_log_density_draws(stk_model* m, int shard, const double* q, int32_t S, double* lp);
+/* host only: out[0] rows per tile, out[1] chunks per shard, out[2] waves per block, out[3] dynamic LDS
+ * bytes, out[4] bytes of the draw image (stk_predictive_launch_info's), out[5] bytes of chunk-partial
+ * workspace per shard.  out[0..3] do not depend on S. */
+STK_API int stk_logdens_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]);
+/* S draws of N(mode, F F^T): q_out[s] = mode + F xi_s, F any D x D row-major matrix (the Python layer passes
+ * L^-T of the Cholesky factorisation -H = L L^T of a Laplace fit), xi_{s,j} = the Box-Muller normal of the
+ * Philox counter {stream, s, j / 2, TAG_LAPLACE} under `seed` (csrc/philox.h), and log_q_out[s] =
+ * -sum_j xi_{s,j}^2 / 2 in index order: the log proposal density without its constant.  stream is the
+ * shard's GLOBAL index, so a shard draws the same proposal on any rank and next to any other shards; draw s
+ * does not depend on S.  1 <= D <= 130, S >= 1; host or device memory for every pointer.  STK_E_ARG
+ * (naming D = ... / S = ...) otherwise. */
+STK_API int stk_laplace_draws(stk_ctx* ctx, const double* mode, const double* factor, int32_t D, int32_t S,
+                              uint64_t seed, uint32_t stream, double* q_out, double* log_q_out);
 
 /* ---- sampling: stark/stark.py:43-56 for every shard of the model ---- */
 STK_API int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out);

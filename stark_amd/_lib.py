@@ -123,6 +123,9 @@ SIGNATURES = [
     ("stk_predictive_launch_info", ctypes.c_int, [_i64, _i32, _i32, _vp]),
     ("stk_loo", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _vp, _vp]),
     ("stk_loo_launch_info", ctypes.c_int, [_i64, _i32, _i32, _vp]),
+    ("stk_log_density_draws", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _vp]),
+    ("stk_logdens_launch_info", ctypes.c_int, [_i64, _i32, _i32, _vp]),
+    ("stk_laplace_draws", ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _u64, ctypes.c_uint32, _vp, _vp]),
 ]
 
 # int (*stk_allreduce_fn)(void* user, double* block, int64_t count, void* stream)

@@ -372,4 +372,76 @@ int stk_loo(stk_model* m, int shard, const double* q, int32_t S, double* rows, d
   return STK_OK;
 }
 
+// ---------------------------------------------------------------- per-draw log-density sweep (logdens.hip)
+// The sweep's launch shape over a shard of n_rows x d against S draws (host only: no device).
+// out: rows per tile, chunks per shard, waves per block, LDS bytes, draw-image bytes, chunk-partial
+// workspace bytes per shard.  Only the last two depend on S.
+int stk_logdens_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_logdens_launch_info: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(stk_logdens_supported(d), "the per-draw log-density sweep covers 1 <= d <= 128 covariates, not d = %d", d);
+  ARG_CHECK(S >= 1, "the per-draw log-density sweep needs S >= 1 draws, not S = %d", S);
+  const int64_t v[6] = {stk_logdens_rows_per_tile(), stk_logdens_chunks(n_rows), stk_logdens_waves(),
+                        (int64_t)stk_logdens_lds_bytes(d), (int64_t)stk_predictive_image_bytes(d, S),
+                        (int64_t)stk_logdens_ws_bytes(n_rows, S)};
+  memcpy(out, v, sizeof(v));
+  return STK_OK;
+}
+
+// The same S draws against one shard or (shard == -1) every shard: one preparation launch (the
+// log-predictive sweep's draw image), one sweep launch and one reduce launch for all of them.
+int stk_log_density_draws(stk_model* m, int shard, const double* q, int32_t S, double* lp) {
+  ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_log_density_draws: bad model or shard");
+  ARG_CHECK(is_regression(m->family), "stk_log_density_draws: no per-draw log-density sweep for the %s family (regressions only)",
+            family_name(m->family));
+  ARG_CHECK(stk_logdens_supported(m->d),
+            "stk_log_density_draws: the per-draw log-density sweep covers 1 <= d <= 128 covariates, not d = %d (%s family)",
+            m->d, family_name(m->family));
+  ARG_CHECK(S >= 1, "stk_log_density_draws: S = %d draws; the %s family at d = %d needs S >= 1", S, family_name(m->family),
+            m->d);
+  ARG_CHECK(q && lp, "stk_log_density_draws: q or lp is NULL (%s family, d = %d)", family_name(m->family), m->d);
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int D = m->Dmax;
+  const ShardRange r = shard_range(m, shard, stk_logdens_chunks);
+  const size_t qn = (size_t)S * D, img_bytes = stk_predictive_image_bytes(m->d, S);
+  const size_t Sp = (size_t)16 * stk_predictive_tiles(S), lpn = (size_t)r.nsh * S;
+  RC(ctx->scratch[SCR_LOGDENS_IMG].ensure(img_bytes + sizeof(double) * (qn + lpn)));
+  RC(ctx->scratch[SCR_LOGDENS_PARTIAL].ensure(sizeof(double) * (size_t)r.nsh * r.Gs * Sp));
+  double* img = ctx->scratch[SCR_LOGDENS_IMG].as<double>();
+  double* qb = img + img_bytes / sizeof(double);
+  double* lpb = qb + qn;
+  STK_HIP_CHECK(hipMemcpyAsync(qb, q, sizeof(double) * qn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(stk_launch_predictive_prep(m->family, m->d, D, S, qb, img, st));
+  STK_HIP_CHECK(stk_launch_logdens(m->family, m->sh_dev.as<ShardDev>(), r.shard0, r.nsh, m->d, D, r.Gs, S, img, qb,
+                                   ctx->scratch[SCR_LOGDENS_PARTIAL].as<double>(), lpb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(lp, lpb, sizeof(double) * lpn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
+// ---------------------------------------------------------------- Laplace proposal (logdens.hip)
+int stk_laplace_draws(stk_ctx* ctx, const double* mode, const double* factor, int32_t D, int32_t S, uint64_t seed,
+                      uint32_t stream, double* q_out, double* log_q_out) {
+  ARG_CHECK(ctx && mode && factor && q_out && log_q_out, "stk_laplace_draws: a NULL argument");
+  ARG_CHECK(D >= 1 && D <= stk_laplace_max_dim(), "stk_laplace_draws: D = %d parameters; the generator covers 1 <= D <= %d", D,
+            stk_laplace_max_dim());
+  ARG_CHECK(S >= 1, "stk_laplace_draws: S = %d draws; need S >= 1", S);
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t nD = (size_t)D, qn = (size_t)S * D;
+  RC(ctx->scratch[SCR_LAPLACE].ensure(sizeof(double) * (nD + nD * nD + qn + (size_t)S)));
+  double* mb = ctx->scratch[SCR_LAPLACE].as<double>();
+  double* fb = mb + nD;
+  double* qb = fb + nD * nD;
+  double* lb = qb + qn;
+  STK_HIP_CHECK(hipMemcpyAsync(mb, mode, sizeof(double) * nD, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipMemcpyAsync(fb, factor, sizeof(double) * nD * nD, hipMemcpyDefault, st));
+  STK_HIP_CHECK(stk_launch_laplace_draws(mb, fb, D, S, seed, stream, qb, lb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(q_out, qb, sizeof(double) * qn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipMemcpyAsync(log_q_out, lb, sizeof(double) * (size_t)S, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
 }  // extern "C"

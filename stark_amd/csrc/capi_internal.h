@@ -65,6 +65,8 @@ enum Scratch : int {
   SCR_COMB_F64, SCR_COMB_MAT, SCR_COMB_I32, // combine: draws-sized doubles, P x P matrices, ints
   SCR_PRED_IMG, SCR_PRED_PARTIAL, SCR_PRED_ROWS,   // predictive: draw image, partials, per-row staging
   SCR_LOO_IMG, SCR_LOO_PARTIAL, SCR_LOO_ROWS,      // PSIS-LOO: draw image, partials, per-row staging
+  SCR_LOGDENS_IMG, SCR_LOGDENS_PARTIAL,            // per-draw log density: draw image + draws + lp, partials
+  SCR_LAPLACE,                                     // Laplace proposal: mode, factor, draws, log_q
   SCR_COUNT
 };
 

@@ -124,6 +124,20 @@ hipError_t stk_launch_loo(int family, const stk::ShardDev* shards, int shard0, i
                           const double* img, double* partial, double* rows, const int64_t* rowoff, double* totals,
                           hipStream_t st);
 
+// ---- logdens.hip (regressions, d <= 128, any S): the per-draw log-density sweep's geometry and launch (the
+// draw image is stk_launch_predictive_prep's), and the Laplace proposal generator (D <= stk_laplace_max_dim())
+bool stk_logdens_supported(int d);
+int stk_logdens_chunks(int64_t n);
+int stk_logdens_rows_per_tile();
+int stk_logdens_waves();
+size_t stk_logdens_lds_bytes(int d);
+size_t stk_logdens_ws_bytes(int64_t n, int S);     // chunk-partial workspace of one shard
+hipError_t stk_launch_logdens(int family, const stk::ShardDev* shards, int shard0, int nsh, int d, int D, int Gs, int S,
+                              const double* img, const double* q, double* partial, double* lp, hipStream_t st);
+int stk_laplace_max_dim();
+hipError_t stk_launch_laplace_draws(const double* mode, const double* factor, int D, int S, uint64_t seed,
+                                    uint32_t stream, double* q, double* log_q, hipStream_t st);
+
 // ---- nuts.hip (and its nuts_fused4.hip / nuts_dense.hip translation units)
 int stk_nch_for(int Dmax);
 size_t stk_fused_lds_bytes(const stk::NutsArgs& A, int nch);

@@ -10,6 +10,10 @@
 //   TAG_X     ctr = {row_lo, row_hi,       j/2,               TAG}  synthetic X_ij
 //   TAG_Y     ctr = {row_lo, row_hi,       0,                 TAG}  synthetic y_i noise
 //   TAG_BETA  ctr = {j/2, 0, 0, TAG}                                 synthetic beta_j
+//   TAG_LAPLACE  ctr = {stream, s,      j/2,               TAG}  xi_{s,j} of Laplace proposal draw s (Box-Muller);
+//                                                                 stream = the shard's GLOBAL index
+//   TAG_RESAMPLE ctr = {stream, k,      0,                 TAG}  U_k of stratified resampling: the first output
+//                                                                 word (host side only, engine.resample)
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -19,7 +23,8 @@
 namespace stk {
 
 enum : uint32_t { TAG_INIT = 0x1, TAG_MOM = 0x2, TAG_UNI = 0x3, TAG_SSMOM = 0x4, TAG_JIT = 0x5,
-                  TAG_X = 0x10, TAG_Y = 0x11, TAG_BETA = 0x12 };
+                  TAG_X = 0x10, TAG_Y = 0x11, TAG_BETA = 0x12,
+                  TAG_LAPLACE = 0x20, TAG_RESAMPLE = 0x21 };
 
 struct u64x2 { uint64_t a, b; };
 

@@ -489,6 +489,23 @@ class Model:
             return tot
         return tot, {k: np.ascontiguousarray(out[:, j]) for j, k in enumerate(("elpd_loo", "khat", "lppd", "p_loo"))}
 
+    def log_density(self, q, shard=None):
+        """lp at each of the S draws ``q`` [S, D] (unconstrained, the layout of ``log_predictive``): by
+        definition the ``lp`` of ``log_density_grad`` at that draw, for all S in one forward-only pass over
+        the shard's rows (stk_log_density_draws: the per-draw log-density sweep; regression families with
+        d <= 128, any S >= 1).  shard: an index (lp [S]) or None for every shard against the same draws in
+        one grouped launch (lp [nshards, S]).  lp of a draw depends on that draw and the shard alone, bit
+        for bit; a non-finite draw has a non-finite lp and touches no other."""
+        every = shard is None
+        q = np.ascontiguousarray(np.atleast_2d(q), np.float64)
+        D = self.D[0 if every else shard]
+        if q.ndim != 2 or q.shape[1] != D:
+            raise ValueError(f"q must be [S, D = {D}], got {q.shape}")
+        lp = np.empty((self.nshards if every else 1, q.shape[0]))
+        check(_lib.load().stk_log_density_draws(self._h, -1 if every else int(shard), q.ctypes.data, q.shape[0],
+                                                lp.ctypes.data))
+        return lp if every else lp[0]
+
     def set_prior(self, alpha=None, beta=None):
         """normal(0, s) priors on alpha and beta (regressions); None or 0: flat."""
         check(_lib.load().stk_model_set_prior(self._h, float(alpha or 0.0), float(beta or 0.0)))
@@ -829,6 +846,162 @@ def fitted_mean(ctx, family, x, q):
         return m.log_predictive(q, 0, rows=True)[1]["mu"]
     finally:
         m.close()
+
+
+def logdens_launch(n_rows: int, n_cols: int, S: int) -> dict:
+    """The launch shape of the per-draw log-density sweep over a shard of ``n_rows`` x ``n_cols`` against
+    ``S`` draws (stk_logdens_launch_info): rows per tile ``T``, chunks per shard ``G``, ``waves`` per
+    block, ``lds_bytes`` -- none of which depends on S -- and ``image_bytes`` of the draw image and
+    ``ws_bytes_per_shard``, which do.  Raises STK_E_ARG past 128 covariates or for S < 1.  Host only."""
+    out = np.zeros(6, np.int64)
+    check(_lib.load().stk_logdens_launch_info(int(n_rows), int(n_cols), int(S), out.ctypes.data))
+    return dict(zip(("T", "G", "waves", "lds_bytes", "image_bytes", "ws_bytes_per_shard"), (int(v) for v in out)))
+
+
+TAG_LAPLACE, TAG_RESAMPLE = 0x20, 0x21       # csrc/philox.h
+
+
+def philox_words(seed: int, c0, c1, c2, c3):
+    """Philox4x32-10 (csrc/philox.h's ``philox``) on numpy arrays of counters: the two 64-bit output words."""
+    c0, c1, c2, c3 = (np.asarray(c, np.uint64) & np.uint64(0xFFFFFFFF) for c in np.broadcast_arrays(c0, c1, c2, c3))
+    m32 = np.uint64(0xFFFFFFFF)
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c0
+        p1 = np.uint64(0xCD9E8D57) * c2
+        n0 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0)
+        n2 = (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1)
+        c1, c3, c0, c2 = p1 & m32, p0 & m32, n0, n2
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return (c1 << np.uint64(32)) | c0, (c3 << np.uint64(32)) | c2
+
+
+def _u53(x):
+    return ((x >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -53
+
+
+def laplace_draws(ctx: Context, mode, factor, S: int, seed: int, stream: int):
+    """S draws of N(mode, F F^T) and their log proposal density without its constant
+    (stk_laplace_draws): theta_s = mode + F xi_s with xi_{s,j} the Box-Muller normal of the Philox counter
+    {stream, s, j / 2, TAG_LAPLACE}, log_q[s] = -sum_j xi_{s,j}^2 / 2.  ``factor`` is any D x D matrix
+    with F F^T = the covariance (``laplace_sample`` passes L^-T of -H = L L^T); D <= 130.  stream: the
+    shard's global index.  Returns (q [S, D], log_q [S])."""
+    mode = np.ascontiguousarray(mode, np.float64).reshape(-1)
+    F = np.ascontiguousarray(factor, np.float64)
+    D = mode.size
+    if F.shape != (D, D):
+        raise ValueError(f"factor must be ({D}, {D}), got {F.shape}")
+    q, lq = np.empty((max(int(S), 0), D)), np.empty(max(int(S), 0))
+    check(_lib.load().stk_laplace_draws(ctx._h, mode.ctypes.data, F.ctypes.data, D, int(S),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, q.ctypes.data,
+                                        lq.ctypes.data))
+    return q, lq
+
+
+def _psis_tail_len(S: int) -> int:
+    b = 0
+    while b * b < 9 * S:
+        b += 1
+    return min((S + 4) // 5, b)
+
+
+def psis_weights(log_ratio):
+    """Pareto-smoothed importance weights of ONE vector of S log importance ratios (any S >= 1, no cap):
+    returns (log_w, khat), log_w the normalised smoothed log weights in the input's order.  A host numpy
+    step with csrc/psis_math.h's definitions: tail length M = ceil(min(S / 5, 3 sqrt S)); the
+    Zhang-Stephens fit of the generalised Pareto tail with the loo package's prior (khat = (k M + 5) /
+    (M + 10)); the M largest ratios replaced by the fitted quantiles at (j - 1/2) / M; everything
+    truncated at the largest raw ratio; normalised by its logsumexp.  No smoothing, and khat = +inf, at
+    S <= 20 (M < 5) and for a constant tail.  -inf ratios are draws of weight 0; NaN or +inf raise."""
+    lr = np.asarray(log_ratio, np.float64).reshape(-1)
+    S = lr.size
+    if S < 1:
+        raise ValueError("psis_weights needs at least one log ratio")
+    if np.isnan(lr).any() or np.any(lr == np.inf) or not np.isfinite(lr.max()):
+        raise ValueError("psis_weights: the log ratios hold a NaN or +inf, or no finite value")
+    order = np.argsort(lr, kind="stable")
+    v = lr[order]
+    mx = v[-1]
+    M = _psis_tail_len(S)
+    lw = v - mx
+    khat = np.inf
+    if M >= 5 and v[S - 1] - v[S - M] > 0.0:
+        with np.errstate(all="ignore"):
+            ecut = np.exp(v[S - M - 1] - mx)
+            x = np.exp(v[S - M:] - mx) - ecut
+            Mg = 30 + int(np.floor(np.sqrt(M)))
+            xN, xstar = x[M - 1], x[(M + 2) // 4 - 1]
+            j = np.arange(1, Mg + 1, dtype=np.float64)
+            theta = 1.0 / xN + (1.0 - np.sqrt(Mg / (j - 0.5))) / 3.0 / xstar
+            kb = np.array([np.sum(np.log1p(-t * x)) / M for t in theta])
+            prof = M * (np.log(-theta / kb) - kb - 1.0)
+            w = np.array([1.0 / np.sum(np.exp(prof - prof[i])) for i in range(Mg)])
+            that = np.sum(theta * w)
+            k = np.sum(np.log1p(-that * x)) / M
+            sigma = -k / that
+            kh = (k * M + 5.0) / (M + 10.0)
+            if np.isfinite(kh):
+                khat = float(kh)
+                pj = (np.arange(1, M + 1, dtype=np.float64) - 0.5) / M
+                lw = lw.copy()
+                lw[S - M:] = np.log(sigma * np.expm1(-kh * np.log1p(-pj)) / kh + ecut)
+    lw = np.minimum(lw, 0.0)
+    m1 = lw.max()
+    lw = lw - (m1 + np.log(np.sum(np.exp(lw - m1))))
+    out = np.empty(S)
+    out[order] = lw
+    return out, khat
+
+
+def resample(log_w, n: int, seed: int, stream: int):
+    """Stratified resampling: n indices into the draws of ``log_w`` (log weights, normalised or not).
+    u_k = (k + U_k) / n, U_k the first uniform of the Philox counter {stream, k, 0, TAG_RESAMPLE} under
+    ``seed``; index k is the first i whose running sum of the weights, taken in index order, exceeds u_k
+    times the total.  Uniform weights with n = S give the identity."""
+    lw = np.asarray(log_w, np.float64).reshape(-1)
+    n = int(n)
+    if n < 1 or lw.size < 1:
+        raise ValueError("resample needs n >= 1 and at least one weight")
+    w = np.exp(lw - lw.max())
+    c = np.cumsum(w)                         # index order
+    kk = np.arange(n, dtype=np.uint64)
+    U = _u53(philox_words(seed, np.uint64(int(stream) & 0xFFFFFFFF), kk, np.uint64(0), np.uint64(TAG_RESAMPLE))[0])
+    u = (np.arange(n, dtype=np.float64) + U) / n
+    return np.minimum(np.searchsorted(c, u * c[-1], side="right"), lw.size - 1).astype(np.int64)
+
+
+def laplace_factor(cov):
+    """F = L^-T of the Cholesky factorisation cov^-1 = -H = L L^T, so that F F^T = cov."""
+    L = np.linalg.cholesky(np.linalg.inv(np.asarray(cov, np.float64)))
+    return np.ascontiguousarray(np.linalg.inv(L).T)
+
+
+def laplace_sample(model, shard: int, draws: int, seed: int, stream=None, fit=None):
+    """``draws`` importance-resampled draws of one shard's posterior from its Laplace approximation --
+    what Stan ships as ``laplace`` and as Pathfinder's last stage: proposals from N(mode, (-H)^-1)
+    (``laplace_draws``), each weighted by target over proposal (``Model.log_density`` against the
+    proposal's log density), the weights smoothed by PSIS (``psis_weights``), then stratified resampling
+    (``resample``).  fit: ``laplace``'s (mode, cov, info) for this shard, or None to fit here (a fit that
+    does not converge raises ``laplace``'s ValueError).  stream: the shard's global index (None: ``shard``).
+    Returns a dict: ``draws`` [S, D] (unconstrained, equally weighted) and ``lp`` at them; ``proposals``,
+    ``log_ratio``, ``log_w`` (normalised, smoothed); ``khat`` -- above 0.7 the proposal is too far from the
+    posterior for the weights to be trusted: sample that shard with NUTS -- and ``ess`` = 1 / sum w^2;
+    ``mode``, ``cov``, ``info``.  A proposal whose log density is NaN gets weight 0."""
+    S = int(draws)
+    if S < 1:
+        raise ValueError(f"laplace_sample needs draws >= 1, got {draws}")
+    mode, cov, info = fit if fit is not None else laplace(model, [int(shard)])
+    stream = int(shard) if stream is None else int(stream)
+    props, log_q = laplace_draws(model.ctx, mode, laplace_factor(cov), S, seed, stream)
+    lp = model.log_density(props, int(shard))
+    with np.errstate(invalid="ignore"):
+        log_ratio = lp - log_q
+    log_ratio = np.where(np.isnan(log_ratio) | (log_ratio == np.inf), -np.inf, log_ratio)
+    log_w, khat = psis_weights(log_ratio)
+    w = np.exp(log_w)
+    idx = resample(log_w, S, seed, stream)
+    return {"draws": np.ascontiguousarray(props[idx]), "lp": lp[idx], "proposals": props, "log_ratio": log_ratio,
+            "log_w": log_w, "khat": khat, "ess": float(1.0 / np.sum(w * w)), "mode": mode, "cov": cov, "info": info}
 
 
 def laplace(model, shards=None, q0=None, reduce=None, max_iter=50, tol=1e-8):

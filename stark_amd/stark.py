@@ -26,6 +26,7 @@ chain order (what the sampler's diagnostics need).
 from __future__ import annotations
 
 import inspect
+import warnings
 
 import numpy as np
 
@@ -316,6 +317,82 @@ class Stark:
         ids = shard_ids if shard_ids is not None else range(len(datas))
         return [permute_draws(d, cfg["chains"], cfg["seed"], p) for d, p in zip(draws, ids)]
 
+    LAPLACE_MAX_COLS = 128    # the per-draw log-density sweep and the Hessian sweep cover d <= 128
+    KHAT_WARN = 0.7           # above it the PSIS weights of a partition are not to be trusted
+
+    def _laplace_partitions(self, datas, shard_ids=None, pars=None, include=True, want_weights=False, permuted=True,
+                            **kwargs):
+        """method="laplace" behind concensusWeight: every data dict as one shard of a single GPU model; per
+        shard a Laplace fit and ``engine.laplace_sample`` with the partition's GLOBAL index as RNG stream.
+        Returns (draws, weights, diagnostics): draws[i] is the P x S matrix of the NUTS path (constrained
+        parameters -- linear: sigma = e^u -- then lp__ = the log density at the draw; pars / include select
+        rows as there), S = ceil((iter - warmup) / thin) * chains; weights[i] the Laplace precision of the
+        selected rows other than lp__ (want_weights, from the SAME fit) or None; diagnostics[i] the 1 x 2
+        array [khat, ess].  permuted is accepted and ignored: the draws are exchangeable."""
+        rows = [frontend.select_pars(self.family, d, pars, include) for d in datas]   # validates first
+        cfg = sampling_config(self.family, datas, **kwargs)
+        S = -(-cfg["num_samples"] // cfg["thin"]) * cfg["chains"]
+        if S < 1:
+            raise ValueError("method='laplace' needs at least one post-warmup draw (iter > warmup)")
+        ids = list(shard_ids) if shard_ids is not None else list(range(len(datas)))
+        shards = [frontend.pack_data(self.family, d) for d in datas]
+        model = engine.Model(engine.default_context(), self.family, shards)
+        if getattr(self, "priors", None):
+            model.set_prior(**self.priors)
+        draws, weights, diags = [], [], []
+        try:
+            for s, r in enumerate(rows):
+                try:
+                    fit = engine.laplace(model, [s])
+                except ValueError as e:
+                    raise ValueError(f"partition {ids[s]}: no Laplace fit ({e})") from None
+                res = engine.laplace_sample(model, s, S, cfg["seed"], stream=ids[s], fit=fit)
+                if res["khat"] > self.KHAT_WARN:
+                    warnings.warn(f"partition {ids[s]}: Pareto khat = {res['khat']:.2f} > {self.KHAT_WARN} (ess = "
+                                  f"{res['ess']:.0f} of {S} draws): its Laplace approximation is too far from the "
+                                  "subposterior for the importance weights to be trusted -- sample this partition "
+                                  "with NUTS (method='nuts')", RuntimeWarning, stacklevel=3)
+                theta = res["draws"].T.copy()
+                cov = res["cov"]
+                if self.family == "linear":
+                    theta[-1] = np.exp(theta[-1])
+                    sig = float(np.exp(res["mode"][-1]))
+                    cov = cov.copy()
+                    cov[-1, :] *= sig
+                    cov[:, -1] *= sig
+                m = np.vstack([theta, res["lp"][None, :]])
+                draws.append(np.ascontiguousarray(m if r is None else m[r]))
+                if want_weights:
+                    if r is not None:
+                        cov = cov[np.ix_(r[:-1], r[:-1])]
+                    weights.append(np.linalg.inv(cov))
+                else:
+                    weights.append(None)
+                diags.append(np.array([[res["khat"], res["ess"]]]))
+        finally:
+            model.close()
+        return draws, weights, diags
+
+    def _run_laplace_distributed(self, parts, want_weights, **kwargs):
+        """_run_distributed for method="laplace": partition p on rank p % world, its global index as the
+        stream, so the results are the same at any rank count."""
+        rank, ws = dist.world()
+        mine = dist.local_partitions(len(parts), rank, ws)
+        datas = [self.prepare_data_callback(list(parts[p])) for p in mine]
+        for p, d in zip(mine, datas):
+            if int(d["K"]) > self.LAPLACE_MAX_COLS:
+                raise ValueError(f"method='laplace' covers at most {self.LAPLACE_MAX_COLS} covariates; partition {p} "
+                                 f"has K = {int(d['K'])}")
+        draws, weights, diags = (self._laplace_partitions(datas, shard_ids=mine, want_weights=want_weights, **kwargs)
+                                 if datas else ([], [], []))
+        n = len(parts)
+        gd = dist.all_gather_partitions(dict(zip(mine, diags)), n)
+        self.laplace_diagnostics = {"khat": [float(np.asarray(g)[0, 0]) for g in gd],
+                                    "ess": [float(np.asarray(g)[0, 1]) for g in gd]}
+        sub = dist.all_gather_partitions(dict(zip(mine, draws)), n)
+        prec = dist.all_gather_partitions(dict(zip(mine, weights)), n) if want_weights else None
+        return sub, prec
+
     def _mcmc(self, callback, **kwargs):
         def w(sts):
             sts = list(sts)
@@ -343,8 +420,21 @@ class Stark:
         return (dist.all_gather_partitions(dict(zip(mine, draws)), len(parts)),
                 dist.all_gather_partitions(dict(zip(mine, weights)), len(parts)))
 
-    def concensusWeight(self, separate_lp=False, weights="sample", **kwargs):
+    def concensusWeight(self, separate_lp=False, weights="sample", method="nuts", **kwargs):
         """stark/stark.py:59-71: subposterior per partition, consensus weighted average.
+
+        method: "nuts" (default: every partition is sampled by NUTS, everything below, bit for bit what
+        omitting the argument gives) or "laplace": every partition's draws are importance-resampled
+        from its Laplace approximation (``engine.laplace_sample``: proposals from N(mode, (-H)^-1), PSIS-
+        smoothed weights of target over proposal, stratified resampling), S = ceil((iter - warmup) / thin)
+        * chains per partition.  The matrix has the NUTS path's shape, rows and pars= / include= handling
+        (constrained parameters, lp__ = the log density at the draw) and goes through the same combine, so
+        separate_lp and weights= keep their meaning; weights="laplace" reuses the fit.  Every partition's
+        Pareto ``khat`` and ``ess`` = 1 / sum w^2 are kept in ``self.laplace_diagnostics``; a partition
+        with khat > 0.7 raises a RuntimeWarning that names it: its subposterior is not near-Gaussian
+        (few rows per covariate) and it should be sampled with NUTS.  The partition's global index is the
+        RNG stream, so the result is the same on 1 or N ranks.  Regression families with at most 128
+        covariates: ValueError for 8 schools and for more columns, before anything runs.
 
         weights: "sample" (default: the reference's W_s = inv(cov(draws_s)), everything below) or
         "laplace": W_s is the precision of shard s's Laplace approximation, -H_s at the shard's mode
@@ -378,6 +468,22 @@ class Stark:
         (DESIGN.md section 9)."""
         if weights not in ("sample", "laplace"):
             raise ValueError(f"weights must be 'sample' or 'laplace', got {weights!r}")
+        if method not in ("nuts", "laplace"):
+            raise ValueError(f"method must be 'nuts' or 'laplace', got {method!r}")
+        if method == "laplace":
+            if self.family is None:
+                raise RuntimeError("call setStanModel() first")
+            if self.family == "schools":
+                raise ValueError("method='laplace' needs a regression family (linear, logistic, poisson): "
+                                 "8 schools has no Hessian or per-draw log-density sweep")
+            kwargs = self._defaults(kwargs)
+            parts = _rdd.partitions_of(self.rdd)
+            sub, prec = self._run_laplace_distributed(parts, weights == "laplace", **kwargs)
+            if prec is not None:
+                out, _ = engine.consensus(sub, weights=prec)
+            else:
+                out, _ = engine.consensus(sub, separate_lp=separate_lp)
+            return out
         if weights == "laplace":
             if self.family is None:
                 raise RuntimeError("call setStanModel() first")
