@@ -39,6 +39,11 @@
  *   stk_log_density_draws /     the log density of a shard at each of S draws in one pass over its rows, and the
  *   stk_logdens_launch_info /   Gaussian proposal draws of a Laplace fit: together the importance ratios of
  *   stk_laplace_draws           Laplace sampling (stark_amd.engine.laplace_sample).  No reference counterpart
+ *   stk_log_density_grad_boot / log density + gradient of bootstrap replicates of a shard, 16 per pass over its rows,
+ *   stk_boot_weights_host /     every row weighted by a Philox draw made in the kernel (Exp(1): the weighted-
+ *   stk_boot_poisson_thresholds / likelihood bootstrap; Poisson(1): the classical one), the weights' host twin and
+ *   stk_boot_launch_info        the launch shape (stark_amd.engine.bootstrap).  The reference's README names the
+ *                               mode ("akin to a distributed bootstrap") without building it
  *
  * Conventions
  *   - Return 0 on success, a negative STK_E_* code on failure; stk_last_error() gives a
@@ -409,6 +414,42 @@ STK_API int stk_logdens_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_
  * (naming D = ... / S = ...) otherwise. */
 STK_API int stk_laplace_draws(stk_ctx* ctx, const double* mode, const double* factor, int32_t D, int32_t S,
                               uint64_t seed, uint32_t stream, double* q_out, double* log_q_out);
+
+/* ---- weighted-likelihood bootstrap sweep (regression families, d <= 128) ----
+ * The bootstrap weight of row i (its index in the shard) in replicate b, a pure function of (seed, stream, i,
+ * b, kind) (csrc/boot_math.h): the Philox counter {(uint32)(i >> 4), ((uint32)(i >> 36) << 2) | (i & 3),
+ * stream << 12 | b, TAG_BOOT} gives four 32-bit words (first output low, high, second output low, high) and the
+ * row takes word (i >> 2) & 3.  kind 0 ("poisson"): w = the number of thresholds T_k <= word, T_k = floor(2^32
+ * sum_{j <= k} e^-1 / j!), k = 0 .. 12 -- integers 0 .. 13 of mean 1.  kind 1 ("exponential"): w = -log((word +
+ * 1/2) 2^-32), mean 1, at most 22.9.  b < 4096; stream < 2^20 is the shard's GLOBAL index, so a shard draws the
+ * same weights on any rank and next to any other shards.
+ *
+ * stk_log_density_grad_boot: q is [R][D] (unconstrained, the layout of stk_log_density_grad) and holds
+ * replicates rep0 .. rep0 + R - 1; rep0 is a multiple of 16 and rep0 + R <= 4096.  For every replicate
+ *   lp_b = sum_i w_ib ll_i(q_b) + prior(q_b) + Jacobian,   grad_b = its gradient [D],   wsum_b = sum_i w_ib
+ * with ll_i, the prior and the Jacobian exactly those of stk_log_density_grad (propto, the stk_model_set_prior
+ * terms unweighted, + u for linear, whose - n u becomes - wsum_b u).  The replicates run as tiles of 16, one
+ * pass over the shard's rows per tile.  shard == -1 runs every shard at the same q in grouped launches and
+ * fills lp[nshards][R], grad[nshards][R][D], wsum[nshards][R]; else lp[R], grad[R][D], wsum[R].  streams holds
+ * one value per shard of the call; NULL: the local shard index.  grad and wsum may be NULL; host or device
+ * memory for q, lp, grad, wsum (streams: host).
+ * A replicate's three outputs depend on (the shard's rows, seed, stream, b, q_b) alone, bit for bit: not on its
+ * companions in the call, on R, on how many shards share the launch or on the device.  A non-finite q_b gives a
+ * non-finite lp_b and touches no other replicate.
+ * STK_E_ARG (the message names the family or the offending value) for 8 schools, d > 128, a kind other than
+ * 0 / 1, R < 1, a rep0 that is no multiple of 16, rep0 + R > 4096, a stream >= 2^20 and a shard whose chunks of
+ * rows exceed 2^31 bytes (split the shard). */
+STK_API int stk_log_density_grad_boot(stk_model* m, int shard, const double* q, int32_t R, int32_t rep0, uint64_t seed,
+                                      const int32_t* streams, int32_t kind, double* lp, double* grad, double* wsum);
+/* host only, no context: out[r - row0][b - rep0] = the weight of row r in replicate b for nrows rows from row0
+ * and R replicates from rep0 (any rep0 here; rep0 + R <= 4096) -- compiled from the header the kernel uses. */
+STK_API int stk_boot_weights_host(uint64_t seed, uint32_t stream, int64_t row0, int64_t nrows, int32_t rep0, int32_t R,
+                                  int32_t kind, double* out);
+/* host only: the 13 thresholds T_k of kind 0. */
+STK_API int stk_boot_poisson_thresholds(uint32_t out[13]);
+/* host only: out[0] rows per sub-tile, out[1] chunks per shard (a function of n_rows alone), out[2] waves per
+ * block, out[3] dynamic LDS bytes, out[4] bytes of chunk-partial workspace per shard and tile of 16 replicates. */
+STK_API int stk_boot_launch_info(int64_t n_rows, int32_t d, int64_t out[5]);
 
 /* ---- sampling: stark/stark.py:43-56 for every shard of the model ---- */
 STK_API int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out);

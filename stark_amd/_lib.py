@@ -126,6 +126,10 @@ SIGNATURES = [
     ("stk_log_density_draws", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _vp]),
     ("stk_logdens_launch_info", ctypes.c_int, [_i64, _i32, _i32, _vp]),
     ("stk_laplace_draws", ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _u64, ctypes.c_uint32, _vp, _vp]),
+    ("stk_log_density_grad_boot", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _i32, _u64, _vp, _i32, _vp, _vp, _vp]),
+    ("stk_boot_weights_host", ctypes.c_int, [_u64, ctypes.c_uint32, _i64, _i64, _i32, _i32, _i32, _vp]),
+    ("stk_boot_poisson_thresholds", ctypes.c_int, [_vp]),
+    ("stk_boot_launch_info", ctypes.c_int, [_i64, _i32, _vp]),
 ]
 
 # int (*stk_allreduce_fn)(void* user, double* block, int64_t count, void* stream)

@@ -1,6 +1,8 @@
 // C ABI of libstark_hip.so: the chain plan, the lp / grad parity hooks, the host-only launch-info
-// calls, the analytic Hessian, the pointwise log-predictive sweep and the PSIS-LOO sweep.
+// calls, the analytic Hessian, the pointwise log-predictive sweep, the PSIS-LOO sweep, the per-draw log
+// density, the weighted bootstrap sweep and the Laplace proposal.
 #include "capi_internal.h"
+#include "boot_math.h"
 
 // The chain counts that are ONE sweep launch in the two single-launch parity hooks (stk_log_density_grad's
 // own batching and stk_log_density_grad_shards): their acceptance set stays as it was before the
@@ -416,6 +418,103 @@ int stk_log_density_draws(stk_model* m, int shard, const double* q, int32_t S, d
   STK_HIP_CHECK(stk_launch_logdens(m->family, m->sh_dev.as<ShardDev>(), r.shard0, r.nsh, m->d, D, r.Gs, S, img, qb,
                                    ctx->scratch[SCR_LOGDENS_PARTIAL].as<double>(), lpb, st));
   STK_HIP_CHECK(hipMemcpyAsync(lp, lpb, sizeof(double) * lpn, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
+// ---------------------------------------------------------------- weighted bootstrap sweep (boot.hip)
+// The sweep's launch shape over a shard of n_rows x d (host only: no device).
+// out: rows per sub-tile, chunks per shard, waves per block, LDS bytes, chunk-partial workspace bytes per shard
+// and tile of 16 replicates.
+int stk_boot_launch_info(int64_t n_rows, int32_t d, int64_t out[5]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_boot_launch_info: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(stk_boot_supported(d), "the bootstrap sweep covers 1 <= d <= 128 covariates, not d = %d", d);
+  const int64_t v[5] = {stk_boot_rows_per_tile(), stk_boot_chunks(n_rows), stk_boot_waves(), (int64_t)stk_boot_lds_bytes(d),
+                        (int64_t)stk_boot_ws_bytes(n_rows, d)};
+  memcpy(out, v, sizeof(v));
+  return STK_OK;
+}
+
+int stk_boot_poisson_thresholds(uint32_t out[13]) {
+  ARG_CHECK(out, "stk_boot_poisson_thresholds: out is NULL");
+  boot_poisson_thresholds(out);
+  return STK_OK;
+}
+
+// The twin of the kernel's weights: boot_math.h's boot_weight, row by row (host only: no device, no context).
+int stk_boot_weights_host(uint64_t seed, uint32_t stream, int64_t row0, int64_t nrows, int32_t rep0, int32_t R, int32_t kind,
+                          double* out) {
+  ARG_CHECK(out, "stk_boot_weights_host: out is NULL");
+  ARG_CHECK(kind == BOOT_POISSON || kind == BOOT_EXPONENTIAL,
+            "stk_boot_weights_host: kind = %d; the weights are 0 (poisson) or 1 (exponential)", kind);
+  ARG_CHECK(row0 >= 0 && nrows >= 0, "stk_boot_weights_host: row0 = %lld, nrows = %lld; need both >= 0", (long long)row0,
+            (long long)nrows);
+  ARG_CHECK(R >= 1, "stk_boot_weights_host: R = %d replicates; need R >= 1", R);
+  ARG_CHECK(rep0 >= 0 && (int64_t)rep0 + R <= BOOT_MAX_REPS,
+            "stk_boot_weights_host: replicates rep0 = %d .. rep0 + R = %d; a replicate index is below %d", rep0, rep0 + R,
+            BOOT_MAX_REPS);
+  ARG_CHECK(stream < BOOT_MAX_STREAM, "stk_boot_weights_host: stream = %u; a stream is below 2^20 = %u", stream, BOOT_MAX_STREAM);
+  for (int64_t r = 0; r < nrows; ++r)
+    for (int32_t b = 0; b < R; ++b) out[r * R + b] = boot_weight(seed, stream, row0 + r, (uint32_t)(rep0 + b), kind);
+  return STK_OK;
+}
+
+// R replicates against one shard or (shard == -1) every shard at the same points: per tile of 16 replicates
+// one sweep launch and one reduce launch for all of them.  The points are staged as [tiles * 16][Dp] with the
+// last one repeated to fill the last tile; only the live columns are reduced.
+int stk_log_density_grad_boot(stk_model* m, int shard, const double* q, int32_t R, int32_t rep0, uint64_t seed,
+                              const int32_t* streams, int32_t kind, double* lp, double* grad, double* wsum) {
+  ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_log_density_grad_boot: bad model or shard");
+  ARG_CHECK(is_regression(m->family), "stk_log_density_grad_boot: no bootstrap sweep for the %s family (regressions only)",
+            family_name(m->family));
+  ARG_CHECK(stk_boot_supported(m->d),
+            "stk_log_density_grad_boot: the bootstrap sweep covers 1 <= d <= 128 covariates, not d = %d (%s family)", m->d,
+            family_name(m->family));
+  ARG_CHECK(kind == BOOT_POISSON || kind == BOOT_EXPONENTIAL,
+            "stk_log_density_grad_boot: kind = %d; the weights are 0 (poisson) or 1 (exponential)", kind);
+  ARG_CHECK(R >= 1, "stk_log_density_grad_boot: R = %d replicates; need R >= 1", R);
+  ARG_CHECK(rep0 >= 0 && rep0 % 16 == 0, "stk_log_density_grad_boot: rep0 = %d; the first replicate is a multiple of 16", rep0);
+  ARG_CHECK((int64_t)rep0 + R <= BOOT_MAX_REPS,
+            "stk_log_density_grad_boot: rep0 + R = %lld; a replicate index is below %d", (long long)rep0 + R, BOOT_MAX_REPS);
+  ARG_CHECK(q && lp, "stk_log_density_grad_boot: q or lp is NULL (%s family, d = %d)", family_name(m->family), m->d);
+  const ShardRange r = shard_range(m, shard, stk_boot_chunks);
+  std::vector<int32_t> sv(r.nsh);
+  for (int s = 0; s < r.nsh; ++s) {
+    sv[s] = streams ? streams[s] : r.shard0 + s;
+    ARG_CHECK(sv[s] >= 0 && (uint32_t)sv[s] < BOOT_MAX_STREAM,
+              "stk_log_density_grad_boot: stream = %d of shard %d; a stream is in 0 .. 2^20 - 1", sv[s], r.shard0 + s);
+    const int64_t n = m->sh[r.shard0 + s].n;
+    ARG_CHECK(stk_boot_chunk_rows(n) * m->d * 8 < (int64_t)1 << 31,
+              "stk_log_density_grad_boot: shard %d: a chunk of n = %lld rows of d = %d covariates must fit a buffer "
+              "descriptor: split the shard", r.shard0 + s, (long long)n, m->d);
+  }
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int D = m->Dmax, Dp = (D + 7) / 8 * 8, d = m->d;
+  const int ntile = (R + 15) / 16;
+  const size_t qn = (size_t)ntile * 16 * Dp, lpn = (size_t)r.nsh * R, gn = lpn * D;
+  const size_t sbytes = (sizeof(int32_t) * r.nsh + 7) / 8 * 8;
+  RC(ctx->scratch[SCR_BOOT_IO].ensure(sizeof(double) * (qn + 2 * lpn + gn) + sbytes));
+  RC(ctx->scratch[SCR_BOOT_PARTIAL].ensure(sizeof(double) * (size_t)r.nsh * r.Gs * 16 * (d + 3)));
+  double* qb = ctx->scratch[SCR_BOOT_IO].as<double>();
+  double* lpb = qb + qn;
+  double* wsb = lpb + lpn;
+  double* gb = wsb + lpn;
+  int32_t* sb = reinterpret_cast<int32_t*>(gb + gn);
+  const size_t pitch = sizeof(double) * Dp, width = sizeof(double) * D;
+  STK_HIP_CHECK(hipMemcpy2DAsync(qb, pitch, q, width, width, R, hipMemcpyDefault, st));
+  for (int c = R; c < ntile * 16; ++c)
+    STK_HIP_CHECK(hipMemcpyAsync(qb + (size_t)c * Dp, q + (size_t)(R - 1) * D, width, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipMemcpyAsync(sb, sv.data(), sizeof(int32_t) * r.nsh, hipMemcpyHostToDevice, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));   // sv is a local
+  for (int t = 0; t < ntile; ++t)
+    STK_HIP_CHECK(stk_launch_boot(m->family, m->sh_dev.as<ShardDev>(), r.shard0, r.nsh, d, r.Gs, Dp, qb + (size_t)t * 16 * Dp,
+                                  ctx->scratch[SCR_BOOT_PARTIAL].as<double>(), sb, seed, rep0 + 16 * t, kind, R, 16 * t,
+                                  std::min(16, R - 16 * t), lpb, gb, wsb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(lp, lpb, sizeof(double) * lpn, hipMemcpyDefault, st));
+  if (grad) STK_HIP_CHECK(hipMemcpyAsync(grad, gb, sizeof(double) * gn, hipMemcpyDefault, st));
+  if (wsum) STK_HIP_CHECK(hipMemcpyAsync(wsum, wsb, sizeof(double) * lpn, hipMemcpyDefault, st));
   STK_HIP_CHECK(hipStreamSynchronize(st));
   return STK_OK;
 }

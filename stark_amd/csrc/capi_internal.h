@@ -67,6 +67,7 @@ enum Scratch : int {
   SCR_LOO_IMG, SCR_LOO_PARTIAL, SCR_LOO_ROWS,      // PSIS-LOO: draw image, partials, per-row staging
   SCR_LOGDENS_IMG, SCR_LOGDENS_PARTIAL,            // per-draw log density: draw image + draws + lp, partials
   SCR_LAPLACE,                                     // Laplace proposal: mode, factor, draws, log_q
+  SCR_BOOT_IO, SCR_BOOT_PARTIAL,                   // bootstrap sweep: points + streams + lp, grad, wsum; partials
   SCR_COUNT
 };
 

@@ -138,6 +138,19 @@ int stk_laplace_max_dim();
 hipError_t stk_launch_laplace_draws(const double* mode, const double* factor, int D, int S, uint64_t seed,
                                     uint32_t stream, double* q, double* log_q, hipStream_t st);
 
+// ---- boot.hip (regressions, d <= 128): the weighted bootstrap sweep's geometry and its launch for one tile of
+// 16 replicates
+bool stk_boot_supported(int d);
+int stk_boot_chunks(int64_t n);
+int64_t stk_boot_chunk_rows(int64_t n);            // rows of the longest chunk
+int stk_boot_rows_per_tile();
+int stk_boot_waves();
+size_t stk_boot_lds_bytes(int d);
+size_t stk_boot_ws_bytes(int64_t n, int d);        // chunk-partial workspace of one shard
+hipError_t stk_launch_boot(int family, const stk::ShardDev* shards, int shard0, int nsh, int d, int Gs, int Dp,
+                           const double* q, double* partial, const int32_t* streams, uint64_t seed, int rep0, int kind,
+                           int R, int c0, int nrep, double* lp, double* grad, double* wsum, hipStream_t st);
+
 // ---- nuts.hip (and its nuts_fused4.hip / nuts_dense.hip translation units)
 int stk_nch_for(int Dmax);
 size_t stk_fused_lds_bytes(const stk::NutsArgs& A, int nch);

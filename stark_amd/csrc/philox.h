@@ -14,6 +14,8 @@
 //                                                                 stream = the shard's GLOBAL index
 //   TAG_RESAMPLE ctr = {stream, k,      0,                 TAG}  U_k of stratified resampling: the first output
 //                                                                 word (host side only, engine.resample)
+//   TAG_BOOT     ctr = {row>>4, (row>>36)<<2 | row&3, stream<<12 | b, TAG}  bootstrap weight of (row, replicate b):
+//                                                                 32-bit word (row >> 2) & 3 (boot_math.h)
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -24,7 +26,7 @@ namespace stk {
 
 enum : uint32_t { TAG_INIT = 0x1, TAG_MOM = 0x2, TAG_UNI = 0x3, TAG_SSMOM = 0x4, TAG_JIT = 0x5,
                   TAG_X = 0x10, TAG_Y = 0x11, TAG_BETA = 0x12,
-                  TAG_LAPLACE = 0x20, TAG_RESAMPLE = 0x21 };
+                  TAG_LAPLACE = 0x20, TAG_RESAMPLE = 0x21, TAG_BOOT = 0x22 };
 
 struct u64x2 { uint64_t a, b; };
 

@@ -506,6 +506,34 @@ class Model:
                                                 lp.ctypes.data))
         return lp if every else lp[0]
 
+    def log_density_grad_boot(self, q, shard=None, rep0=0, seed=0, streams=None, kind="exponential"):
+        """lp, grad lp and the weight sum of bootstrap replicates rep0 .. rep0 + R - 1 at the points ``q``
+        [R, D] (unconstrained, the layout of ``log_density_grad``): every row's log likelihood carries the
+        weight ``boot_weights`` gives it, made in the kernel (stk_log_density_grad_boot: the weighted
+        bootstrap sweep, 16 replicates per pass over the rows; regression families with d <= 128).  kind:
+        "exponential" (Exp(1): the weighted-likelihood bootstrap) or "poisson" (Poisson(1): the classical
+        one).  rep0: a multiple of 16, rep0 + R <= 4096.  shard: an index (lp [R], grad [R, D], wsum [R]) or
+        None for every shard at the same points in grouped launches ([nshards, R], [nshards, R, D],
+        [nshards, R]).  streams: one RNG stream per shard of the call -- the shard's GLOBAL index, below
+        2^20 -- or None for the local index.  A replicate's outputs depend on (rows, seed, stream, replicate,
+        q_b) alone, bit for bit; the prior and the Jacobian are not weighted."""
+        every = shard is None
+        q = np.ascontiguousarray(np.atleast_2d(q), np.float64)
+        D = self.D[0 if every else shard]
+        if q.ndim != 2 or q.shape[1] != D:
+            raise ValueError(f"q must be [R, D = {D}], got {q.shape}")
+        ns, R = (self.nshards if every else 1), q.shape[0]
+        sv = None
+        if streams is not None:
+            sv = np.ascontiguousarray(np.atleast_1d(streams), np.int32)
+            if sv.shape != (ns,):
+                raise ValueError(f"streams must hold one value per shard of the call ({ns}), got shape {sv.shape}")
+        lp, g, ws = np.empty((ns, R)), np.empty((ns, R, D)), np.empty((ns, R))
+        check(_lib.load().stk_log_density_grad_boot(self._h, -1 if every else int(shard), q.ctypes.data, R, int(rep0),
+                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(sv), boot_kind(kind),
+                                                    lp.ctypes.data, g.ctypes.data, ws.ctypes.data))
+        return (lp, g, ws) if every else (lp[0], g[0], ws[0])
+
     def set_prior(self, alpha=None, beta=None):
         """normal(0, s) priors on alpha and beta (regressions); None or 0: flat."""
         check(_lib.load().stk_model_set_prior(self._h, float(alpha or 0.0), float(beta or 0.0)))
@@ -858,7 +886,134 @@ def logdens_launch(n_rows: int, n_cols: int, S: int) -> dict:
     return dict(zip(("T", "G", "waves", "lds_bytes", "image_bytes", "ws_bytes_per_shard"), (int(v) for v in out)))
 
 
-TAG_LAPLACE, TAG_RESAMPLE = 0x20, 0x21       # csrc/philox.h
+TAG_LAPLACE, TAG_RESAMPLE, TAG_BOOT = 0x20, 0x21, 0x22       # csrc/philox.h
+BOOT_KINDS = {"poisson": 0, "exponential": 1}                # csrc/boot_math.h
+BOOT_MAX_REPS = 4096
+
+
+def boot_kind(kind) -> int:
+    """"poisson" | "exponential" (or 0 | 1) as the library's kind."""
+    if kind in BOOT_KINDS:
+        return BOOT_KINDS[kind]
+    if isinstance(kind, (int, np.integer)) and not isinstance(kind, bool):
+        return int(kind)                     # the library judges the value
+    raise ValueError(f"kind must be one of {sorted(BOOT_KINDS)}, got {kind!r}")
+
+
+def boot_weights(seed: int, stream: int, row0: int, nrows: int, rep0: int, R: int, kind="exponential") -> np.ndarray:
+    """The bootstrap weights [nrows, R] of rows row0 .. of a shard in replicates rep0 .. rep0 + R - 1
+    (stk_boot_weights_host: the host twin of the kernel's weights, compiled from the same header; needs no
+    device).  Philox counter {row >> 4, (row >> 36) << 2 | row & 3, stream << 12 | b, TAG_BOOT} under ``seed``,
+    32-bit word (row >> 2) & 3 of its four; "poisson": the number of the 13 thresholds at or below the word
+    (``boot_poisson_thresholds``), "exponential": -log((word + 1/2) 2^-32).  stream: the shard's global index."""
+    out = np.empty((max(int(nrows), 0), max(int(R), 0)))
+    check(_lib.load().stk_boot_weights_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, int(row0), int(nrows),
+                                            int(rep0), int(R), boot_kind(kind), out.ctypes.data))
+    return out
+
+
+def boot_poisson_thresholds() -> np.ndarray:
+    """T_k = floor(2^32 sum_{j <= k} e^-1 / j!), k = 0 .. 12 (stk_boot_poisson_thresholds), as uint32."""
+    out = np.zeros(13, np.uint32)
+    check(_lib.load().stk_boot_poisson_thresholds(out.ctypes.data))
+    return out
+
+
+def boot_launch(n_rows: int, n_cols: int) -> dict:
+    """The launch shape of the weighted bootstrap sweep over a shard of ``n_rows`` x ``n_cols``
+    (stk_boot_launch_info): rows per sub-tile ``T``, chunks per shard ``G`` (a function of n_rows alone),
+    ``waves`` per block, ``lds_bytes`` and ``ws_bytes_per_shard`` (per tile of 16 replicates).  Raises
+    STK_E_ARG past 128 covariates.  Host only."""
+    out = np.zeros(5, np.int64)
+    check(_lib.load().stk_boot_launch_info(int(n_rows), int(n_cols), out.ctypes.data))
+    return dict(zip(("T", "G", "waves", "lds_bytes", "ws_bytes_per_shard"), (int(v) for v in out)))
+
+
+def bootstrap(model, B: int, kind="exponential", seed: int = 0, streams=None, combine=None, fit=None, max_iter: int = 60,
+              tol: float = 1e-8):
+    """B bootstrap replicates of the maximiser of the log density summed over every shard of ``model``:
+    replicate b maximises sum_i w_ib ll_i + prior + Jacobian with the weights of ``boot_weights`` ("exponential":
+    the weighted-likelihood bootstrap, whose replicates are approximate posterior draws that do not lean on
+    the model being right; "poisson": the classical bootstrap).  B <= 4096.
+
+    Start: the unweighted mode and cov = (-H)^-1 of ``laplace`` over all shards, or ``fit`` = (mode, cov[, info]).
+    Every replicate starts at the mode with its own inverse-Hessian estimate M_b = cov and iterates
+    step = M_b g_b, q_b += step, BFGS update of M_b from (step, -(g_new - g_old)) when their product is
+    positive, until max |step| / sd < tol with sd = sqrt(diag(cov)).  The replicates of a tile of 16 move in
+    lockstep, finished ones keep their point; an iteration is one ``log_density_grad_boot`` call over every
+    shard per tile.  The per-shard blocks [R][D + 2] (lp, grad, wsum) are summed in shard order; ``combine``,
+    when given, maps the local blocks [nshards, R, D + 2] to the global sum [R, D + 2] instead -- with shards
+    on several ranks every rank calls this with the same arguments and takes identical steps.  streams: the
+    shards' global indices (None: the local ones).
+
+    A replicate that is not finite, or not converged after max_iter iterations, gets a NaN row and
+    converged[b] = False; one RuntimeWarning gives the count.  Returns a dict: ``estimates`` [B, D]
+    (unconstrained), ``lp`` (the weighted log density at the estimate), ``wsum``, ``iterations``,
+    ``converged``, ``mode`` and ``cov``."""
+    import warnings
+    B = int(B)
+    if B < 1 or B > BOOT_MAX_REPS:
+        raise ValueError(f"bootstrap needs 1 <= B <= {BOOT_MAX_REPS} replicates, got {B}")
+    k = boot_kind(kind)
+    if fit is None:
+        fit = laplace(model)
+    mode = np.array(fit[0], np.float64).reshape(-1)
+    cov = np.array(fit[1], np.float64)
+    D = mode.size
+    if cov.shape != (D, D):
+        raise ValueError(f"fit: cov must be ({D}, {D}), got {cov.shape}")
+    sd = np.sqrt(np.diag(cov))
+    est, lps, wss = np.full((B, D), np.nan), np.full(B, np.nan), np.full(B, np.nan)
+    its, conv = np.zeros(B, np.int64), np.zeros(B, bool)
+
+    def evaluate(Q, rep0):
+        lp, g, ws = model.log_density_grad_boot(Q, None, rep0=rep0, seed=seed, streams=streams, kind=k)
+        blocks = np.concatenate([np.asarray(lp)[:, :, None], np.asarray(g), np.asarray(ws)[:, :, None]], axis=2)
+        if combine is not None:
+            tot = np.asarray(combine(blocks), np.float64)
+        else:
+            tot = blocks[0].copy()
+            for blk in blocks[1:]:               # shard order
+                tot = tot + blk
+        return tot[:, 0].copy(), tot[:, 1:1 + D].copy(), tot[:, 1 + D].copy()
+
+    for rep0 in range(0, B, 16):
+        R = min(16, B - rep0)
+        Q = np.tile(mode, (R, 1))
+        M = np.tile(cov, (R, 1, 1))
+        lp, g, ws = evaluate(Q, rep0)
+        bad = ~(np.isfinite(lp) & np.isfinite(g).all(axis=1))
+        done, n_it = np.zeros(R, bool), np.zeros(R, np.int64)
+        for _ in range(int(max_iter)):
+            active = ~done & ~bad
+            if not active.any():
+                break
+            step = np.einsum("rij,rj->ri", M, np.where(active[:, None], g, 0.0))
+            step[~active] = 0.0
+            Qn = Q + step
+            lpn, gn, _ws = evaluate(Qn, rep0)
+            for r in np.flatnonzero(active):
+                if not (np.isfinite(lpn[r]) and np.isfinite(gn[r]).all()):
+                    bad[r] = True
+                    continue
+                s, y = step[r], -(gn[r] - g[r])
+                sy = float(s @ y)
+                if sy > 0.0:
+                    My = M[r] @ y
+                    M[r] = M[r] - (np.outer(s, My) + np.outer(My, s)) / sy + (1.0 + float(y @ My) / sy) / sy * np.outer(s, s)
+                Q[r], lp[r], g[r] = Qn[r], lpn[r], gn[r]
+                n_it[r] += 1
+                if np.abs(s / sd).max() < tol:
+                    done[r] = True
+        ok = done & ~bad
+        sl = slice(rep0, rep0 + R)
+        est[sl][ok], lps[sl][ok], wss[sl] = Q[ok], lp[ok], ws
+        its[sl], conv[sl] = n_it, ok
+    nbad = int((~conv).sum())
+    if nbad:
+        warnings.warn(f"bootstrap: {nbad} of {B} replicates are not finite or did not converge in {int(max_iter)} "
+                      "iterations; their rows are NaN", RuntimeWarning, stacklevel=2)
+    return {"estimates": est, "lp": lps, "wsum": wss, "iterations": its, "converged": conv, "mode": mode, "cov": cov}
 
 
 def philox_words(seed: int, c0, c1, c2, c3):
@@ -1004,14 +1159,17 @@ def laplace_sample(model, shard: int, draws: int, seed: int, stream=None, fit=No
             "log_w": log_w, "khat": khat, "ess": float(1.0 / np.sum(w * w)), "mode": mode, "cov": cov, "info": info}
 
 
-def laplace(model, shards=None, q0=None, reduce=None, max_iter=50, tol=1e-8):
+def laplace(model, shards=None, q0=None, reduce=None, max_iter=50, tol=1e-8, combine=None):
     """Mode and covariance (-H)^-1 of the posterior formed by the SUM of ``shards`` (None: every
     shard of the model), by a safeguarded Newton iteration on the analytic Hessian
     (``Model.hessian``).  Returns (mode, cov, info), in the unconstrained parameters.
 
     The meaning and the ``reduce=`` contract are those of ``tools.laplace.laplace``: with shards on
     several ranks every rank calls this with its own shards, the same q0 and a ``reduce`` that sums
-    a float64 array over the ranks in place; all ranks then take identical steps.
+    a float64 array over the ranks in place; all ranks then take identical steps.  ``combine``, when
+    given, replaces both the local sum and ``reduce``: it maps the local per-shard blocks [shards, 1, L]
+    to the global sum [1, L] (``bootstrap``'s contract), so a caller that sums per-partition blocks in
+    partition order gets the same bits at any rank count.
 
     Every iteration takes one Hessian of every shard and steps by a Cholesky factor of -H.  Where
     -H is not positive definite (the linear family away from its mode, where the theta-u cross
@@ -1035,10 +1193,12 @@ def laplace(model, shards=None, q0=None, reduce=None, max_iter=50, tol=1e-8):
         return v
 
     def density(p):
+        lps = [float(np.asarray(model.log_density_grad(s, p[None])[0]).reshape(-1)[0]) for s in ids]
+        if combine is not None:
+            return float(np.asarray(combine(np.array(lps).reshape(-1, 1, 1))).reshape(-1)[0])
         lp = 0.0
-        for s in ids:
-            l_, _ = model.log_density_grad(s, p[None])
-            lp += float(np.asarray(l_).reshape(-1)[0])
+        for l_ in lps:
+            lp += l_
         return float(total([[lp]])[0])
 
     def curvature(p):
@@ -1049,6 +1209,11 @@ def laplace(model, shards=None, q0=None, reduce=None, max_iter=50, tol=1e-8):
         for s, H in zip(ids, Hs):
             if not np.all(np.isfinite(H)):
                 raise ValueError(f"shard {s}: the Hessian at the current point is not finite")
+        if combine is not None:
+            blocks = np.stack([np.concatenate([[float(l_)], np.asarray(g_).reshape(-1), np.asarray(H_).reshape(-1)])
+                               for l_, g_, H_ in zip(lps, gs, Hs)])[:, None, :]
+            v = np.asarray(combine(blocks), np.float64).reshape(-1)
+            return float(v[0]), v[1:1 + D].copy(), v[1 + D:].reshape(D, D).copy()
         lp, g, H = 0.0, np.zeros(D), np.zeros((D, D))
         for l_, g_, H_ in zip(lps, gs, Hs):      # shard order
             lp, g, H = lp + float(l_), g + g_, H + H_

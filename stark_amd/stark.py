@@ -579,6 +579,70 @@ class Stark:
         out["partition_totals"] = totals
         return out
 
+    BOOT_MAX_COLS = 128       # the weighted bootstrap sweep and the Hessian sweep cover d <= 128
+    BOOT_WEIGHTS = {"bayesian": "exponential", "poisson": "poisson"}
+
+    def bootstrap(self, n=200, weights="bayesian", seed=0, pars=None, include=True):
+        """n bootstrap replicates of the FULL-DATA maximiser -- the mode the reference's README names next
+        ("if MAP estimates were found instead of full posteriors then one might have something akin to a
+        distributed bootstrap"): a P x n matrix with the rows of ``concensusWeight`` (constrained
+        parameters -- linear: sigma = e^u -- then lp__ = the replicate's weighted log density at its
+        maximiser; pars / include select rows as there).  weights: "bayesian" (Exp(1) row weights: the
+        weighted-likelihood bootstrap, whose replicates are approximate posterior draws that do not lean on
+        the model being right) or "poisson" (Poisson(1): the classical bootstrap).
+
+        Partitions are placed on ranks as ``waic`` places them and a partition's global index is its RNG
+        stream; every iteration's per-partition blocks are all-gathered and summed in partition order
+        (the ``combine`` of ``engine.laplace`` and ``engine.bootstrap``), so every rank takes identical steps and
+        returns the same matrix, bit for bit, on 1 or N ranks.
+        ``self.bootstrap_diagnostics`` keeps ``iterations``, ``converged`` and ``wsum`` per replicate.
+        Regression families with at most 128 covariates: ValueError otherwise, before a model is built."""
+        if self.family is None:
+            raise RuntimeError("call setStanModel() first")
+        if self.family not in ("linear", "logistic", "poisson"):
+            raise ValueError(f"no bootstrap for the {self.family} family: the weighted bootstrap sweep covers the "
+                             "regression families (linear, logistic, poisson), not 8 schools")
+        if weights not in self.BOOT_WEIGHTS:
+            raise ValueError(f"weights must be one of {sorted(self.BOOT_WEIGHTS)}, got {weights!r}")
+        parts = _rdd.partitions_of(self.rdd)
+        rank, ws = dist.world()
+        mine = dist.local_partitions(len(parts), rank, ws)
+        datas = [self.prepare_data_callback(list(parts[p])) for p in mine]
+        for p, d in zip(mine, datas):
+            if int(d["K"]) > self.BOOT_MAX_COLS:
+                raise ValueError(f"bootstrap covers at most {self.BOOT_MAX_COLS} covariates; partition {p} has K = "
+                                 f"{int(d['K'])}")
+        rows = [frontend.select_pars(self.family, d, pars, include) for d in datas]   # validates first
+        if not datas:
+            raise ValueError(f"rank {rank} holds no partition: bootstrap needs at most as many ranks as partitions")
+        n_parts = len(parts)
+
+        def combine(blocks):             # [local partitions, R, D + 2] -> the sum over ALL partitions, in their order
+            every = dist.all_gather_partitions({p: np.ascontiguousarray(b) for p, b in zip(mine, blocks)}, n_parts)
+            tot = np.array(every[0], np.float64)
+            for b in every[1:]:
+                tot = tot + np.asarray(b, np.float64)
+            return tot
+
+        model = engine.Model(engine.default_context(), self.family, [frontend.pack_data(self.family, d) for d in datas])
+        try:
+            if getattr(self, "priors", None):
+                model.set_prior(**self.priors)
+            try:
+                fit = engine.laplace(model, combine=combine)      # the same partition-order sums
+            except ValueError as e:
+                raise ValueError(f"no Laplace fit of the full data ({e})") from None
+            res = engine.bootstrap(model, int(n), kind=self.BOOT_WEIGHTS[weights], seed=seed, streams=list(mine),
+                                   combine=combine, fit=fit)
+        finally:
+            model.close()
+        self.bootstrap_diagnostics = {k: res[k] for k in ("iterations", "converged", "wsum")}
+        theta = res["estimates"].T.copy()
+        if self.family == "linear":
+            theta[-1] = np.exp(theta[-1])
+        m = np.vstack([theta, res["lp"][None, :]])
+        return np.ascontiguousarray(m if rows[0] is None else m[rows[0]])
+
     def distribute(self, n=2, reference_union=False, **kwargs):
         """stark/stark.py:73-85: naive parallel runs over the full data, draws stacked with
         ``concatenate_samples`` (row blocks of P x S)."""
