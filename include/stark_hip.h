@@ -567,6 +567,60 @@ STK_API int stk_consensus_blocked(stk_ctx* ctx, const double* draws, int32_t nsh
 STK_API int stk_consensus_weighted(stk_ctx* ctx, const double* draws, const double* weights, int32_t nshards,
                                    int32_t P, int32_t S, double* out, int32_t* shard_used);
 
+/* ---- semiparametric density-product combiner (semiparamDPE of "Asymptotically exact, embarrassingly
+ * parallel MCMC"), a second combiner next to stk_consensus.  No reference counterpart.
+ * With M usable shards of S draws theta^m_s in R^p (p = P, or P - 1 when lp_row: the last row is lp__),
+ * mu_m / Sigma_m each shard's sample mean and covariance (stk_consensus_products' stages),
+ *   Sigma_M = inv(sum_m inv(Sigma_m)) = L L^T,   mu_M = Sigma_M sum_m inv(Sigma_m) mu_m,
+ * every shard density is estimated as
+ *   p_m(theta) = N(theta | mu_m, Sigma_m) (1/S) sum_s N(theta | theta^m_s, h^2 M Sigma_M) / N(theta^m_s | mu_m, Sigma_m)
+ * (kernel covariance h^2 M Sigma_M instead of the paper's h^2 I: affine invariant).  With
+ *   y^m_s = inv(L) (theta^m_s - mu_M) / sqrt(M),  n^m_s = |y^m_s|^2,  g^m_s = (theta^m_s - mu_m)^T inv(Sigma_m) (theta^m_s - mu_m) / 2
+ * the product of the p_m is a mixture over index tuples t = (t_1 .. t_M); with s_t, N_t, G_t the sums of
+ * y, n, g at the chosen indices,
+ *   log W_t(h) = -(N_t - |s_t|^2 / M) / (2 h^2) - |s_t|^2 / (2 M (1 + h^2)) + G_t
+ *   component:   y ~ N(s_t / (M (1 + h^2)), h^2 / (M (1 + h^2)) I),   theta = mu_M + sqrt(M) L y.
+ * The sampler is independent Metropolis within Gibbs on t, K independent chains: chain k starts from uniform
+ * indices; sweep r (counted from 0, burn-in and thinning included) uses h = h[r] and proposes, for m = 0 .. M - 1
+ * in order, c uniform on {0 .. S - 1}, accepted iff log u < log W_t' - log W_t; after `burn` sweeps every
+ * `thin`-th sweep emits a draw, chain k's j-th being output column j K + k (columns >= T are not produced).
+ * h has burn + thin ceil(T / K) entries, every one positive and finite.  The lp__ row of a draw is
+ * sum_m lp_w[m] lp^m_{t_m}, lp_w[m] ~ 1 / var(lp^m) (the 1 x 1 block of stk_consensus_blocked).
+ * Philox counters and the bit-level contract: csrc/dpe_math.h, DESIGN.md section 3.
+ *
+ * stk_dpe_launch_info: out = {p, ldp (row stride of the image: p rounded up to 8), coordinates per lane,
+ *   draws per chain, LDS bytes per chain, prepare workspace bytes, sample workspace bytes, blocks (= K)}.
+ * stk_dpe_prepare: draws [nshards][P][S] (host or device) -> shard_used [nshards] and n_used = M (host), and,
+ *   host or device: mu [p], L [p][p] (lower), lp_w [nshards] (first M; lp_row), Y [nshards][S][ldp] (first M
+ *   shards; one draw per row, pads zero), nrm / g / lpv [nshards][S] (first M; lpv: lp_row).  Shards with NaN
+ *   draws are left out; S <= p is STK_E_LINALG before any arithmetic.  Every sum is in an order fixed by
+ *   (M, P, S).
+ * stk_dpe_sample: prepared arrays of M shards (host or device; lp_w and lpv both NULL: no lp__ row) -> out
+ *   [p (+ 1)][T] (host or device), accept [M] accepted proposals per shard (host, or NULL), and optionally the
+ *   trace: trace_idx [K][sweeps][M] the index of coordinate m after its proposal, trace_logw [K][sweeps]
+ *   log W of the state at the end of the sweep.
+ * stk_dpe_sample_host: the same on host arrays with no device: the arithmetic of dpe_math.h in the kernel's
+ *   order, so indices and accept counts are the kernel's (the normals' sin / cos / log may differ in the last bit).
+ * stk_consensus_dpe: prepare + sample in one call; accept [nshards] (first M).
+ * STK_E_ARG, naming the value: T < 1, K < 1, thin < 1, burn < 0, a bandwidth <= 0 or not finite, p > 1024
+ * (16 coordinates per lane), more than 4096 shards, stream >= 2^24. */
+STK_API int stk_dpe_launch_info(int32_t nshards, int32_t P, int32_t S, int32_t T, int32_t K, int32_t lp_row,
+                                int64_t out[8]);
+STK_API int stk_dpe_prepare(stk_ctx* ctx, const double* draws, int32_t nshards, int32_t P, int32_t S, int32_t lp_row,
+                            int32_t* shard_used, int32_t* n_used, double* mu, double* L, double* lp_w, double* Y,
+                            double* nrm, double* g, double* lpv);
+STK_API int stk_dpe_sample(stk_ctx* ctx, int32_t M, int32_t p, int32_t S, const double* mu, const double* L,
+                           const double* lp_w, const double* Y, const double* nrm, const double* g, const double* lpv,
+                           uint64_t seed, uint32_t stream, int32_t T, int32_t K, int32_t burn, int32_t thin,
+                           const double* h, double* out, int64_t* accept, int32_t* trace_idx, double* trace_logw);
+STK_API int stk_dpe_sample_host(int32_t M, int32_t p, int32_t S, const double* mu, const double* L, const double* lp_w,
+                                const double* Y, const double* nrm, const double* g, const double* lpv, uint64_t seed,
+                                uint32_t stream, int32_t T, int32_t K, int32_t burn, int32_t thin, const double* h,
+                                double* out, int64_t* accept, int32_t* trace_idx, double* trace_logw);
+STK_API int stk_consensus_dpe(stk_ctx* ctx, const double* draws, int32_t nshards, int32_t P, int32_t S, int32_t lp_row,
+                              uint64_t seed, uint32_t stream, int32_t T, int32_t K, int32_t burn, int32_t thin,
+                              const double* h, double* out, int32_t* shard_used, int64_t* accept);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,14 @@ SIGNATURES = [
     ("stk_boot_weights_host", ctypes.c_int, [_u64, ctypes.c_uint32, _i64, _i64, _i32, _i32, _i32, _vp]),
     ("stk_boot_poisson_thresholds", ctypes.c_int, [_vp]),
     ("stk_boot_launch_info", ctypes.c_int, [_i64, _i32, _vp]),
+    ("stk_dpe_launch_info", ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("stk_dpe_prepare", ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("stk_dpe_sample", ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, ctypes.c_uint32,
+                                      _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    ("stk_dpe_sample_host", ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, ctypes.c_uint32,
+                                           _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    ("stk_consensus_dpe", ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _u64, ctypes.c_uint32, _i32, _i32, _i32, _i32,
+                                         _vp, _vp, _vp, _vp]),
 ]
 
 # int (*stk_allreduce_fn)(void* user, double* block, int64_t count, void* stream)

@@ -68,6 +68,8 @@ enum Scratch : int {
   SCR_LOGDENS_IMG, SCR_LOGDENS_PARTIAL,            // per-draw log density: draw image + draws + lp, partials
   SCR_LAPLACE,                                     // Laplace proposal: mode, factor, draws, log_q
   SCR_BOOT_IO, SCR_BOOT_PARTIAL,                   // bootstrap sweep: points + streams + lp, grad, wsum; partials
+  SCR_DPE_IN, SCR_DPE_MOM, SCR_DPE_PREP, SCR_DPE_WS,   // density-product combiner: staged draws; the combine's moments;
+                                                       // prepared arrays (one-call path, host callers); Z, draws, trace
   SCR_COUNT
 };
 

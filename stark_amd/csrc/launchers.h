@@ -178,10 +178,35 @@ size_t stk_general_inverse_work_bytes(int P);
 hipError_t stk_launch_consensus_solve(const double* sum_w, const double* sum_wtheta, int P, int S, double* inv_buf,
                                       double* work, int32_t* status, double* out, hipStream_t st, bool general);
 size_t stk_spd_inverse_work_bytes(int P, int batch);
+hipError_t stk_launch_spd_inverse(const double* M, double* Inv, double* work, int P, int batch, const int32_t* used,
+                                  int32_t* status, hipStream_t st);
 // the caller's weights W [nshards][P][P] (device, modified: NaN-draw shards are zeroed) in place of inv(cov)
 hipError_t stk_launch_consensus_weighted(const double* X, int nshards, int P, int S, double* mean, int32_t* rowbad,
                                          int32_t* used, int32_t* status, double* W, double* sum_w, double* sum_wtheta,
                                          hipStream_t st);
+
+// ---- dpe.hip: the semiparametric density-product combiner (kernels and the host twin of the chains)
+struct StkDpeChains {
+  const double *Y, *nrm, *g, *lpv, *lpw;   // the prepared arrays of the M usable shards; lpv / lpw null: no lp__ row
+  const void* coef;                        // [sweeps] stk::DpeCoef (dpe_math.h)
+  double* ydraw;                           // device: [T][ldp] whitened draws
+  double* lpout;                           // device: [T] the lp__ row, or null
+  unsigned long long* accept;              // [M], added to
+  int32_t* tidx;                           // [K][sweeps][M] or null
+  double* tlogw;                           // [K][sweeps] or null
+  uint64_t seed;
+  uint32_t stream;
+  int M, p, S, T, K, burn, thin, sweeps;
+};
+int stk_dpe_coords_per_lane(int p);
+size_t stk_dpe_lds_bytes(int M);
+hipError_t stk_launch_dpe_image(const double* X, const double* mean, const double* W, const int32_t* zmap, int M, int P,
+                                int p, int S, const double* mu, const double* Linv, double* Y, double* Z, double* nrm,
+                                double* g, double* lpv, hipStream_t st);
+hipError_t stk_launch_dpe_chains(const StkDpeChains& c, hipStream_t st);
+hipError_t stk_launch_dpe_map(const double* ydraw, const double* L, const double* mu, int M, int p, int T, double* out,
+                              hipStream_t st);
+void stk_dpe_chains_host(const StkDpeChains& c, const double* mu, const double* L, double* out);
 
 // ---- fingerprint.hip
 uint64_t stk_fp_fmix(uint64_t a);

@@ -1390,3 +1390,204 @@ def consensus_solve(sum_w, sum_wtheta, ctx: Context | None = None):
     out = np.empty((P, S))
     check(_lib.load().stk_consensus_solve(ctx._h, sw.ctypes.data, swt.ctypes.data, P, S, out.ctypes.data))
     return out
+
+
+# ---------------------------------------------------------------- semiparametric density-product combiner
+DPE_LAUNCH_FIELDS = ("p", "ldp", "coords_per_lane", "draws_per_chain", "lds_bytes", "prepare_ws_bytes",
+                     "sample_ws_bytes", "blocks")
+
+
+def dpe_launch(nshards: int, P: int, S: int, T: int, K: int, lp_row: bool = True) -> dict:
+    """Geometry of the density-product combiner for ``nshards`` shards of P x S draws, T output draws from K
+    chains (stk_dpe_launch_info): parameter rows ``p``, the image's row stride ``ldp``, coordinates per lane,
+    draws per chain, LDS bytes per chain, the prepare's and the sampler's workspace bytes, blocks (= K)."""
+    out = np.zeros(8, np.int64)
+    check(_lib.load().stk_dpe_launch_info(int(nshards), int(P), int(S), int(T), int(K), int(bool(lp_row)),
+                                          out.ctypes.data))
+    return dict(zip(DPE_LAUNCH_FIELDS, (int(v) for v in out)))
+
+
+def dpe_sweeps(T: int, K: int, burn: int, thin: int) -> int:
+    """Sweeps every chain runs: burn-in, then ``thin`` per emitted draw, ceil(T / K) draws per chain."""
+    return int(burn) + int(thin) * (-(-int(T) // int(K)))
+
+
+def dpe_bandwidths(bandwidth, sweeps: int, p: int) -> np.ndarray:
+    """The table h_r of a run: None is the annealing schedule h_r = (r + 1)^(-1 / (4 + p)), a float a
+    constant, an array is taken as it is (one entry per sweep).  Computed once on the host, so the
+    kernel and its twin read the same doubles."""
+    if bandwidth is None:
+        return (np.arange(1, sweeps + 1, dtype=np.float64)) ** (-1.0 / (4.0 + p))
+    h = np.asarray(bandwidth, np.float64)
+    if h.ndim == 0:
+        return np.full(sweeps, float(h))
+    if h.shape != (sweeps,):
+        raise ValueError(f"bandwidth table has shape {h.shape}; the run has {sweeps} sweeps")
+    return np.ascontiguousarray(h)
+
+
+def _dpe_chain_args(S, T, chains, burn, thin, bandwidth, p):
+    T = int(S if T is None else T)
+    K = int(min(T, 1024) if chains is None else chains)
+    if T >= 1 and K >= 1 and thin >= 1 and burn >= 0:
+        sweeps = dpe_sweeps(T, K, burn, thin)
+        h = dpe_bandwidths(bandwidth, sweeps, p)
+    else:                       # the library refuses these by name
+        sweeps, h = 1, np.ones(1)
+    return T, K, sweeps, h
+
+
+def dpe_prepare(draws, lp_row: bool = True, ctx: Context | None = None) -> dict:
+    """The prepared arrays of the density-product combiner (stk_dpe_prepare): for the M usable shards the
+    whitened image ``Y`` [M, S, ldp] (y = inv(L)(theta - mu_M) / sqrt(M), one draw per row, pads zero),
+    ``n`` = |y|^2 and ``g`` = the shard's Gaussian exponent of the draw [M, S], ``lpv`` the lp__ values and
+    ``lp_w`` their weights (lp_row), the product moments ``mu`` [p] and ``L`` [p, p] (Sigma_M = L L^T), and
+    ``shard_used``.  draws as ``consensus`` takes them; the arrays lie where the draws lay (numpy arrays or
+    cuda tensors).  S <= p raises LinAlgError."""
+    dev = _device_stack(draws)
+    if dev is None and not isinstance(draws, (list, tuple)) and hasattr(draws, "numpy"):
+        draws = list(draws.numpy())
+    ctx = ctx or default_context()
+    if dev is not None:
+        import torch
+        ns, P, S = (int(v) for v in dev.shape)
+        if dev.device.index != ctx.device:
+            raise ValueError(f"draws on {dev.device} but the context is on cuda:{ctx.device}")
+        torch.cuda.current_stream(dev.device).synchronize()
+        new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev.device)   # noqa: E731
+        src = dev
+    else:
+        src, (P, S) = _stack(draws)
+        ns = len(draws)
+        new = lambda *shape: np.zeros(shape)   # noqa: E731
+    p = P - 1 if lp_row else P
+    if p < 1 or p > 1024 or ns > 4096 or S <= p:     # refused by name in the library, before any allocation
+        ldp = 8
+        arrs = {k: new(1) for k in ("mu", "L", "lp_w", "Y", "n", "g", "lpv")}
+    else:
+        ldp = (p + 7) // 8 * 8
+        arrs = {"mu": new(p), "L": new(p, p), "lp_w": new(ns), "Y": new(ns, S, ldp), "n": new(ns, S), "g": new(ns, S),
+                "lpv": new(ns, S)}
+    used = np.zeros(ns, np.int32)
+    n_used = np.zeros(1, np.int32)
+    check(_lib.load().stk_dpe_prepare(ctx._h, _ptr(src), ns, P, S, int(bool(lp_row)), used.ctypes.data,
+                                      n_used.ctypes.data, _ptr(arrs["mu"]), _ptr(arrs["L"]),
+                                      _ptr(arrs["lp_w"]) if lp_row else None, _ptr(arrs["Y"]), _ptr(arrs["n"]),
+                                      _ptr(arrs["g"]), _ptr(arrs["lpv"]) if lp_row else None))
+    M = int(n_used[0])
+    out = {"M": M, "p": p, "S": S, "ldp": ldp, "lp_row": bool(lp_row), "shard_used": used.astype(bool),
+           "mu": arrs["mu"], "L": arrs["L"]}
+    for k in ("Y", "n", "g", "lpv", "lp_w"):
+        out[k] = arrs[k][:M] if (lp_row or k not in ("lpv", "lp_w")) else None
+    return out
+
+
+def _dpe_info(accept, K, sweeps, h):
+    return {"accept": accept, "accept_rate": accept / float(K * sweeps), "h_first": float(h[0]), "h_last": float(h[-1]),
+            "h_min": float(h.min()), "h_max": float(h.max()), "sweeps": sweeps, "chains": K}
+
+
+def _dpe_call(fn, head, prep, T, chains, burn, thin, bandwidth, seed, stream, trace, out, to_ptr):
+    M, p, S = prep["M"], prep["p"], prep["S"]
+    T, K, sweeps, h = _dpe_chain_args(S, T, chains, burn, thin, bandwidth, p)
+    accept = np.zeros(M, np.int64)
+    tidx = np.zeros((K, sweeps, M), np.int32) if trace else None
+    tlogw = np.zeros((K, sweeps)) if trace else None
+    o = out(p + (1 if prep["lp_row"] else 0), max(T, 1))
+    check(fn(*head, M, p, S, to_ptr(prep["mu"]), to_ptr(prep["L"]), to_ptr(prep["lp_w"]) if prep["lp_row"] else None,
+             to_ptr(prep["Y"]), to_ptr(prep["n"]), to_ptr(prep["g"]), to_ptr(prep["lpv"]) if prep["lp_row"] else None,
+             int(seed), int(stream), T, K, int(burn), int(thin), h.ctypes.data, _ptr(o), accept.ctypes.data,
+             _ptr(tidx), _ptr(tlogw)))
+    info = _dpe_info(accept, K, sweeps, h)
+    if trace:
+        info["trace_idx"], info["trace_logw"] = tidx, tlogw
+    return o, info
+
+
+def dpe_sample(prep, T=None, chains=None, burn=200, thin=5, bandwidth=None, seed=0, stream=0, trace=False,
+               ctx: Context | None = None):
+    """T draws of the density product from ``dpe_prepare``'s arrays (stk_dpe_sample: k_dpe_img, one wavefront
+    per chain).  Returns (P x T, info); the draws lie where the prepared arrays lay.  info: ``accept`` (accepted
+    proposals per shard), ``accept_rate``, the bandwidth range, and with trace=True ``trace_idx``
+    [K, sweeps, M] (the index of coordinate m after its proposal) and ``trace_logw`` [K, sweeps].
+    Defaults: T = S, chains = min(T, 1024); burn and thin are those of a numpy prototype on a skewed
+    one-dimensional case, not tuned on hardware."""
+    ctx = ctx or default_context()
+    on_dev = hasattr(prep["Y"], "data_ptr")
+    keep = []
+
+    def to_ptr(a):
+        if a is None:
+            return None
+        c = a.contiguous() if on_dev else np.ascontiguousarray(a, np.float64)
+        keep.append(c)
+        return _ptr(c)
+
+    if on_dev:
+        import torch
+        torch.cuda.current_stream(prep["Y"].device).synchronize()
+        out = lambda P, T_: torch.empty((P, T_), dtype=torch.float64, device=prep["Y"].device)   # noqa: E731
+    else:
+        out = lambda P, T_: np.empty((P, T_))   # noqa: E731
+    return _dpe_call(_lib.load().stk_dpe_sample, (ctx._h,), prep, T, chains, burn, thin, bandwidth, seed, stream, trace,
+                     out, to_ptr)
+
+
+def dpe_sample_host(prep, T=None, chains=None, burn=200, thin=5, bandwidth=None, seed=0, stream=0, trace=False):
+    """``dpe_sample`` without a device (stk_dpe_sample_host): the kernel's arithmetic and sum orders on the
+    host, so index traces and accept counts are the kernel's.  Device-resident prepared arrays are copied."""
+    keep = []
+
+    def to_ptr(a):
+        if a is None:
+            return None
+        c = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, np.float64)
+        keep.append(c)
+        return c.ctypes.data
+
+    return _dpe_call(_lib.load().stk_dpe_sample_host, (), prep, T, chains, burn, thin, bandwidth, seed, stream, trace,
+                     lambda P, T_: np.empty((P, T_)), to_ptr)
+
+
+def consensus_dpe(draws, T=None, chains=None, burn=200, thin=5, bandwidth=None, seed=0, stream=0, lp_row=True,
+                  ctx: Context | None = None):
+    """Semiparametric density-product combine of subposterior draws (stk_consensus_dpe):
+    T draws of prod_m p_m(theta), each p_m the shard's Gaussian fit times a kernel correction, sampled by
+    independent Metropolis within Gibbs over index tuples.  Unlike ``consensus`` it does not assume Gaussian
+    subposteriors.  Returns (P x T, shard_used, info).
+
+    draws as ``consensus`` takes them; the result lies where the draws lay.  lp_row: the last row is lp__,
+    kept out of theta and combined as sum_m w_m lp^m at the chosen draws, w_m ~ 1 / var(lp^m).
+    bandwidth: None anneals h_r = (r + 1)^(-1 / (4 + p)) over the sweeps, a float holds it.
+    Defaults: T = S, chains = min(T, 1024).  burn = 200 and thin = 5 come from a numpy prototype (four
+    Gamma(3, 1) shards, h = 0.3); they are not tuned on hardware.
+    info: per-shard ``accept`` counts and ``accept_rate``, the h range, sweeps, chains."""
+    dev = _device_stack(draws)
+    if dev is None and not isinstance(draws, (list, tuple)) and hasattr(draws, "numpy"):
+        draws = list(draws.numpy())
+    if dev is not None:
+        ns, P, S = (int(v) for v in dev.shape)
+    else:
+        X, (P, S) = _stack(draws)
+        ns = len(draws)
+    p = P - 1 if lp_row else P
+    T, K, sweeps, h = _dpe_chain_args(S, T, chains, burn, thin, bandwidth, p)
+    ctx = ctx or default_context()
+    used = np.zeros(ns, np.int32)
+    accept = np.zeros(ns, np.int64)
+    if dev is not None:
+        import torch
+        if dev.device.index != ctx.device:
+            raise ValueError(f"draws on {dev.device} but the context is on cuda:{ctx.device}: pass a context "
+                             f"of the draws' device (engine.Context({dev.device.index}))")
+        out = torch.empty((P, max(T, 1)), dtype=torch.float64, device=dev.device)
+        torch.cuda.current_stream(dev.device).synchronize()
+        src = dev
+    else:
+        out = np.empty((P, max(T, 1)))
+        src = X
+    check(_lib.load().stk_consensus_dpe(ctx._h, _ptr(src), ns, P, S, int(bool(lp_row)), int(seed), int(stream), T, K,
+                                        int(burn), int(thin), h.ctypes.data, _ptr(out), used.ctypes.data,
+                                        accept.ctypes.data))
+    used = used.astype(bool)
+    return out, used, _dpe_info(accept[:int(used.sum())], K, sweeps, h)

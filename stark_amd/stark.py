@@ -420,8 +420,19 @@ class Stark:
         return (dist.all_gather_partitions(dict(zip(mine, draws)), len(parts)),
                 dist.all_gather_partitions(dict(zip(mine, weights)), len(parts)))
 
-    def concensusWeight(self, separate_lp=False, weights="sample", method="nuts", **kwargs):
+    def concensusWeight(self, separate_lp=False, weights="sample", method="nuts", combiner="consensus",
+                        combiner_args=None, **kwargs):
         """stark/stark.py:59-71: subposterior per partition, consensus weighted average.
+
+        combiner: "consensus" (default: the weighted average, everything below, bit for bit what omitting
+        the argument gives) or "semiparametric": the same subposteriors, sampled by method= as below, go
+        through ``engine.consensus_dpe``, the semiparametric density-product estimator, which does not
+        assume Gaussian subposteriors (skewed or small shards).  lp__ (the last row)
+        stays out of the product and is combined at the chosen draws.  ``combiner_args`` is a dict of
+        consensus_dpe's options (T, chains, burn, thin, bandwidth); the sampling seed seeds the index
+        chains too.  separate_lp and weights= have no meaning there: a non-default value raises ValueError
+        before anything is sampled.  Every rank combines the gathered draws itself, so all ranks hold the
+        same bits.  Works with method="nuts" and method="laplace" and every family, 8 schools included.
 
         method: "nuts" (default: every partition is sampled by NUTS, everything below, bit for bit what
         omitting the argument gives) or "laplace": every partition's draws are importance-resampled
@@ -470,6 +481,36 @@ class Stark:
             raise ValueError(f"weights must be 'sample' or 'laplace', got {weights!r}")
         if method not in ("nuts", "laplace"):
             raise ValueError(f"method must be 'nuts' or 'laplace', got {method!r}")
+        if combiner not in ("consensus", "semiparametric"):
+            raise ValueError(f"combiner must be 'consensus' or 'semiparametric', got {combiner!r}")
+        if combiner == "consensus" and combiner_args:
+            raise ValueError("combiner_args are the options of combiner='semiparametric'")
+        if combiner == "semiparametric":
+            if separate_lp or weights != "sample":
+                raise ValueError("combiner='semiparametric' keeps lp__ out of the product and forms its own weights: "
+                                 "separate_lp and weights= do not apply")
+            args = dict(combiner_args or {})
+            unknown = sorted(set(args) - {"T", "chains", "burn", "thin", "bandwidth"})
+            if unknown:
+                raise ValueError(f"combiner_args {unknown} are not options of engine.consensus_dpe "
+                                 "(T, chains, burn, thin, bandwidth)")
+            if kwargs.get("seed") is None:
+                kwargs["seed"] = int(np.random.SeedSequence().entropy) & 0x7FFFFFFF
+            if method == "laplace":
+                if self.family is None:
+                    raise RuntimeError("call setStanModel() first")
+                if self.family == "schools":
+                    raise ValueError("method='laplace' needs a regression family (linear, logistic, poisson): "
+                                     "8 schools has no Hessian or per-draw log-density sweep")
+            seed = kwargs["seed"]
+            kwargs = self._defaults(kwargs)
+            parts = _rdd.partitions_of(self.rdd)
+            if method == "laplace":
+                sub, _ = self._run_laplace_distributed(parts, False, **kwargs)
+            else:
+                sub = self._run_distributed(parts, **kwargs)
+            out, _, self.combiner_info = engine.consensus_dpe(sub, seed=seed, **args)
+            return out
         if method == "laplace":
             if self.family is None:
                 raise RuntimeError("call setStanModel() first")
