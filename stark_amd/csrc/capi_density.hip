@@ -119,6 +119,58 @@ static int hook_every_shard(stk_model* m, const std::vector<int>& sizes, const d
   return STK_OK;
 }
 
+// The sweeps over a draw image.  S draws q [S][D] are staged behind their image, with room for `extra`
+// doubles after them, and the image is built (one preparation launch, the log-predictive sweep's).
+struct DrawImage { double *img, *q; };
+static int stage_draws(stk_model* m, const double* q, int S, size_t extra, DrawImage* out) {
+  stk_ctx* ctx = m->ctx;
+  const size_t qn = (size_t)S * m->Dmax, img_bytes = stk_predictive_image_bytes(m->d, S);
+  RC(ctx->scratch[SCR_DRAW_IMG].ensure(img_bytes + sizeof(double) * (qn + extra)));
+  out->img = ctx->scratch[SCR_DRAW_IMG].as<double>();
+  out->q = out->img + img_bytes / sizeof(double);
+  STK_HIP_CHECK(hipMemcpyAsync(out->q, q, sizeof(double) * qn, hipMemcpyDefault, ctx->stream));
+  STK_HIP_CHECK(stk_launch_predictive_prep(m->family, m->d, m->Dmax, S, out->q, out->img, ctx->stream));
+  return STK_OK;
+}
+
+// The rows-and-totals contract of stk_log_predictive and stk_loo: the same S draws against one shard or
+// (shard == -1) every shard, one preparation launch, one sweep launch and one reduce launch for all of
+// them.  Per-row output goes straight to `rows` when that is memory of the context's device, else
+// through a staging buffer.
+typedef hipError_t (*RowsLaunch)(int family, const ShardDev* shards, int shard0, int nsh, int d, int Gs, int S,
+                                 const double* img, double* partial, double* rows, const int64_t* rowoff, double* totals,
+                                 hipStream_t st);
+static int rows_and_totals(stk_model* m, int shard, const double* q, int S, double* rows, double* totals, RowsLaunch launch,
+                           int (*chunks)(int64_t n)) {
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const ShardRange r = shard_range(m, shard, chunks);
+  const int shard0 = r.shard0, nsh = r.nsh, Gs = r.Gs;
+  std::vector<int64_t> off(nsh);
+  int64_t nrows = 0;
+  for (int s = 0; s < nsh; ++s) {
+    off[s] = nrows;
+    nrows += m->sh[shard0 + s].n;
+  }
+  RC(ctx->scratch[SCR_DRAW_PARTIAL].ensure(sizeof(double) * 8 * ((size_t)nsh * Gs + nsh) + sizeof(int64_t) * nsh));
+  double* partial = ctx->scratch[SCR_DRAW_PARTIAL].as<double>();
+  double* tb = partial + (size_t)nsh * Gs * 8;
+  int64_t* offb = reinterpret_cast<int64_t*>(tb + (size_t)nsh * 8);
+  const bool staged = rows && !is_device_ptr(rows, ctx->device);
+  if (staged) RC(ctx->scratch[SCR_DRAW_ROWS].ensure(sizeof(double) * 4 * (size_t)nrows));
+  double* rb = staged ? ctx->scratch[SCR_DRAW_ROWS].as<double>() : rows;
+  DrawImage di;                              // every buffer is there before anything is queued
+  RC(stage_draws(m, q, S, 0, &di));
+  STK_HIP_CHECK(hipMemcpyAsync(offb, off.data(), sizeof(int64_t) * nsh, hipMemcpyHostToDevice, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));   // off is a local
+  STK_HIP_CHECK(launch(m->family, m->sh_dev.as<ShardDev>(), shard0, nsh, m->d, Gs, S, di.img, partial, rb, offb, tb, st));
+  if (totals) STK_HIP_CHECK(hipMemcpyAsync(totals, tb, sizeof(double) * 8 * nsh, hipMemcpyDefault, st));
+  if (staged) STK_HIP_CHECK(hipMemcpyAsync(rows, rb, sizeof(double) * 4 * (size_t)nrows, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
 extern "C" {
 
 // ---------------------------------------------------------------- lp / grad (parity hook)
@@ -262,9 +314,6 @@ int stk_predictive_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out
   return STK_OK;
 }
 
-// The same S draws against one shard or (shard == -1) every shard: one preparation launch, one sweep
-// launch and one reduce launch for all of them.  Per-row output goes straight to `rows` when that is
-// memory of the context's device, else through a staging buffer.
 int stk_log_predictive(stk_model* m, int shard, const double* q, int32_t S, double* rows, double* totals) {
   ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_log_predictive: bad model or shard");
   ARG_CHECK(is_regression(m->family), "stk_log_predictive: no log-predictive sweep for the %s family (regressions only)",
@@ -276,39 +325,7 @@ int stk_log_predictive(stk_model* m, int shard, const double* q, int32_t S, doub
   ARG_CHECK(q, "stk_log_predictive: q is NULL (%s family, d = %d)", family_name(m->family), m->d);
   ARG_CHECK(rows || totals, "stk_log_predictive: rows and totals are both NULL (%s family, d = %d)", family_name(m->family),
             m->d);
-  stk_ctx* ctx = m->ctx;
-  STK_HIP_CHECK(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int D = m->Dmax;
-  const ShardRange r = shard_range(m, shard, stk_predictive_chunks);
-  const int shard0 = r.shard0, nsh = r.nsh, Gs = r.Gs;
-  std::vector<int64_t> off(nsh);
-  int64_t nrows = 0;
-  for (int s = 0; s < nsh; ++s) {
-    off[s] = nrows;
-    nrows += m->sh[shard0 + s].n;
-  }
-  const size_t qn = (size_t)S * D, img_bytes = stk_predictive_image_bytes(m->d, S);
-  RC(ctx->scratch[SCR_PRED_IMG].ensure(img_bytes + sizeof(double) * qn));
-  RC(ctx->scratch[SCR_PRED_PARTIAL].ensure(sizeof(double) * 8 * ((size_t)nsh * Gs + nsh) + sizeof(int64_t) * nsh));
-  double* img = ctx->scratch[SCR_PRED_IMG].as<double>();
-  double* qb = img + img_bytes / sizeof(double);
-  double* partial = ctx->scratch[SCR_PRED_PARTIAL].as<double>();
-  double* tb = partial + (size_t)nsh * Gs * 8;
-  int64_t* offb = reinterpret_cast<int64_t*>(tb + (size_t)nsh * 8);
-  const bool staged = rows && !is_device_ptr(rows, ctx->device);
-  if (staged) RC(ctx->scratch[SCR_PRED_ROWS].ensure(sizeof(double) * 4 * (size_t)nrows));
-  double* rb = staged ? ctx->scratch[SCR_PRED_ROWS].as<double>() : rows;
-  STK_HIP_CHECK(hipMemcpyAsync(qb, q, sizeof(double) * qn, hipMemcpyDefault, st));
-  STK_HIP_CHECK(hipMemcpyAsync(offb, off.data(), sizeof(int64_t) * nsh, hipMemcpyHostToDevice, st));
-  STK_HIP_CHECK(hipStreamSynchronize(st));   // off is a local
-  STK_HIP_CHECK(stk_launch_predictive_prep(m->family, m->d, D, S, qb, img, st));
-  STK_HIP_CHECK(stk_launch_predictive(m->family, m->sh_dev.as<ShardDev>(), shard0, nsh, m->d, Gs, S, img, partial, rb,
-                                      offb, tb, st));
-  if (totals) STK_HIP_CHECK(hipMemcpyAsync(totals, tb, sizeof(double) * 8 * nsh, hipMemcpyDefault, st));
-  if (staged) STK_HIP_CHECK(hipMemcpyAsync(rows, rb, sizeof(double) * 4 * (size_t)nrows, hipMemcpyDefault, st));
-  STK_HIP_CHECK(hipStreamSynchronize(st));
-  return STK_OK;
+  return rows_and_totals(m, shard, q, S, rows, totals, stk_launch_predictive, stk_predictive_chunks);
 }
 
 // ---------------------------------------------------------------- PSIS-LOO sweep (loo.hip)
@@ -327,8 +344,6 @@ int stk_loo_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]) {
   return STK_OK;
 }
 
-// stk_log_predictive's contract: the same S draws against one shard or (shard == -1) every shard, one
-// preparation launch (the log-predictive sweep's draw image), one sweep launch and one reduce launch.
 int stk_loo(stk_model* m, int shard, const double* q, int32_t S, double* rows, double* totals) {
   ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_loo: bad model or shard");
   ARG_CHECK(is_regression(m->family), "stk_loo: no PSIS-LOO sweep for the %s family (regressions only)", family_name(m->family));
@@ -340,38 +355,7 @@ int stk_loo(stk_model* m, int shard, const double* q, int32_t S, double* rows, d
             S, stk_loo_max_draws(), family_name(m->family), m->d);
   ARG_CHECK(q, "stk_loo: q is NULL (%s family, d = %d)", family_name(m->family), m->d);
   ARG_CHECK(rows || totals, "stk_loo: rows and totals are both NULL (%s family, d = %d)", family_name(m->family), m->d);
-  stk_ctx* ctx = m->ctx;
-  STK_HIP_CHECK(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int D = m->Dmax;
-  const ShardRange r = shard_range(m, shard, stk_loo_chunks);
-  const int shard0 = r.shard0, nsh = r.nsh, Gs = r.Gs;
-  std::vector<int64_t> off(nsh);
-  int64_t nrows = 0;
-  for (int s = 0; s < nsh; ++s) {
-    off[s] = nrows;
-    nrows += m->sh[shard0 + s].n;
-  }
-  const size_t qn = (size_t)S * D, img_bytes = stk_predictive_image_bytes(m->d, S);
-  RC(ctx->scratch[SCR_LOO_IMG].ensure(img_bytes + sizeof(double) * qn));
-  RC(ctx->scratch[SCR_LOO_PARTIAL].ensure(sizeof(double) * 8 * ((size_t)nsh * Gs + nsh) + sizeof(int64_t) * nsh));
-  double* img = ctx->scratch[SCR_LOO_IMG].as<double>();
-  double* qb = img + img_bytes / sizeof(double);
-  double* partial = ctx->scratch[SCR_LOO_PARTIAL].as<double>();
-  double* tb = partial + (size_t)nsh * Gs * 8;
-  int64_t* offb = reinterpret_cast<int64_t*>(tb + (size_t)nsh * 8);
-  const bool staged = rows && !is_device_ptr(rows, ctx->device);
-  if (staged) RC(ctx->scratch[SCR_LOO_ROWS].ensure(sizeof(double) * 4 * (size_t)nrows));
-  double* rb = staged ? ctx->scratch[SCR_LOO_ROWS].as<double>() : rows;
-  STK_HIP_CHECK(hipMemcpyAsync(qb, q, sizeof(double) * qn, hipMemcpyDefault, st));
-  STK_HIP_CHECK(hipMemcpyAsync(offb, off.data(), sizeof(int64_t) * nsh, hipMemcpyHostToDevice, st));
-  STK_HIP_CHECK(hipStreamSynchronize(st));   // off is a local
-  STK_HIP_CHECK(stk_launch_predictive_prep(m->family, m->d, D, S, qb, img, st));
-  STK_HIP_CHECK(stk_launch_loo(m->family, m->sh_dev.as<ShardDev>(), shard0, nsh, m->d, Gs, S, img, partial, rb, offb, tb, st));
-  if (totals) STK_HIP_CHECK(hipMemcpyAsync(totals, tb, sizeof(double) * 8 * nsh, hipMemcpyDefault, st));
-  if (staged) STK_HIP_CHECK(hipMemcpyAsync(rows, rb, sizeof(double) * 4 * (size_t)nrows, hipMemcpyDefault, st));
-  STK_HIP_CHECK(hipStreamSynchronize(st));
-  return STK_OK;
+  return rows_and_totals(m, shard, q, S, rows, totals, stk_launch_loo, stk_loo_chunks);
 }
 
 // ---------------------------------------------------------------- per-draw log-density sweep (logdens.hip)
@@ -406,17 +390,13 @@ int stk_log_density_draws(stk_model* m, int shard, const double* q, int32_t S, d
   hipStream_t st = ctx->stream;
   const int D = m->Dmax;
   const ShardRange r = shard_range(m, shard, stk_logdens_chunks);
-  const size_t qn = (size_t)S * D, img_bytes = stk_predictive_image_bytes(m->d, S);
   const size_t Sp = (size_t)16 * stk_predictive_tiles(S), lpn = (size_t)r.nsh * S;
-  RC(ctx->scratch[SCR_LOGDENS_IMG].ensure(img_bytes + sizeof(double) * (qn + lpn)));
-  RC(ctx->scratch[SCR_LOGDENS_PARTIAL].ensure(sizeof(double) * (size_t)r.nsh * r.Gs * Sp));
-  double* img = ctx->scratch[SCR_LOGDENS_IMG].as<double>();
-  double* qb = img + img_bytes / sizeof(double);
-  double* lpb = qb + qn;
-  STK_HIP_CHECK(hipMemcpyAsync(qb, q, sizeof(double) * qn, hipMemcpyDefault, st));
-  STK_HIP_CHECK(stk_launch_predictive_prep(m->family, m->d, D, S, qb, img, st));
-  STK_HIP_CHECK(stk_launch_logdens(m->family, m->sh_dev.as<ShardDev>(), r.shard0, r.nsh, m->d, D, r.Gs, S, img, qb,
-                                   ctx->scratch[SCR_LOGDENS_PARTIAL].as<double>(), lpb, st));
+  RC(ctx->scratch[SCR_DRAW_PARTIAL].ensure(sizeof(double) * (size_t)r.nsh * r.Gs * Sp));
+  DrawImage di;
+  RC(stage_draws(m, q, S, lpn, &di));
+  double* lpb = di.q + (size_t)S * D;
+  STK_HIP_CHECK(stk_launch_logdens(m->family, m->sh_dev.as<ShardDev>(), r.shard0, r.nsh, m->d, D, r.Gs, S, di.img, di.q,
+                                   ctx->scratch[SCR_DRAW_PARTIAL].as<double>(), lpb, st));
   STK_HIP_CHECK(hipMemcpyAsync(lp, lpb, sizeof(double) * lpn, hipMemcpyDefault, st));
   STK_HIP_CHECK(hipStreamSynchronize(st));
   return STK_OK;

@@ -57,15 +57,15 @@ struct DevBuf {
 
 // The context's grow-only scratch buffers, each named after the one entry-point family that owns
 // it: an entry point may call another family's while it holds its own (the Hessian calls the hooks).
+// The three sweeps over a draw image (predictive, PSIS-LOO, per-draw log density) are one family:
+// they never call one another, and each synchronises before it returns.
 enum Scratch : int {
   SCR_HOOK_Q, SCR_HOOK_LP, SCR_HOOK_GRAD,   // parity hooks (regression and schools): points, lp, grad
   SCR_HOOK_PARTIAL, SCR_HOOK_WS,            // regression hooks: partial sums, 64-chain workspace
   SCR_FP_SUM, SCR_FP_STAGE,                 // fingerprints: the device sum, staging of host words
   SCR_HESS_WS, SCR_HESS_QH,                 // Hessian: chunk-partial workspace, points and result
   SCR_COMB_F64, SCR_COMB_MAT, SCR_COMB_I32, // combine: draws-sized doubles, P x P matrices, ints
-  SCR_PRED_IMG, SCR_PRED_PARTIAL, SCR_PRED_ROWS,   // predictive: draw image, partials, per-row staging
-  SCR_LOO_IMG, SCR_LOO_PARTIAL, SCR_LOO_ROWS,      // PSIS-LOO: draw image, partials, per-row staging
-  SCR_LOGDENS_IMG, SCR_LOGDENS_PARTIAL,            // per-draw log density: draw image + draws + lp, partials
+  SCR_DRAW_IMG, SCR_DRAW_PARTIAL, SCR_DRAW_ROWS,   // draw-image sweeps: image + draws (+ lp), partials, per-row staging
   SCR_LAPLACE,                                     // Laplace proposal: mode, factor, draws, log_q
   SCR_BOOT_IO, SCR_BOOT_PARTIAL,                   // bootstrap sweep: points + streams + lp, grad, wsum; partials
   SCR_DPE_IN, SCR_DPE_MOM, SCR_DPE_PREP, SCR_DPE_WS,   // density-product combiner: staged draws; the combine's moments;

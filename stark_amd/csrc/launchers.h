@@ -8,11 +8,6 @@ namespace stk {
 
 struct SweepArgs;   // sweep_common.h (device side)
 
-// The draw image of k_predictive_prep (predictive.hip), which loo.hip reads too: k-steps per draw tile,
-// and doubles per draw tile: the k-steps, 64 per-draw scalars, padded to a whole number of block-wide copies
-__host__ __device__ constexpr int pred_kf(int d) { return (d + 3) / 4; }
-__host__ __device__ constexpr int pred_slab(int kf) { return (kf * 64 + 64 + 255) / 256 * 256; }
-
 // Which regression sweep runs; the numbers are those of tests/golden/sweep_launch.json.
 enum SweepKind : int {
   SWEEP_NONE = 0,     // no sweep: the chunk bytes do not fit a buffer descriptor, or (C, d) has no kernel

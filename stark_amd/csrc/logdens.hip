@@ -5,32 +5,27 @@
 // (the definitions are in include/stark_hip.h).  The second half of the file is
 // the proposal itself: k_laplace_draws.
 //
-//   eta_is = alpha_s + x_i . beta_s           the forward half of k_predictive, for S draws
+//   eta_is = alpha_s + x_i . beta_s           draw_forward.h's forward pass, for S draws
 //   logistic  t = (2 y_i - 1) eta, e = exp(-|t|):  sum_i ll = sum (t - |t|) / 2 - log prod (1 + e)
 //   poisson   sum_i ll = sum y_i eta - exp(eta)                                  (propto: no lgamma)
 //   linear    the sweep carries sum (y_i - eta)^2; the reduce finishes -e^{-2u} sum / 2 - n u
 //   lp_s = sum_i ll + prior + Jacobian, the terms of k_sweep_reduce (sweep.hip)
 //
-// k_logdens: k_predictive's forward half as it stands -- the k_predictive_prep draw image, 4 waves per
-// block and two blocks per CU, chunks of whole 64-row groups that depend only on n, a wave's 16 rows held
-// as the A operand in registers for the whole draw loop, every draw-tile slab shared by the four waves
-// through the two-slot LDS ring.  Per draw tile a wave forms eta[16 rows][16 draws] (lane (lr, lg): rows
-// lg + 4 i of draw lr) and reduces the other way from k_predictive: the lane's four elements are summed
-// (logistic: the four 1 + e multiplied and ONE log taken, the sweeps' running product cut at the tile),
-// then the four lane groups in a fixed order: one number per (wave, draw).  The four waves' numbers meet
-// in a small double-buffered LDS array; wave 0 adds them in wave order to the chunk's running sum of
-// that draw, which lives in the chunk's row of the partial buffer (read, add, write by the same lane
-// every time: program order; the first group of a chunk writes without reading, so the buffer needs no
-// zeroing).  A chunk's working set is S doubles: it stays in L2.
+// k_logdens: k_predictive's launch shape (4 waves per block, two blocks per CU, chunks of whole 64-row
+// groups, the slab ring) with the element work reduced the other way: the lane's four elements are summed
+// (logistic: the four 1 + e multiplied and ONE log taken, the sweeps' running product cut at the tile --
+// so not draw_ll, which takes a log1p per element), then the four lane groups in a fixed order: one
+// number per (wave, draw).  The four waves' numbers meet in a small double-buffered LDS array; wave 0
+// adds them in wave order to the chunk's running sum of that draw, which lives in the chunk's row of
+// the partial buffer (read, add, write by the same lane every time: program order; the first group of
+// a chunk writes without reading, so the buffer needs no zeroing).  A chunk's working set is S doubles:
+// it stays in L2.
 // Rows past n are masked out by select, never by a product, so a NaN draw stays NaN and a finite draw is
 // never touched by a padding row.  Draw s is column s & 15 of tile s >> 4; an MFMA output column depends
 // on its own B column only, every sum above runs in an order fixed by (n, d), and k_logdens_reduce adds
 // the chunks in chunk order: lp_s depends on draw s and the shard alone, bit for bit -- not on S, on
 // the position in q, on its companions or on how many shards share the launch.
-#include "launchers.h"
-#include "sweep_common.h"
-#include "predictive_math.h"
-#include <math.h>
+#include "draw_forward.h"
 #include <algorithm>
 
 namespace stk {
@@ -41,10 +36,7 @@ constexpr int LD_GPC = 4;         // 64-row groups per chunk before the chunk co
 constexpr int LD_GMAX = 256;      // chunks per shard at most
 constexpr int LD_RED = 2 * LD_W * 16;   // the waves' per-draw sums of two tiles
 
-__host__ __device__ inline int logdens_chunks(int64_t n) {
-  const int64_t ng = (n + LD_R * LD_W - 1) / (LD_R * LD_W), g = (ng + LD_GPC - 1) / LD_GPC;
-  return (int)(g < 1 ? 1 : (g > LD_GMAX ? LD_GMAX : g));
-}
+__host__ __device__ inline int logdens_chunks(int64_t n) { return draw_chunks(draw_units(n, LD_R * LD_W), LD_GPC, LD_GMAX); }
 // the exp table, the waves' sums, then ONE area that holds the four waves' rows while a group starts and
 // the slab ring after
 __host__ __device__ constexpr size_t logdens_lds_doubles(int d) {
@@ -63,7 +55,6 @@ struct LogdensArgs {
 
 template <int FAM, int KF>
 __global__ __launch_bounds__(64 * LD_W, 2) void k_logdens(LogdensArgs A) {
-  constexpr int SLAB = pred_slab(KF), NPF = SLAB / (64 * LD_W);
   const int si = blockIdx.y, chunk = blockIdx.x;
   const ShardDev sh = A.shards[A.shard0 + si];
   const int G = logdens_chunks(sh.n);
@@ -81,10 +72,9 @@ __global__ __launch_bounds__(64 * LD_W, 2) void k_logdens(LogdensArgs A) {
   double* const xs = ring + (size_t)w * LD_R * d;    // [16][d] the wave's rows, before the ring is filled
   if constexpr (!LIN) exp_table_init(tab);
 
-  const int64_t ng = (sh.n + LD_R * LD_W - 1) / (LD_R * LD_W);
-  const int64_t g0 = ng * chunk / G, g1 = ng * (chunk + 1) / G;
+  const UnitRange groups = draw_chunk_units(draw_units(sh.n, LD_R * LD_W), chunk, G);
   const gptr_t<double> xg = gp(sh.x);
-  const gptr_t<double> img = gp(A.img);
+  SlabRing<KF, LD_W> slabs{ring, gp(A.img), tid};
   const int64_t lim = sh.n * d;
   double* const acc = A.partial + ((size_t)si * A.Gs + chunk) * ((size_t)16 * A.ntile);
 
@@ -98,58 +88,30 @@ __global__ __launch_bounds__(64 * LD_W, 2) void k_logdens(LogdensArgs A) {
     }
   };
 
-  for (int64_t grp = g0; grp < g1; ++grp) {
+  for (int64_t grp = groups.first; grp < groups.last; ++grp) {
     const int64_t row0 = grp * (LD_R * LD_W) + w * LD_R;
-    const bool first = grp == g0;
-    double yv[4];
+    const bool first = grp == groups.first;
+    double yv[4], lgam[4];                           // no lgamma here: propto
     bool ok[4];
+    draw_row_y<FAM, false>(sh, row0, lr, lg, yv, lgam);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t row = row0 + lg + 4 * i;
-      ok[i] = row < sh.n;
-      yv[i] = 0.0;
-      if (ok[i]) yv[i] = LIN ? sh.y[row] : (double)sh.yi[row];
-    }
-    // ---- the wave's 16 rows: contiguous in HBM, through the slot, into the A registers
-    const int64_t base = row0 * d;
-    for (int i = lane; i < LD_R * d; i += 64) xs[i] = base + i < lim ? __builtin_nontemporal_load(xg + base + i) : 0.0;
+    for (int i = 0; i < 4; ++i) ok[i] = row0 + lg + 4 * i < sh.n;
+    // ---- the wave's 16 rows into the A registers
+    draw_stage_rows(xs, xg, row0 * d, lim, d, lane, 64);
     __syncthreads();
     double a[KF];
-#pragma unroll
-    for (int s = 0; s < KF; ++s) {
-      const int col = 4 * s + lg;
-      a[s] = col < d ? xs[lr * d + col] : 0.0;
-    }
+    draw_load_a<KF>(xs, d, lr, lg, a);
     __syncthreads();                                 // every wave has its rows: the area becomes the ring
-    double pf[NPF];
-#pragma unroll
-    for (int j = 0; j < NPF; ++j) {
-      const int k = tid + 64 * LD_W * j;
-      ring[k] = img[k];
-    }
+    slabs.fill_first();
     __syncthreads();
 
 #pragma nounroll                                      // one copy of the body
     for (int t = 0; t < A.ntile; ++t) {
-      const double* B = ring + (t & 1) * SLAB;
-      const double alpha = B[KF * 64 + lr];
-      dbl4 e0 = dbl4{alpha, alpha, alpha, alpha}, e1 = dbl4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s = 0; s < KF; ++s) {
-        if (s & 1) e1 = mfma_f64(a[s], B[s * 64 + lane], e1);
-        else e0 = mfma_f64(a[s], B[s * 64 + lane], e0);
-        if ((s & 7) == 7) __builtin_amdgcn_sched_barrier(0);   // B reads at most 8 k-steps ahead: registers
-      }
-      const dbl4 eta4 = e0 + e1;
+      const double* B = slabs.slab(t);
+      const dbl4 eta4 = draw_eta<KF>(a, B, B[KF * 64 + lr], lane);
       __builtin_amdgcn_sched_barrier(0);
       // the next slab, into registers while the element work runs (the B operands' registers are free now)
-      if (t + 1 < A.ntile) {
-#pragma unroll
-        for (int j = 0; j < NPF; ++j) {
-          const int k = tid + 64 * LD_W * j;
-          pf[j] = img[(size_t)(t + 1) * SLAB + k];
-        }
-      }
+      if (t + 1 < A.ntile) slabs.prefetch(t + 1);
       if (t > 0) flush(t - 1, first);                // the barrier that ended tile t - 1 published its sums
       double v;
       if constexpr (LOGI) {
@@ -185,14 +147,7 @@ __global__ __launch_bounds__(64 * LD_W, 2) void k_logdens(LogdensArgs A) {
       // the four lane groups of draw lr, in a fixed order; lanes of group 0 hand the wave's sum over
       const double v1 = __shfl(v, lr + 16), v2 = __shfl(v, lr + 32), v3 = __shfl(v, lr + 48);
       if (lg == 0) red[(t & 1) * (LD_W * 16) + w * 16 + lr] = ((v + v1) + v2) + v3;
-      if (t + 1 < A.ntile) {
-        double* Bn = ring + ((t + 1) & 1) * SLAB;
-#pragma unroll
-        for (int j = 0; j < NPF; ++j) {
-          const int k = tid + 64 * LD_W * j;
-          Bn[k] = pf[j];
-        }
-      }
+      if (t + 1 < A.ntile) slabs.commit(t + 1);
       __syncthreads();
     }
     flush(A.ntile - 1, first);                       // before the next group's barriers: its slot is reused after them
@@ -235,19 +190,6 @@ static hipError_t go_logdens(const LogdensArgs& A, int d, int nsh, hipStream_t s
     if (const hipError_t e = allow_big_lds(reinterpret_cast<const void*>(kern))) return e;
   hipLaunchKernelGGL(kern, dim3(A.Gs, nsh), dim3(64 * LD_W), lds, st, A);
   return hipGetLastError();
-}
-
-template <int FAM>
-static hipError_t launch_logdens(const LogdensArgs& A, int d, int nsh, hipStream_t st) {
-  switch (pred_kf(d)) {
-#define STK_LD(K) case K: return go_logdens<FAM, K>(A, d, nsh, st);
-    STK_LD(1) STK_LD(2) STK_LD(3) STK_LD(4) STK_LD(5) STK_LD(6) STK_LD(7) STK_LD(8)
-    STK_LD(9) STK_LD(10) STK_LD(11) STK_LD(12) STK_LD(13) STK_LD(14) STK_LD(15) STK_LD(16)
-    STK_LD(17) STK_LD(18) STK_LD(19) STK_LD(20) STK_LD(21) STK_LD(22) STK_LD(23) STK_LD(24)
-    STK_LD(25) STK_LD(26) STK_LD(27) STK_LD(28) STK_LD(29) STK_LD(30) STK_LD(31) STK_LD(32)
-#undef STK_LD
-  }
-  return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------- the Laplace proposal
@@ -304,10 +246,9 @@ size_t stk_logdens_ws_bytes(int64_t n, int S) {
 hipError_t stk_launch_logdens(int family, const ShardDev* shards, int shard0, int nsh, int d, int D, int Gs, int S,
                               const double* img, const double* q, double* partial, double* lp, hipStream_t st) {
   const LogdensArgs A{shards, img, q, partial, lp, family, shard0, Gs, S, stk_predictive_tiles(S), D};
-  hipError_t e = hipErrorInvalidValue;
-  if (family == STK_LOGREG) e = launch_logdens<STK_LOGREG>(A, d, nsh, st);
-  else if (family == STK_LINREG) e = launch_logdens<STK_LINREG>(A, d, nsh, st);
-  else if (family == STK_POISSON) e = launch_logdens<STK_POISSON>(A, d, nsh, st);
+  const hipError_t e = draw_dispatch(family, d, [&](auto fam, auto kf) {
+    return go_logdens<decltype(fam)::value, decltype(kf)::value>(A, d, nsh, st);
+  });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_logdens_reduce, dim3((unsigned)((S + 255) / 256), nsh), dim3(256), 0, st, A);
   return hipGetLastError();

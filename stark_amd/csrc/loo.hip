@@ -6,12 +6,12 @@
 // The n x S matrix of log ratios never reaches HBM: a workgroup owns one 16-row MFMA tile at a time and
 // keeps the tile's [16][Sp] log ratios in LDS (Sp = S padded to a power of two, 128 KB at Sp = 1024).
 //
-//   forward   The tile's 16 rows go from HBM (nontemporal) through an LDS slot into EVERY wave's registers
-//             as the same A operand of v_mfma_f64_16x16x4.  The waves split the 16-draw tiles of
-//             k_predictive_prep's K-major image (tile t to wave t mod W); a slab is read by exactly one
-//             wave of the block, so its B operands come straight from global memory (L2) into registers,
-//             512 B per k-step, with no LDS ring.  ll is k_predictive's, to the instruction; the wave
-//             writes lr = -ll to mat[row][draw].  A draw lane of the last tile past S and the columns up
+//   forward   draw_forward.h's forward pass; ll is its draw_ll, the other pieces are written out here (KEPT,
+//             below).  The tile's 16 rows go into EVERY wave's registers as the same A
+//             operand.  The waves split the 16-draw tiles of the image (tile t to wave t mod W); a slab
+//             is read by exactly one wave of the block, so its B operands come straight from global
+//             memory (L2) into registers, 512 B per k-step, with no LDS ring.  The wave writes
+//             lr = -ll to mat[row][draw].  A draw lane of the last tile past S and the columns up
 //             to Sp hold -inf, which sorts to the front.  A non-finite ll sets the row's flag (1: -inf,
 //             2: NaN, 4: +inf) and is stored as +inf (-inf for ll = +inf), so the sort never meets a NaN.
 //   sort      A block is W = 4 waves (8 from Sp = 512).  Wave w takes the 16 / W rows from (16 / W) w and
@@ -29,13 +29,10 @@
 // so the row stride is Sp with no padding; compare-exchange strides below 32 read two-way conflicted.
 //
 // A shard is cut into G chunks of whole 16-row tiles, G a function of n alone (and W of S alone).  A
-// row's four values depend only on (x_i, y_i) and the draws.  Every chunk writes its partial totals
-// (wave order, then row order); k_loo_reduce sums them in chunk order, so the totals are bitwise
-// independent of how many shards share a launch and of which GPU runs a shard.
-#include "launchers.h"
-#include "sweep_common.h"
+// row's four values depend only on (x_i, y_i) and the draws.  A chunk's partial totals are summed in
+// wave order, then row order.
+#include "draw_forward.h"
 #include "psis_math.h"
-#include <math.h>
 #include <algorithm>
 
 namespace stk {
@@ -47,7 +44,14 @@ constexpr int LO_TPC = 2;         // tiles per chunk before the chunk count satu
 constexpr int LO_GMAX = 512;      // chunks per shard at most
 constexpr int LO_SCR = PSIS_MMAX + 2 * 40;   // per-wave scratch doubles: exceedances, profile, theta * weight
 
-__host__ __device__ inline int loo_chunks(int64_t n) {
+// KEPT.  k_loo shares with draw_forward.h only what leaves every one of its instantiations the instructions
+// it had before that header existed: draw_ll and draw_chunk_units.  With any of draw_chunks (below),
+// draw_row_y, draw_stage_rows, draw_load_a or a PredArgs inside LooArgs, the compiler orders and places
+// the same work differently, and the 4-wave kernel at S = 256 then ran 0.5 to 1 % slower in every run
+// (8 shards x 1.25e7 rows, d = 100); with draw_eta the 8-wave linear kernels at KF 29, 31, 32 also spilled.
+// So those pieces stand here as k_predictive had them; tools/codeobj_compare.py shows whether a change
+// to either copy still leaves k_loo's text alone.
+__host__ __device__ inline int loo_chunks(int64_t n) {   // draw_chunks(draw_units(n, LO_R), LO_TPC, LO_GMAX)
   const int64_t nt = (n + LO_R - 1) / LO_R, g = (nt + LO_TPC - 1) / LO_TPC;
   return (int)(g < 1 ? 1 : (g > LO_GMAX ? LO_GMAX : g));
 }
@@ -64,6 +68,8 @@ __host__ __device__ inline size_t loo_lds_doubles(int d, int S) {
   return (size_t)EX_TAB + loo_area(d) + (size_t)LO_R * loo_sp(S) + LO_R / 2;
 }
 
+// PredArgs's fields, then three more -- written out, not derived: a PredArgs base or member is padded to 72
+// bytes and moves Sp, M and Mg in the kernel's argument segment, which is among what KEPT below is about
 struct LooArgs {
   const ShardDev* shards;
   const double* img;        // [ntile][slab] the draw image
@@ -173,8 +179,7 @@ __global__ __launch_bounds__(64 * LO_W) void k_loo(LooArgs A) {
   const int G = loo_chunks(sh.n);
   if (chunk >= G) return;                            // block-uniform
   const int d = sh.d, S = A.S, Sp = A.Sp;
-  constexpr bool LIN = FAM == STK_LINREG, LOGI = FAM == STK_LOGREG, POIS = FAM == STK_POISSON;
-  static_assert(LIN || LOGI || POIS, "k_loo: unknown family");
+  constexpr bool LIN = FAM == STK_LINREG, POIS = FAM == STK_POISSON;
   const int tid = threadIdx.x, lane = tid & 63, w = uniform_int(tid >> 6);
   const int lr = lane & 15, lg = lane >> 4;
 
@@ -185,8 +190,7 @@ __global__ __launch_bounds__(64 * LO_W) void k_loo(LooArgs A) {
   int* const flags = reinterpret_cast<int*>(mat + (size_t)LO_R * Sp);   // [16]
   exp_table_init(tab);
 
-  const int64_t nt = (sh.n + LO_R - 1) / LO_R;
-  const int64_t t0 = nt * chunk / G, t1 = nt * (chunk + 1) / G;
+  const UnitRange tiles = draw_chunk_units(draw_units(sh.n, LO_R), chunk, G);
   const gptr_t<double> xg = gp(sh.x);
   const gptr_t<double> img = gp(A.img);
   const int64_t lim = sh.n * d;
@@ -194,9 +198,9 @@ __global__ __launch_bounds__(64 * LO_W) void k_loo(LooArgs A) {
   const int padc = Sp - 16 * A.ntile;                // columns no draw tile writes
   double tot[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // sum lppd, p_loo, elpd, elpd^2, #k > 0.5, #k > 0.7, #non-finite
 
-  for (int64_t tile = t0; tile < t1; ++tile) {
+  for (int64_t tile = tiles.first; tile < tiles.last; ++tile) {
     const int64_t row0 = tile * LO_R;
-    // y of rows lg + 4 i; poisson: lgamma(y + 1) once per row (lane lr takes row lr) and handed round
+    // draw_row_y<FAM, true> (KEPT): y of rows lg + 4 i; poisson: lgamma(y + 1) once per row and handed round
     double yv[4], lgam[4], lgr = 0.0;
     if constexpr (POIS) {
       const int64_t row = row0 + lr;
@@ -210,7 +214,7 @@ __global__ __launch_bounds__(64 * LO_W) void k_loo(LooArgs A) {
       lgam[i] = POIS ? __shfl(lgr, lg + 4 * i) : 0.0;
     }
     __builtin_amdgcn_sched_barrier(0);               // lgamma is done before the rows take their registers
-    // ---- the tile's 16 rows: contiguous in HBM, through the slot, into every wave's A registers
+    // ---- draw_stage_rows and draw_load_a (KEPT): the tile's 16 rows into every wave's A registers
     const int64_t base = row0 * d;
     for (int i = tid; i < LO_R * d; i += 64 * LO_W) area[i] = base + i < lim ? __builtin_nontemporal_load(xg + base + i) : 0.0;
     if (tid < LO_R) flags[tid] = 0;
@@ -229,6 +233,7 @@ __global__ __launch_bounds__(64 * LO_W) void k_loo(LooArgs A) {
       const gptr_t<double> B = img + (size_t)t * SLAB;
       const double alpha = B[KF * 64 + lr], u = B[KF * 64 + 16 + lr], e2u = B[KF * 64 + 32 + lr];
       const bool live = B[KF * 64 + 48 + lr] != 0.0;
+      // draw_eta's loop (KEPT), without its (s & 7) fence and with B in global memory
       dbl4 e0 = dbl4{alpha, alpha, alpha, alpha}, e1 = dbl4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int s = 0; s < KF; ++s) {
@@ -238,21 +243,8 @@ __global__ __launch_bounds__(64 * LO_W) void k_loo(LooArgs A) {
       const dbl4 eta4 = e0 + e1;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const double eta = eta4[i];
-        double ll;
-        if constexpr (LOGI) {
-          const double z = yv[i] != 0.0 ? eta : -eta;
-          const double e = pd_exp(-fabs(eta), tab);
-          const double lt = (z < 0.0 ? z : 0.0) - pd_log1p01(e);
-          ll = eta != eta ? eta : lt;                // pd_exp turns a NaN into 0: put it back
-        } else if constexpr (LIN) {
-          const double r = yv[i] - eta;
-          ll = -0.91893853320467274178 - u - 0.5 * (r * r) * e2u;
-        } else {
-          double g = pd_exp(eta, tab);
-          g = eta != eta ? eta : g;
-          ll = yv[i] * eta - g - lgam[i];
-        }
+        double g;                                    // not used here
+        const double ll = draw_ll<FAM>(eta4[i], yv[i], lgam[i], u, e2u, tab, g);
         const int row = lg + 4 * i;
         double v = -ll;
         if (!live) {
@@ -332,22 +324,6 @@ __global__ __launch_bounds__(64 * LO_W) void k_loo(LooArgs A) {
   }
 }
 
-// totals[s][1 + k] = the chunk partials of shard s summed in chunk order; [0] = n
-__global__ __launch_bounds__(64) void k_loo_reduce(LooArgs A, int nsh) {
-  const int idx = blockIdx.x * 64 + threadIdx.x;
-  if (idx >= nsh * 8) return;
-  const int si = idx >> 3, k = idx & 7;
-  const ShardDev sh = A.shards[A.shard0 + si];
-  double v = (double)sh.n;
-  if (k != 0) {
-    const int G = loo_chunks(sh.n);
-    const double* src = A.partial + (size_t)si * A.Gs * 8 + (k - 1);
-    v = src[0];
-    for (int c = 1; c < G; ++c) v += src[(size_t)c * 8];
-  }
-  A.totals[idx] = v;
-}
-
 template <int FAM, int KF>
 static hipError_t go_loo(const LooArgs& A, int d, int nsh, hipStream_t st) {
   const size_t lds = loo_lds_doubles(d, A.S) * sizeof(double);
@@ -362,19 +338,6 @@ static hipError_t go_loo(const LooArgs& A, int d, int nsh, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(A.Gs, nsh), dim3(64 * 4), lds, st, A);
   }
   return hipGetLastError();
-}
-
-template <int FAM>
-static hipError_t launch_loo(const LooArgs& A, int d, int nsh, hipStream_t st) {
-  switch (pred_kf(d)) {
-#define STK_LO(K) case K: return go_loo<FAM, K>(A, d, nsh, st);
-    STK_LO(1) STK_LO(2) STK_LO(3) STK_LO(4) STK_LO(5) STK_LO(6) STK_LO(7) STK_LO(8)
-    STK_LO(9) STK_LO(10) STK_LO(11) STK_LO(12) STK_LO(13) STK_LO(14) STK_LO(15) STK_LO(16)
-    STK_LO(17) STK_LO(18) STK_LO(19) STK_LO(20) STK_LO(21) STK_LO(22) STK_LO(23) STK_LO(24)
-    STK_LO(25) STK_LO(26) STK_LO(27) STK_LO(28) STK_LO(29) STK_LO(30) STK_LO(31) STK_LO(32)
-#undef STK_LO
-  }
-  return hipErrorInvalidValue;
 }
 
 }  // namespace stk
@@ -397,14 +360,12 @@ hipError_t stk_launch_loo(int family, const ShardDev* shards, int shard0, int ns
                           hipStream_t st) {
   if (S < 1 || S > PSIS_SMAX || !stk_loo_supported(d)) return hipErrorInvalidValue;
   const int M = psis_tail_len(S);
-  const LooArgs A{shards, img, partial, rows, rowoff, totals, family, shard0, Gs, S, stk_predictive_tiles(S),
+  const PredArgs P{shards, img, partial, rows, rowoff, totals, family, shard0, Gs, S, stk_predictive_tiles(S)};
+  const LooArgs A{P.shards, P.img, P.partial, P.rows, P.rowoff, P.totals, P.family, P.shard0, P.Gs, P.S, P.ntile,
                   loo_sp(S), M, psis_grid(M)};
   if (loo_lds_doubles(d, S) * sizeof(double) > BIG_LDS_BYTES) return hipErrorInvalidValue;
-  hipError_t e = hipErrorInvalidValue;
-  if (family == STK_LOGREG) e = launch_loo<STK_LOGREG>(A, d, nsh, st);
-  else if (family == STK_LINREG) e = launch_loo<STK_LINREG>(A, d, nsh, st);
-  else if (family == STK_POISSON) e = launch_loo<STK_POISSON>(A, d, nsh, st);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_loo_reduce, dim3((nsh * 8 + 63) / 64), dim3(64), 0, st, A, nsh);
-  return hipGetLastError();
+  const hipError_t e = draw_dispatch(family, d, [&](auto fam, auto kf) {
+    return go_loo<decltype(fam)::value, decltype(kf)::value>(A, d, nsh, st);
+  });
+  return e != hipSuccess ? e : launch_draw_totals<loo_chunks, 7>(P, nsh, st);
 }

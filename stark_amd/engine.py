@@ -440,6 +440,24 @@ class Model:
                                                   g.ctypes.data, H.ctypes.data))
         return (lp, g, H) if every else (lp[0], g[0], H[0])
 
+    def _rows_and_totals(self, fn, keys, q, shard, rows):
+        """The call ``log_predictive`` and ``loo`` share: ``fn`` is the C entry point, ``keys`` name the four
+        per-row columns."""
+        every = shard is None
+        q = np.ascontiguousarray(np.atleast_2d(q), np.float64)
+        D = self.D[0 if every else shard]
+        if q.ndim != 2 or q.shape[1] != D:
+            raise ValueError(f"q must be [S, D = {D}], got {q.shape}")
+        ns = self.nshards if every else 1
+        n = sum(self.n_rows) if every else self.n_rows[shard]
+        tot = np.empty((ns, 8))
+        out = np.empty((n, 4)) if rows else None
+        check(fn(self._h, -1 if every else int(shard), q.ctypes.data, q.shape[0], _ptr(out), tot.ctypes.data))
+        tot = tot if every else tot[0]
+        if not rows:
+            return tot
+        return tot, {k: np.ascontiguousarray(out[:, j]) for j, k in enumerate(keys)}
+
     def log_predictive(self, q, shard=None, rows=False):
         """Per-row statistics of the normalised pointwise log likelihood over the S draws ``q`` [S, D]
         (unconstrained, the layout of ``log_density_grad``), and their per-shard totals
@@ -449,21 +467,7 @@ class Model:
         dict of per-row arrays ``lppd``, ``mean``, ``var``, ``mu`` (shard-major when shard is None).
         Non-finite values are what IEEE arithmetic on the definitions gives (include/stark_hip.h);
         totals[..., 6] counts the rows that have one."""
-        every = shard is None
-        q = np.ascontiguousarray(np.atleast_2d(q), np.float64)
-        D = self.D[0 if every else shard]
-        if q.ndim != 2 or q.shape[1] != D:
-            raise ValueError(f"q must be [S, D = {D}], got {q.shape}")
-        ns = self.nshards if every else 1
-        n = sum(self.n_rows) if every else self.n_rows[shard]
-        tot = np.empty((ns, 8))
-        out = np.empty((n, 4)) if rows else None
-        check(_lib.load().stk_log_predictive(self._h, -1 if every else int(shard), q.ctypes.data, q.shape[0],
-                                             _ptr(out), tot.ctypes.data))
-        tot = tot if every else tot[0]
-        if not rows:
-            return tot
-        return tot, {k: np.ascontiguousarray(out[:, j]) for j, k in enumerate(("lppd", "mean", "var", "mu"))}
+        return self._rows_and_totals(_lib.load().stk_log_predictive, ("lppd", "mean", "var", "mu"), q, shard, rows)
 
     def loo(self, q, shard=None, rows=False):
         """PSIS-LOO of every row over the S <= 1024 draws ``q`` [S, D] (the layout of
@@ -473,21 +477,7 @@ class Model:
         dict of per-row arrays ``elpd_loo``, ``khat``, ``lppd``, ``p_loo`` (shard-major when shard is
         None).  khat is +inf where a row is not smoothed (S <= 20, or a constant tail); a row with a
         non-finite log likelihood has NaN elpd_loo, p_loo and khat and is counted in totals[..., 7]."""
-        every = shard is None
-        q = np.ascontiguousarray(np.atleast_2d(q), np.float64)
-        D = self.D[0 if every else shard]
-        if q.ndim != 2 or q.shape[1] != D:
-            raise ValueError(f"q must be [S, D = {D}], got {q.shape}")
-        ns = self.nshards if every else 1
-        n = sum(self.n_rows) if every else self.n_rows[shard]
-        tot = np.empty((ns, 8))
-        out = np.empty((n, 4)) if rows else None
-        check(_lib.load().stk_loo(self._h, -1 if every else int(shard), q.ctypes.data, q.shape[0], _ptr(out),
-                                  tot.ctypes.data))
-        tot = tot if every else tot[0]
-        if not rows:
-            return tot
-        return tot, {k: np.ascontiguousarray(out[:, j]) for j, k in enumerate(("elpd_loo", "khat", "lppd", "p_loo"))}
+        return self._rows_and_totals(_lib.load().stk_loo, ("elpd_loo", "khat", "lppd", "p_loo"), q, shard, rows)
 
     def log_density(self, q, shard=None):
         """lp at each of the S draws ``q`` [S, D] (unconstrained, the layout of ``log_predictive``): by

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 kernels of two builds of libstark_hip.so, object file by object file.
 
-    python tools/codeobj_compare.py PARENT_OBJ_DIR BRANCH_OBJ_DIR [--out profiles/NAME.json]
+    python tools/codeobj_compare.py PARENT_OBJ_DIR BRANCH_OBJ_DIR [--out profiles/NAME.json] [--brief]
 
 For every *.o of both directories the gfx950 code object is taken out of the object's fat binary,
 and for every kernel in it the compiler's metadata (VGPRs, SGPRs, scratch bytes, static LDS bytes) is
@@ -95,6 +95,7 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("branch")
     ap.add_argument("--out")
+    ap.add_argument("--brief", action="store_true", help="record counts of unchanged kernels and one line per changed one")
     ap.add_argument("--parent-label", default="parent commit")
     ap.add_argument("--branch-label", default="this change")
     a = ap.parse_args()
@@ -114,6 +115,13 @@ def main():
         nsame, ndiff, nnew, ngone = nsame + len(same), ndiff + len(changed), nnew + len(new), ngone + len(gone)
         res["objects"][o] = {"same": {k: kb[k] for k in same}, "changed": changed, "new": new, "gone": gone}
     res["summary"] = {"kernels_same": nsame, "kernels_changed": ndiff, "kernels_new": nnew, "kernels_gone": ngone}
+    if a.brief:
+        keys = ("vgpr", "sgpr", "scratch_bytes", "lds_static_bytes", "vgpr_spills", "sgpr_spills", "instructions")
+        res["brief"] = "same: a count; changed: 'parent>branch' of " + ", ".join(keys) + "; new: the kernel names"
+        for r in res["objects"].values():
+            r["same"] = len(r["same"])
+            r["changed"] = {k: " ".join(f"{v['parent'][f]}>{v['branch'][f]}" for f in keys) for k, v in r["changed"].items()}
+            r["new"] = sorted(r["new"])
     text = json.dumps(res, indent=1, sort_keys=True)
     if a.out:
         with open(a.out, "w") as f:

@@ -8,8 +8,8 @@ GPU, at S = 1024 draws: the generating point plus N(0, 1e-3) noise.  In one proc
   sweep step  stk_log_density_grad_chains at 16 points per shard: one 16-chain sweep step (k_sweep16) and
               its reduce -- forward AND backward, X read once per 16 draws.  S / 16 of them are the only
               route to the same S numbers without k_logdens;
-  predictive  stk_log_predictive(shard = -1, rows = NULL) at the same S: k_predictive, the kernel whose
-              forward half k_logdens takes (recorded for comparison, no bar).
+  predictive  stk_log_predictive(shard = -1, rows = NULL) at the same S: k_predictive, the kernel that
+              shares its forward half with k_logdens (draw_forward.h; recorded for comparison, no bar).
 Each is timed with a HIP event pair on the context's stream after a warm-up of all three (the entry
 points copy their small host arguments inside the window, as a caller pays for them); medians and the
 spread over `--repeats` rounds are reported.  The bar is the existing route, not a fixed time: all

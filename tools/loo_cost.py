@@ -4,9 +4,9 @@
 Workload: BASELINE configs[3]'s model, 8 synthetic logistic shards x 1.25e7 rows x d = 100, on one
 GPU, scored against S draws (1024 and 256 by default): the generating point plus N(0, 1e-3) noise.  In
 one process, for every S, alternating between the two:
-  loo         stk_loo(shard = -1, rows = NULL): k_predictive_prep, k_loo, k_loo_reduce;
+  loo         stk_loo(shard = -1, rows = NULL): k_predictive_prep, k_loo, k_draw_totals;
   predictive  stk_log_predictive(shard = -1, rows = NULL) at the same S: k_predictive_prep,
-              k_predictive, k_predictive_reduce -- the same forward pass without the sort and the fit.
+              k_predictive, k_draw_totals -- the same forward pass without the sort and the fit.
 Each pass is timed with a HIP event pair on the context's stream after a warm-up of both; medians and
 the spread over `--repeats` rounds are reported, and their ratio.  There is no bar: no earlier path
 computes PSIS-LOO.  Every GPU step (building the model, the warm-up, each timed pass) runs under its

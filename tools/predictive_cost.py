@@ -6,7 +6,7 @@ GPU, scored against S = 1024 draws: the generating point plus N(0, 1e-3) noise. 
 alternating between the two:
   predictive  stk_log_predictive(shard = -1, rows = NULL): the totals of all shards, one preparation
               launch, one sweep launch and one reduce launch (k_predictive_prep, k_predictive,
-              k_predictive_reduce);
+              k_draw_totals);
   sweep step  sweep_ms / sweeps of a 16-chain sampler on the same model (k_sweep16), with the
               context's profiling on.  S / 16 of them see as many (row, draw) pairs as the predictive
               sweep does -- forward AND backward, with X read S / 16 times instead of once.

@@ -8,6 +8,12 @@ of libstark_hip.so bit for bit (the library is the one STARK_HIP_LIB names, else
   sample   logistic sampling runs at d = 20, chains = 7, 30 + 30 iterations: 3 shards of 1500, 1500
            and 77 rows, and 8 shards of 77 rows (tiny n: launches dominate) -- draws and stats hashed,
            wall time per sampler step reported as `host_ms_per_step` (a figure, never compared)
+  draws    the sweeps over a draw image -- log_predictive(rows=True), loo(rows=True) and log_density --
+           for the three regression families at d in {1, 5, 50, 100, 128} (KF = 1, 2, 13, 25, 32) x
+           S in {1, 17, 100, 600} (one draw, a partial draw tile, the 4-wave LOO with a fitted tail, the
+           8-wave LOO): shards of 1, 65 and 257 rows in one grouped launch, and shard 1 alone
+           (shard0 > 0); at d = 5, S = 17 also with one draw whose intercept is NaN and (poisson) one
+           whose eta overflows
 
 The sweeps reduce in a fixed order, so two builds that launch the same kernels with the same
 arguments give equal hashes; a differing hash is a routing or argument error.
@@ -56,6 +62,46 @@ def points(rng, family, d, beta, shape):
     return q
 
 
+DRAW_ROWS, DRAW_D, DRAW_S = (1, 65, 257), (1, 5, 50, 100, 128), (1, 17, 100, 600)
+
+
+def draws_section(engine, ctx, H):
+    for family in ("logistic", "poisson", "linear"):
+        for d in DRAW_D:
+            rng = np.random.default_rng(7000 + 10 * d + len(family))
+            beta = rng.normal(0, 1 / np.sqrt(d), d)
+            shards = []
+            for n in DRAW_ROWS:
+                X = rng.uniform(-1.7, 1.7, (n, d))
+                eta = 0.3 + X @ beta
+                y = {"logistic": lambda: (rng.uniform(size=n) < 1 / (1 + np.exp(-eta))).astype(np.int32),
+                     "poisson": lambda: rng.poisson(np.exp(eta)).astype(np.int32),
+                     "linear": lambda: eta + 0.7 * rng.normal(size=n)}[family]()
+                shards.append({"x": X, "y": y})
+            truth = np.concatenate([[0.3], beta, [np.log(0.7)] if family == "linear" else []])
+            m = engine.Model(ctx, family, shards)
+            try:
+                cases = [(f"S{S}", truth + rng.normal(0, 0.1, (S, truth.size))) for S in DRAW_S]
+                if d == 5:
+                    bad = cases[1][1].copy()
+                    bad[3, 0] = np.nan
+                    cases.append(("S17nan", bad))
+                    if family == "poisson":
+                        big = cases[1][1].copy()
+                        big[7, 1] = 800.0
+                        cases.append(("S17overflow", big))
+                for tag, Q in cases:
+                    for sh in (None, 1):
+                        key = f"draws/{family}/d{d}/{tag}/shard{'s' if sh is None else sh}"
+                        tot, rows = m.log_predictive(Q, sh, rows=True)
+                        H[key + "/predictive"] = sha(tot, *rows.values())
+                        tot, rows = m.loo(Q, sh, rows=True)
+                        H[key + "/loo"] = sha(tot, *rows.values())
+                        H[key + "/logdens"] = sha(m.log_density(Q, sh))
+            finally:
+                m.close()
+
+
 def main(out_path):
     from stark_amd import _lib, engine
     from test_gpu_sweep_shards import ROWS, SHAPES
@@ -91,6 +137,7 @@ def main(out_path):
         H[f"sample/{tag}"] = sha(*r.draws, *r.stats)
         H[f"sample/{tag}/repeat"] = sha(*r2.draws, *r2.stats)
         res["host_ms_per_step"][tag] = {"steps": int(r.info["steps"]), "ms_per_step": 1e3 * dt / r.info["steps"]}
+    draws_section(engine, ctx, H)
     with open(out_path, "w") as f:
         json.dump(res, f, indent=1, sort_keys=True)
         f.write("\n")
