@@ -44,6 +44,11 @@
  *   stk_boot_poisson_thresholds / likelihood bootstrap; Poisson(1): the classical one), the weights' host twin and
  *   stk_boot_launch_info        the launch shape (stark_amd.engine.bootstrap).  The reference's README names the
  *                               mode ("akin to a distributed bootstrap") without building it
+ *   stk_posterior_predict /     posterior predictive replicates y_rep of every (row, draw), drawn in the kernel by a
+ *   stk_yrep_host /             Philox generator, with their per-draw statistics and Pearson discrepancies, per-row
+ *   stk_ppc_launch_info         counts and sums, the generator's host twin and the launch shape
+ *                               (stark_amd.engine.ppc).  The reference extracts a Stan model's generated quantities
+ *                               (stark/stark.py:49-56); the fixed families have no such block, so this supplies it
  *
  * Conventions
  *   - Return 0 on success, a negative STK_E_* code on failure; stk_last_error() gives a
@@ -450,6 +455,55 @@ STK_API int stk_boot_poisson_thresholds(uint32_t out[13]);
 /* host only: out[0] rows per sub-tile, out[1] chunks per shard (a function of n_rows alone), out[2] waves per
  * block, out[3] dynamic LDS bytes, out[4] bytes of chunk-partial workspace per shard and tile of 16 replicates. */
 STK_API int stk_boot_launch_info(int64_t n_rows, int32_t d, int64_t out[5]);
+
+/* ---- posterior predictive replicates and checks (regression families, d <= 128) ----
+ * The replicate y_rep of (row i, draw s) is a pure function of (seed, stream, i, s, eta_is, u_s) (csrc/yrep_math.h).
+ * Philox call j of the element has the counter {(uint32) i, (uint32)(i >> 32) | s << 8, stream << 12 | j, TAG_YREP}:
+ * i < 2^40 is the row's index in its shard, s < 2^24 the draw's GLOBAL index (draw0 + its position in q), stream <
+ * 2^20 the shard's GLOBAL index, j < 4096; U and V are the 53-bit uniforms of its two 64-bit outputs.  One call per
+ * element, never shared between rows.
+ *   logistic  g = 1 / (1 + e^-eta);  y_rep = 1 if U < g else 0                                          (call 0)
+ *   linear    z = sqrt(-2 log U) cos(2 pi V);  y_rep = eta + e^u z                                      (call 0)
+ *   poisson   mu = e^eta.  mu < 10: inversion of U by upward search (k = 0, p = e^-mu, c = p; while U > c: k += 1,
+ *             p *= mu / k, c += p), stopped at k = 128.  10 <= mu < 2^30: Hormann's transformed rejection (PTRS,
+ *             numpy's constants), attempt j on call j, floor(mu + 1/2) after 64 rejected attempts.  2^30 <= mu < inf:
+ *             max(0, floor(mu + sqrt(mu) z + 1/2)), the normal approximation (distribution function within 2.1e-6).
+ *   A non-finite eta or e^u, or mu = +inf, gives y_rep = NaN.
+ *
+ * stk_posterior_predict: q is [S][D] unconstrained, the layout of stk_log_predictive, and holds draws draw0 ..
+ * draw0 + S - 1; X is read once for all of them.  Outputs, with (m, V) = (g, g (1 - g)) logistic, (mu, mu) poisson,
+ * (eta, e^{2u}) linear and D(z, theta_s) = sum_i (z_i - m_is)^2 / V_is (a term with V = 0 is 0 where z = m and +inf
+ * otherwise, the limit of a point mass):
+ *   stats[s][0..7]  sum_i y_rep, sum_i y_rep^2, max_i y_rep, min_i y_rep, #{i : y_rep = 0}, D(y_rep_s, theta_s),
+ *                   D(y, theta_s), the number of NaN replicates of the draw (which makes [0..3] and [5] NaN)
+ *   obs[0..7]       the same [0..4] of the observed y, [5] = n, the rest 0                           (may be NULL)
+ *   rows[i][0..3]   #{s : y_rep_is < y_i}, #{s : y_rep_is = y_i}, sum_s y_rep, sum_s y_rep^2         (may be NULL)
+ *                   a NaN replicate counts in neither and makes the sums NaN
+ *   yrep[i][s]      the replicates, [n_rows][S]                                                      (may be NULL)
+ * shard == -1 is one grouped launch of every shard against the same draws: stats[nshards][S][8], obs[nshards][8],
+ * rows[sum n][4] and yrep[sum n][S] shard-major.  streams holds one value per shard of the call (host memory);
+ * NULL: the local shard index.  Host or device memory for q and every output, as stk_log_predictive has it: rows
+ * and yrep are written in place when they are memory of the context's device.
+ * An element's y_rep, a row's four numbers and a draw's eight depend on (the shard's rows, seed, stream, the
+ * draw's global index, the draw) alone, bit for bit: not on how many shards share the launch, on the shard's
+ * position, on the device, on S or on the draw's position in q or its companions -- a call on q[a .. b) with draw0
+ * = a returns columns a .. b - 1 of the call on all of q.
+ * STK_E_ARG (the message names the family, or the offending value as d = ... / S = ...) for 8 schools, d > 128,
+ * S < 1, draw0 < 0 or draw0 + S > 2^24, a stream >= 2^20 and a NULL q or stats. */
+STK_API int stk_posterior_predict(stk_model* m, int shard, const double* q, int32_t S, int32_t draw0, uint64_t seed,
+                                  const int32_t* streams, double* stats, double* obs, double* rows, double* yrep);
+/* host only, no context: out[r][c] = y_rep of row row0 + r at draw draw0 + c for the caller's eta[nrows][S] (and
+ * u[S] = log sigma, linear) -- compiled from the header the kernel uses.  family: 2 linear, 3 logistic, 4 poisson.
+ * margin, unless NULL, receives per element the smallest relative gap of any comparison that decided the value
+ * (+inf where none did): |a - b| / max(|a|, |b|) for a < b, the distance of a floor's argument to the nearest integer
+ * over max(1, mu), |lhs - rhs| over the largest term for the PTRS acceptance test.  An element below 1e-10 may come
+ * out differently from an eta that differs in its last bits. */
+STK_API int stk_yrep_host(int32_t family, uint64_t seed, uint32_t stream, int64_t row0, int64_t nrows, int32_t draw0,
+                          int32_t S, const double* eta, const double* u, double* out, double* margin);
+/* host only: out[0] rows per tile, out[1] chunks per shard, out[2] waves per block, out[3] dynamic LDS bytes,
+ * out[4] bytes of the draw image (stk_predictive_launch_info's), out[5] bytes of chunk-partial workspace per
+ * shard.  out[0..3] do not depend on S. */
+STK_API int stk_ppc_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]);
 
 /* ---- sampling: stark/stark.py:43-56 for every shard of the model ---- */
 STK_API int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out);

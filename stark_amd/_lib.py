@@ -130,6 +130,9 @@ SIGNATURES = [
     ("stk_boot_weights_host", ctypes.c_int, [_u64, ctypes.c_uint32, _i64, _i64, _i32, _i32, _i32, _vp]),
     ("stk_boot_poisson_thresholds", ctypes.c_int, [_vp]),
     ("stk_boot_launch_info", ctypes.c_int, [_i64, _i32, _vp]),
+    ("stk_posterior_predict", ctypes.c_int, [_vp, ctypes.c_int, _vp, _i32, _i32, _u64, _vp, _vp, _vp, _vp, _vp]),
+    ("stk_yrep_host", ctypes.c_int, [_i32, _u64, ctypes.c_uint32, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    ("stk_ppc_launch_info", ctypes.c_int, [_i64, _i32, _i32, _vp]),
     ("stk_dpe_launch_info", ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("stk_dpe_prepare", ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("stk_dpe_sample", ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, ctypes.c_uint32,

@@ -1,8 +1,9 @@
 // C ABI of libstark_hip.so: the chain plan, the lp / grad parity hooks, the host-only launch-info
 // calls, the analytic Hessian, the pointwise log-predictive sweep, the PSIS-LOO sweep, the per-draw log
-// density, the weighted bootstrap sweep and the Laplace proposal.
+// density, the weighted bootstrap sweep, the Laplace proposal and the posterior predictive replicate sweep.
 #include "capi_internal.h"
 #include "boot_math.h"
+#include "yrep_math.h"
 
 // The chain counts that are ONE sweep launch in the two single-launch parity hooks (stk_log_density_grad's
 // own batching and stk_log_density_grad_shards): their acceptance set stays as it was before the
@@ -519,6 +520,112 @@ int stk_laplace_draws(stk_ctx* ctx, const double* mode, const double* factor, in
   STK_HIP_CHECK(stk_launch_laplace_draws(mb, fb, D, S, seed, stream, qb, lb, st));
   STK_HIP_CHECK(hipMemcpyAsync(q_out, qb, sizeof(double) * qn, hipMemcpyDefault, st));
   STK_HIP_CHECK(hipMemcpyAsync(log_q_out, lb, sizeof(double) * (size_t)S, hipMemcpyDefault, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));
+  return STK_OK;
+}
+
+// ---------------------------------------------------------------- posterior predictive replicates (ppc.hip)
+// The sweep's launch shape over a shard of n_rows x d against S draws (host only: no device).
+// out: rows per tile, chunks per shard, waves per block, LDS bytes, draw-image bytes, chunk-partial
+// workspace bytes per shard.  Only the last two depend on S.
+int stk_ppc_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_ppc_launch_info: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(stk_ppc_supported(d), "the posterior predictive sweep covers 1 <= d <= 128 covariates, not d = %d", d);
+  ARG_CHECK(S >= 1, "the posterior predictive sweep needs S >= 1 draws, not S = %d", S);
+  const int64_t v[6] = {stk_ppc_rows_per_tile(), stk_ppc_chunks(n_rows), stk_ppc_waves(), (int64_t)stk_ppc_lds_bytes(d),
+                        (int64_t)stk_predictive_image_bytes(d, S), (int64_t)stk_ppc_ws_bytes(n_rows, S)};
+  memcpy(out, v, sizeof(v));
+  return STK_OK;
+}
+
+// The twin of the kernel's replicates: yrep_math.h's yrep_element, element by element, on the caller's eta
+// (host only: no device, no context).  The exp table is the kernel's, 2^(j/1024).
+int stk_yrep_host(int32_t family, uint64_t seed, uint32_t stream, int64_t row0, int64_t nrows, int32_t draw0, int32_t S,
+                  const double* eta, const double* u, double* out, double* margin) {
+  ARG_CHECK(is_regression(family), "stk_yrep_host: no replicates for the %s family (regressions only)", family_name(family));
+  ARG_CHECK(eta && out, "stk_yrep_host: eta or out is NULL");
+  ARG_CHECK(family != STK_LINREG || u, "stk_yrep_host: the linear family needs u = log sigma of every draw");
+  ARG_CHECK(row0 >= 0 && nrows >= 0 && row0 + nrows <= (int64_t)1 << 40,
+            "stk_yrep_host: rows row0 = %lld .. row0 + nrows = %lld; a row index is in 0 .. 2^40 - 1", (long long)row0,
+            (long long)(row0 + nrows));
+  ARG_CHECK(S >= 1, "stk_yrep_host: S = %d draws; need S >= 1", S);
+  ARG_CHECK(draw0 >= 0 && (int64_t)draw0 + S <= YREP_MAX_DRAWS,
+            "stk_yrep_host: draws draw0 = %d .. draw0 + S = %lld; a draw index is below 2^24", draw0, (long long)draw0 + S);
+  ARG_CHECK(stream < YREP_MAX_STREAM, "stk_yrep_host: stream = %u; a stream is below 2^20 = %u", stream, YREP_MAX_STREAM);
+  static const std::vector<double> tab = [] {
+    std::vector<double> t(1024);
+    for (int i = 0; i < 1024; ++i) t[i] = exp2((double)i / 1024.0);
+    return t;
+  }();
+  for (int64_t r = 0; r < nrows; ++r)
+    for (int32_t c = 0; c < S; ++c) {
+      const size_t k = (size_t)r * S + c;
+      double mg = HUGE_VAL;
+      out[k] = yrep_element(family, seed, stream, row0 + r, (uint32_t)(draw0 + c), eta[k], u ? u[c] : 0.0, tab.data(),
+                            margin ? &mg : nullptr);
+      if (margin) margin[k] = mg;
+    }
+  return STK_OK;
+}
+
+// The same S draws against one shard or (shard == -1) every shard: one preparation launch (the log-predictive
+// sweep's draw image), one sweep launch, one launch over y and one reduce launch for all of them.  rows and yrep
+// are written in place when they are memory of the context's device, else through a staging buffer.
+int stk_posterior_predict(stk_model* m, int shard, const double* q, int32_t S, int32_t draw0, uint64_t seed,
+                          const int32_t* streams, double* stats, double* obs, double* rows, double* yrep) {
+  ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_posterior_predict: bad model or shard");
+  ARG_CHECK(is_regression(m->family), "stk_posterior_predict: no posterior predictive sweep for the %s family (regressions only)",
+            family_name(m->family));
+  ARG_CHECK(stk_ppc_supported(m->d),
+            "stk_posterior_predict: the posterior predictive sweep covers 1 <= d <= 128 covariates, not d = %d (%s family)",
+            m->d, family_name(m->family));
+  ARG_CHECK(S >= 1, "stk_posterior_predict: S = %d draws; the %s family at d = %d needs S >= 1", S, family_name(m->family),
+            m->d);
+  ARG_CHECK(draw0 >= 0 && (int64_t)draw0 + S <= YREP_MAX_DRAWS,
+            "stk_posterior_predict: draws draw0 = %d .. draw0 + S = %lld; a draw index is in 0 .. 2^24 - 1", draw0,
+            (long long)draw0 + S);
+  ARG_CHECK(q, "stk_posterior_predict: q is NULL (%s family, d = %d)", family_name(m->family), m->d);
+  ARG_CHECK(stats, "stk_posterior_predict: stats is NULL (%s family, d = %d)", family_name(m->family), m->d);
+  const ShardRange r = shard_range(m, shard, stk_ppc_chunks);
+  const int nsh = r.nsh;
+  std::vector<int32_t> sv(nsh);
+  std::vector<int64_t> off(nsh);
+  int64_t nrows = 0;
+  for (int s = 0; s < nsh; ++s) {
+    sv[s] = streams ? streams[s] : r.shard0 + s;
+    ARG_CHECK(sv[s] >= 0 && (uint32_t)sv[s] < YREP_MAX_STREAM,
+              "stk_posterior_predict: stream = %d of shard %d; a stream is in 0 .. 2^20 - 1", sv[s], r.shard0 + s);
+    off[s] = nrows;
+    nrows += m->sh[r.shard0 + s].n;
+  }
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t Sp = (size_t)128 * stk_predictive_tiles(S) + 8;       // doubles per chunk (stk_ppc_ws_bytes)
+  const size_t wn = (size_t)nsh * r.Gs * Sp, sn = (size_t)nsh * S * 8, on = (size_t)nsh * 8;
+  RC(ctx->scratch[SCR_DRAW_PARTIAL].ensure(sizeof(double) * (wn + sn + on) + sizeof(int64_t) * nsh + sizeof(int32_t) * nsh));
+  double* partial = ctx->scratch[SCR_DRAW_PARTIAL].as<double>();
+  double* sb = partial + wn;
+  double* ob = sb + sn;
+  int64_t* offb = reinterpret_cast<int64_t*>(ob + on);
+  int32_t* strb = reinterpret_cast<int32_t*>(offb + nsh);
+  const size_t rn = (size_t)nrows * 4, yn = (size_t)nrows * S;
+  const bool rows_staged = rows && !is_device_ptr(rows, ctx->device), yrep_staged = yrep && !is_device_ptr(yrep, ctx->device);
+  if (rows_staged || yrep_staged)
+    RC(ctx->scratch[SCR_DRAW_ROWS].ensure(sizeof(double) * ((rows_staged ? rn : 0) + (yrep_staged ? yn : 0))));
+  double* rb = rows_staged ? ctx->scratch[SCR_DRAW_ROWS].as<double>() : rows;
+  double* yb = yrep_staged ? ctx->scratch[SCR_DRAW_ROWS].as<double>() + (rows_staged ? rn : 0) : yrep;
+  DrawImage di;                              // every buffer is there before anything is queued
+  RC(stage_draws(m, q, S, 0, &di));
+  STK_HIP_CHECK(hipMemcpyAsync(offb, off.data(), sizeof(int64_t) * nsh, hipMemcpyHostToDevice, st));
+  STK_HIP_CHECK(hipMemcpyAsync(strb, sv.data(), sizeof(int32_t) * nsh, hipMemcpyHostToDevice, st));
+  STK_HIP_CHECK(hipStreamSynchronize(st));   // off and sv are locals
+  STK_HIP_CHECK(stk_launch_ppc(m->family, m->sh_dev.as<ShardDev>(), r.shard0, nsh, m->d, r.Gs, S, draw0, seed, strb, di.img,
+                               partial, sb, ob, rb, yb, offb, st));
+  STK_HIP_CHECK(hipMemcpyAsync(stats, sb, sizeof(double) * sn, hipMemcpyDefault, st));
+  if (obs) STK_HIP_CHECK(hipMemcpyAsync(obs, ob, sizeof(double) * on, hipMemcpyDefault, st));
+  if (rows_staged) STK_HIP_CHECK(hipMemcpyAsync(rows, rb, sizeof(double) * rn, hipMemcpyDefault, st));
+  if (yrep_staged) STK_HIP_CHECK(hipMemcpyAsync(yrep, yb, sizeof(double) * yn, hipMemcpyDefault, st));
   STK_HIP_CHECK(hipStreamSynchronize(st));
   return STK_OK;
 }

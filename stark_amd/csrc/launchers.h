@@ -146,6 +146,19 @@ hipError_t stk_launch_boot(int family, const stk::ShardDev* shards, int shard0, 
                            const double* q, double* partial, const int32_t* streams, uint64_t seed, int rep0, int kind,
                            int R, int c0, int nrep, double* lp, double* grad, double* wsum, hipStream_t st);
 
+// ---- ppc.hip (regressions, d <= 128, any S): the posterior predictive replicate sweep's geometry and launch (the
+// draw image is stk_launch_predictive_prep's).  stats [nsh][S][8], obs [nsh][8]; rows ([sum n][4]) and yrep
+// ([sum n][S]) may be null; partial holds stk_ppc_ws_bytes of every shard at the stride Gs.
+bool stk_ppc_supported(int d);
+int stk_ppc_chunks(int64_t n);
+int stk_ppc_rows_per_tile();
+int stk_ppc_waves();
+size_t stk_ppc_lds_bytes(int d);
+size_t stk_ppc_ws_bytes(int64_t n, int S);         // chunk-partial workspace of one shard
+hipError_t stk_launch_ppc(int family, const stk::ShardDev* shards, int shard0, int nsh, int d, int Gs, int S, int draw0,
+                          uint64_t seed, const int32_t* streams, const double* img, double* partial, double* stats,
+                          double* obs, double* rows, double* yrep, const int64_t* rowoff, hipStream_t st);
+
 // ---- nuts.hip (and its nuts_fused4.hip / nuts_dense.hip translation units)
 int stk_nch_for(int Dmax);
 size_t stk_fused_lds_bytes(const stk::NutsArgs& A, int nch);

@@ -20,6 +20,8 @@
 //                                                                 of coordinate m, 32-bit word m & 3
 //   TAG_DPE_PROP ctr = {chain, sweep,   m,      stream<<8 | TAG}  proposal index (r.a low) and uniform (r.b)
 //   TAG_DPE_NORM ctr = {chain, draw,    i/2,    stream<<8 | TAG}  normals of the chain's emitted draw (Box-Muller)
+//   TAG_YREP     ctr = {row_lo, row_hi | s<<8, stream<<12 | j, TAG}  call j of the posterior predictive replicate of
+//                                                                 (row, draw s): U = u53(r.a), V = u53(r.b) (yrep_math.h)
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -31,7 +33,7 @@ namespace stk {
 enum : uint32_t { TAG_INIT = 0x1, TAG_MOM = 0x2, TAG_UNI = 0x3, TAG_SSMOM = 0x4, TAG_JIT = 0x5,
                   TAG_X = 0x10, TAG_Y = 0x11, TAG_BETA = 0x12,
                   TAG_LAPLACE = 0x20, TAG_RESAMPLE = 0x21, TAG_BOOT = 0x22,
-                  TAG_DPE_INIT = 0x23, TAG_DPE_PROP = 0x24, TAG_DPE_NORM = 0x25 };
+                  TAG_DPE_INIT = 0x23, TAG_DPE_PROP = 0x24, TAG_DPE_NORM = 0x25, TAG_YREP = 0x26 };
 
 struct u64x2 { uint64_t a, b; };
 

@@ -524,6 +524,44 @@ class Model:
                                                     lp.ctypes.data, g.ctypes.data, ws.ctypes.data))
         return (lp, g, ws) if every else (lp[0], g[0], ws[0])
 
+    def posterior_predict(self, q, shard=None, seed=0, draw0=0, streams=None, rows=False, yrep=False):
+        """Posterior predictive replicates of every (row, draw) of the S draws ``q`` [S, D] (unconstrained, the
+        layout of ``log_predictive``), drawn in the kernel from the family's sampling distribution at eta_is, and
+        reduced both ways (stk_posterior_predict: the posterior predictive sweep; regression families with
+        d <= 128, any S >= 1; include/stark_hip.h has the generator).  Returns ``stats`` [S, 8] per draw -- sum
+        y_rep, sum y_rep^2, max, min, #zeros, the Pearson discrepancies D(y_rep_s, theta_s) and D(y, theta_s), the
+        number of NaN replicates -- and ``obs`` [8], the same first five of the observed y and n; ``ppc(stats,
+        obs)`` turns them into the checks.  shard: an index, or None for every shard against the same draws in one
+        grouped launch (stats [nshards, S, 8], obs [nshards, 8]).  rows=True adds a dict of per-row arrays
+        ``n_less``, ``n_equal``, ``sum``, ``sum_sq`` over the draws (shard-major when shard is None);
+        yrep=True adds the replicates as [S, n].  draw0: the global index of q[0] -- a call on q[a:b] with
+        draw0=a returns columns a .. b - 1 of the call on all of q, bit for bit.  streams: one RNG stream per
+        shard of the call -- the shard's GLOBAL index, below 2^20 -- or None for the local index."""
+        every = shard is None
+        q = np.ascontiguousarray(np.atleast_2d(q), np.float64)
+        D = self.D[0 if every else shard]
+        if q.ndim != 2 or q.shape[1] != D:
+            raise ValueError(f"q must be [S, D = {D}], got {q.shape}")
+        ns, S = (self.nshards if every else 1), q.shape[0]
+        n = sum(self.n_rows) if every else self.n_rows[shard]
+        sv = None
+        if streams is not None:
+            sv = np.ascontiguousarray(np.atleast_1d(streams), np.int32)
+            if sv.shape != (ns,):
+                raise ValueError(f"streams must hold one value per shard of the call ({ns}), got shape {sv.shape}")
+        stats, obs = np.empty((ns, S, 8)), np.empty((ns, 8))
+        rw = np.empty((n, 4)) if rows else None
+        yr = np.empty((n, max(S, 0))) if yrep else None
+        check(_lib.load().stk_posterior_predict(self._h, -1 if every else int(shard), q.ctypes.data, S, int(draw0),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(sv), stats.ctypes.data,
+                                                obs.ctypes.data, _ptr(rw), _ptr(yr)))
+        out = [stats if every else stats[0], obs if every else obs[0]]
+        if rows:
+            out.append({k: np.ascontiguousarray(rw[:, j]) for j, k in enumerate(("n_less", "n_equal", "sum", "sum_sq"))})
+        if yrep:
+            out.append(np.ascontiguousarray(yr.T))
+        return tuple(out)
+
     def set_prior(self, alpha=None, beta=None):
         """normal(0, s) priors on alpha and beta (regressions); None or 0: flat."""
         check(_lib.load().stk_model_set_prior(self._h, float(alpha or 0.0), float(beta or 0.0)))
@@ -899,6 +937,80 @@ def boot_weights(seed: int, stream: int, row0: int, nrows: int, rep0: int, R: in
     out = np.empty((max(int(nrows), 0), max(int(R), 0)))
     check(_lib.load().stk_boot_weights_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, int(row0), int(nrows),
                                             int(rep0), int(R), boot_kind(kind), out.ctypes.data))
+    return out
+
+
+TAG_YREP = 0x26                                              # csrc/philox.h
+PPC_STATS = ("mean", "sd", "max", "min", "frac_zero")
+
+
+def yrep_host(family, seed: int, stream: int, row0: int, draw0: int, eta, u=None, margin=False):
+    """The replicates [nrows, S] of rows row0 .. of a shard at draws draw0 .. for the caller's ``eta`` [nrows, S]
+    (and ``u`` [S] = log sigma, linear): stk_yrep_host, the host twin of the kernel's generator, compiled from the
+    same header; needs no device.  margin=True also returns, per element, the smallest relative gap of any
+    comparison that decided the value: below 1e-10 the element may differ for an eta that differs in its last
+    bits.  stream: the shard's global index."""
+    fam = FAMILIES.get(family, family)
+    eta = np.ascontiguousarray(np.atleast_2d(eta), np.float64)
+    uv = None if u is None else np.ascontiguousarray(np.atleast_1d(u), np.float64)
+    if uv is not None and uv.shape != (eta.shape[1],):
+        raise ValueError(f"u must hold one value per draw ({eta.shape[1]}), got shape {uv.shape}")
+    out = np.empty(eta.shape)
+    mg = np.empty(eta.shape) if margin else None
+    check(_lib.load().stk_yrep_host(int(fam), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, int(row0),
+                                    eta.shape[0], int(draw0), eta.shape[1], eta.ctypes.data, _ptr(uv), out.ctypes.data,
+                                    _ptr(mg)))
+    return (out, mg) if margin else out
+
+
+def ppc_launch(n_rows: int, n_cols: int, S: int) -> dict:
+    """The launch shape of the posterior predictive sweep over a shard of ``n_rows`` x ``n_cols`` against ``S``
+    draws (stk_ppc_launch_info): rows per tile ``T``, chunks per shard ``G``, ``waves`` per block, ``lds_bytes``
+    -- none of which depends on S -- and ``image_bytes`` of the draw image and ``ws_bytes_per_shard``, which do.
+    Raises STK_E_ARG past 128 covariates or for S < 1.  Host only."""
+    out = np.zeros(6, np.int64)
+    check(_lib.load().stk_ppc_launch_info(int(n_rows), int(n_cols), int(S), out.ctypes.data))
+    return dict(zip(("T", "G", "waves", "lds_bytes", "image_bytes", "ws_bytes_per_shard"), (int(v) for v in out)))
+
+
+def _ppc_T(tot, n):
+    """mean, sd, max, min, frac_zero from [..., 0:5] = (sum, sum of squares, max, min, zeros) over n values; the
+    sd is the sample one (0 at n = 1)."""
+    tot = np.asarray(tot, np.float64)
+    mean = tot[..., 0] / n
+    with np.errstate(invalid="ignore"):
+        var = (tot[..., 1] - tot[..., 0] * tot[..., 0] / n) / (n - 1.0) if n > 1 else 0.0 * tot[..., 0]
+        sd = np.sqrt(np.where(var < 0.0, 0.0, var))              # rounding only; a NaN stays
+    return {"mean": mean, "sd": sd, "max": tot[..., 2], "min": tot[..., 3], "frac_zero": tot[..., 4] / n}
+
+
+def ppc(stats, obs) -> dict:
+    """Posterior predictive checks from the ``stats`` [..., S, 8] and ``obs`` [..., 8] of
+    ``Model.posterior_predict``, pooled over partitions in the order given: sums add, extrema combine, the sd
+    comes from the pooled sums.  For T in (mean, sd, max, min, frac_zero): ``T`` = {"obs": T(y), "rep": the S
+    values T(y_rep_s), "p": #{s : T(y_rep_s) >= T(y)} / S}; ``chi2`` = {"obs": D(y, theta_s) [S], "rep":
+    D(y_rep_s, theta_s) [S], "p": #{s : D(y_rep_s, theta_s) >= D(y, theta_s)} / S}; ``n`` and ``n_non_finite``
+    (NaN replicates; a draw that has one compares as not >=)."""
+    st, ob = np.asarray(stats, np.float64), np.asarray(obs, np.float64)
+    if st.ndim < 2 or st.shape[-1] != 8 or ob.shape[-1] != 8:
+        raise ValueError(f"stats must be [..., S, 8] and obs [..., 8], got {st.shape} and {ob.shape}")
+    S = st.shape[-2]
+    st, ob = st.reshape(-1, S, 8), ob.reshape(-1, 8)
+    if st.shape[0] != ob.shape[0]:
+        raise ValueError(f"stats holds {st.shape[0]} partitions, obs {ob.shape[0]}")
+    ps, po = st[0].copy(), ob[0].copy()
+    for a, b in zip(st[1:], ob[1:]):         # partition order
+        for acc, x in ((ps, a), (po, b)):
+            mx, mn = np.fmax(acc[..., 2], x[..., 2]), np.fmin(acc[..., 3], x[..., 3])
+            nan = np.isnan(acc[..., 2]) | np.isnan(x[..., 2])
+            acc += x
+            acc[..., 2], acc[..., 3] = np.where(nan, np.nan, mx), np.where(nan, np.nan, mn)
+    n = float(po[5])
+    To, Tr = _ppc_T(po, n), _ppc_T(ps, n)
+    out = {"n": int(n), "n_non_finite": int(ps[:, 7].sum())}
+    for k in PPC_STATS:
+        out[k] = {"obs": float(To[k]), "rep": Tr[k], "p": float(np.count_nonzero(Tr[k] >= To[k])) / S}
+    out["chi2"] = {"obs": ps[:, 6].copy(), "rep": ps[:, 5].copy(), "p": float(np.count_nonzero(ps[:, 5] >= ps[:, 6])) / S}
     return out
 
 

@@ -620,6 +620,50 @@ class Stark:
         out["partition_totals"] = totals
         return out
 
+    PPC_MAX_COLS = 128        # the posterior predictive sweep covers d <= 128
+
+    def ppc(self, samples, seed=0):
+        """Posterior predictive checks of a P x S matrix of draws against EVERY partition's rows: would data
+        simulated from this fit look like the data?  For every (row, draw) a replicate y_rep is drawn on the
+        device from the family's sampling distribution; per draw, the replicated data set's mean, sd, max, min
+        and fraction of zeros and the Pearson discrepancy chi2 are compared with the observed ones.  Exchanged
+        exactly as ``waic`` does it: every rank scores its own partitions in one grouped launch with RNG stream =
+        the partition's global index, the per-partition [S, 8] and [8] arrays are all-gathered and pooled in
+        partition order, so every rank returns the same bits on 1 or N ranks.  Returns ``engine.ppc``'s dict
+        (per statistic "obs", "rep" [S] and the posterior predictive p-value "p"; n; n_non_finite) plus
+        ``partition_stats`` [n_partitions, S, 8] and ``partition_obs`` [n_partitions, 8].  Regression families
+        with at most 128 covariates: ValueError otherwise, before a model is built."""
+        if self.family is None:
+            raise RuntimeError("call setStanModel() first")
+        if self.family not in ("linear", "logistic", "poisson"):
+            raise ValueError(f"no ppc for the {self.family} family: the posterior predictive sweep covers the "
+                             "regression families (linear, logistic, poisson), not 8 schools")
+        parts = _rdd.partitions_of(self.rdd)
+        rank, ws = dist.world()
+        mine = dist.local_partitions(len(parts), rank, ws)
+        datas = [self.prepare_data_callback(list(parts[p])) for p in mine]
+        for p, d in zip(mine, datas):
+            if int(d["K"]) > self.PPC_MAX_COLS:
+                raise ValueError(f"ppc covers at most {self.PPC_MAX_COLS} covariates; partition {p} has K = "
+                                 f"{int(d['K'])}")
+        q = unconstrain_draws(self.family, samples, n_cols=int(datas[0]["K"]) if datas else None)
+        S = q.shape[0]
+        local = {}
+        if datas:
+            model = engine.Model(engine.default_context(), self.family, [frontend.pack_data(self.family, d) for d in datas])
+            try:
+                stats, obs = model.posterior_predict(q, seed=seed, streams=list(mine))
+            finally:
+                model.close()
+            local = {p: np.concatenate([np.asarray(st, np.float64).reshape(-1), np.asarray(ob, np.float64).reshape(-1)])
+                     .reshape(1, S * 8 + 8) for p, st, ob in zip(mine, stats, obs)}
+        every = np.concatenate([np.asarray(t, np.float64).reshape(1, S * 8 + 8)
+                                for t in dist.all_gather_partitions(local, len(parts))])
+        pstats, pobs = every[:, :S * 8].reshape(len(parts), S, 8), np.ascontiguousarray(every[:, S * 8:])
+        out = engine.ppc(pstats, pobs)
+        out["partition_stats"], out["partition_obs"] = pstats, pobs
+        return out
+
     BOOT_MAX_COLS = 128       # the weighted bootstrap sweep and the Hessian sweep cover d <= 128
     BOOT_WEIGHTS = {"bayesian": "exponential", "poisson": "poisson"}
 
