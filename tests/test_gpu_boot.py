@@ -34,6 +34,21 @@ def points(truth, R, seed):
     return truth[None, :] + np.random.default_rng(seed).normal(0, 0.1, (R, truth.size))
 
 
+def errors(lp, g, ws, ref, kind):
+    """The largest errors of lp, grad and wsum in units of their bars against ref = br.weighted(...)."""
+    rlp, rg, rws, slp, sg = ref
+    with np.errstate(invalid="ignore", divide="ignore"):      # a scale of 0 (every weight 0): exact
+        el = np.abs(lp.astype(L) - rlp) / (BAR * slp)
+        eg = np.abs(g.astype(L) - rg) / (BAR * sg)
+    e_lp = float(np.where(slp > 0, el, np.where(lp == rlp, 0, np.inf)).max())
+    e_g = float(np.where(sg > 0, eg, np.where(g == rg, 0, np.inf)).max())
+    if kind == "poisson":
+        e_ws = 0.0 if np.array_equal(ws, rws.astype(np.float64)) else np.inf
+    else:
+        e_ws = float((np.abs(ws.astype(L) - rws) / (1e-12 * rws)).max())      # Exp(1) weights are > 0
+    return e_lp, e_g, e_ws
+
+
 @pytest.mark.parametrize("d", DS)
 @pytest.mark.parametrize("family", FAMILIES)
 def test_density_gradient_and_wsum_match_the_restatement(ctx, family, d):
@@ -50,19 +65,11 @@ def test_density_gradient_and_wsum_match_the_restatement(ctx, family, d):
                 m.set_prior(*(prior or (None, None)))
                 for kind in KINDS:
                     W = engine.boot_weights(11, 0, 0, n, 0, max(RS), kind)
-                    rlp, rg, rws, slp, sg = br.weighted(family, X[:n], y[:n], Q, W, prior)
+                    ref = br.weighted(family, X[:n], y[:n], Q, W, prior)
                     lp, g, ws = m.log_density_grad_boot(Q, 0, seed=11, kind=kind)
                     assert lp.shape == (33,) and g.shape == (33, truth.size) and ws.shape == (33,)
                     assert np.isfinite(lp).all() and np.isfinite(g).all()
-                    with np.errstate(invalid="ignore", divide="ignore"):      # a scale of 0 (every weight 0): exact
-                        el = np.abs(lp.astype(L) - rlp) / (BAR * slp)
-                        eg = np.abs(g.astype(L) - rg) / (BAR * sg)
-                    e_lp = float(np.where(slp > 0, el, np.where(lp == rlp, 0, np.inf)).max())
-                    e_g = float(np.where(sg > 0, eg, np.where(g == rg, 0, np.inf)).max())
-                    if kind == "poisson":
-                        e_ws = 0.0 if np.array_equal(ws, rws.astype(np.float64)) else np.inf
-                    else:
-                        e_ws = float((np.abs(ws.astype(L) - rws) / (1e-12 * rws)).max())      # Exp(1) weights are > 0
+                    e_lp, e_g, e_ws = errors(lp, g, ws, ref, kind)
                     for k, v in (("lp", e_lp), ("grad", e_g), ("wsum", e_ws)):
                         worst[k] = max(worst[k], v)
                     assert e_lp <= 1.0 and e_g <= 1.0 and e_ws <= 1.0, (family, n, d, prior, kind, e_lp, e_g, e_ws)
