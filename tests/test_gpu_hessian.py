@@ -18,8 +18,8 @@ BAR = 1e-10
 DBL_MAX = np.finfo(np.float64).max
 FAMILIES = ("logistic", "poisson", "linear")
 # both sides of every 16-column padding edge of d + 1 (the issue's set) and of d + 2 live columns (the
-# kernel's: x, the ones column, linear's residual column)
-DS = (1, 3, 4, 14, 15, 16, 17, 100, 111, 112, 126, 127, 128)
+# kernel's: x, the ones column, linear's residual column): k_hessian<NT>, NT = ceil((d + 2) / 16) = 1 .. 9
+DS = (1, 3, 4, 14, 15, 16, 17, 30, 31, 46, 47, 62, 63, 78, 79, 94, 95, 100, 111, 112, 126, 127, 128)
 NS = (1, 15, 16, 17, 63, 64, 65)
 
 

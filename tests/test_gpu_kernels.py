@@ -348,12 +348,15 @@ def test_combine_general_shards(ctx, orc, S):
                                    atol=1e-11 * np.abs(ref).max())
 
 
-@pytest.mark.parametrize("P,S", [(2, 50), (16, 80), (17, 90), (40, 300), (113, 640), (128, 700), (150, 900)])
+@pytest.mark.parametrize("P,S", [(2, 50), (16, 80), (17, 90), (40, 300), (113, 640), (128, 700), (150, 900),
+                                 (65, 401), (80, 333), (81, 402), (96, 403), (40, 301)])
 def test_combine_sizes_and_blocked_weights(ctx, orc, P, S):
     """Every inverse path (register block Gauss-Jordan on 16 x 16 tiles up to P = 128 -- one
-    to eight tiles, full and ragged last tiles -- and the global-memory pivoted GJ above)
-    vs the numpy restatement, and the blocked call (stk_consensus_blocked) equal to combining
-    the two row blocks separately."""
+    to eight tiles, full and ragged last tiles; five and six tiles at P = 65, 80, 81, 96 -- and the
+    global-memory pivoted GJ above) vs the numpy restatement, and the blocked call
+    (stk_consensus_blocked) equal to combining the two row blocks separately.  S = 401, 333, 403 and 301
+    are odd, 1 and 3 mod 4: rows that are not 16-B aligned, CovLd::row4's scalar loads at every k;
+    402, like 50 and 90, is 2 mod 4: a ragged last group of four after the vector loads."""
     from stark_amd import engine
     rng = np.random.default_rng(P)
     draws = []

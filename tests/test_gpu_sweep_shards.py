@@ -26,33 +26,33 @@ def _rel(a, b):
     return np.abs(a - b) / np.maximum(np.abs(b), 1.0)
 
 
-def _grouped_case(orc, family, d, C, **prior):
-    """Shards of ROWS rows from one generator (the recipe of test_regression_lpgrad, its large-|eta|
+def _grouped_case(orc, family, d, C, rows=ROWS, **prior):
+    """Shards of `rows` rows from one generator (the recipe of test_regression_lpgrad, its large-|eta|
     rows at the head of every shard), the oracle model of each, and C points per shard."""
     rng = np.random.default_rng(1000 * d + C)
-    N = sum(ROWS)
-    off = np.concatenate([[0], np.cumsum(ROWS)])
+    N = sum(rows)
+    off = np.concatenate([[0], np.cumsum(rows)])
     X = rng.uniform(-1.7, 1.7, (N, d))
     beta = rng.normal(0, 1 / np.sqrt(d), d)
     if family == "logistic":
         eta = X @ beta
-        for s, n in enumerate(ROWS):
+        for s, n in enumerate(rows):
             eta[off[s]: off[s] + max(1, n // 50)] *= 80.0     # the +-20 cutoff branches
         y = (rng.uniform(size=N) < 1 / (1 + np.exp(-eta))).astype(np.int32)
         fam, D = orc.FAM_LOGREG, d + 1
     else:
         y = 0.3 + X @ beta + rng.normal(size=N)
         fam, D = orc.FAM_LINREG, d + 2
-    shards = [{"x": X[off[s]: off[s + 1]], "y": y[off[s]: off[s + 1]]} for s in range(len(ROWS))]
+    shards = [{"x": X[off[s]: off[s + 1]], "y": y[off[s]: off[s + 1]]} for s in range(len(rows))]
     oms = [orc.Model(fam, X=sh["x"], y=sh["y"], **prior) for sh in shards]
-    q = rng.normal(0, 0.2, (len(ROWS), C, D))
+    q = rng.normal(0, 0.2, (len(rows), C, D))
     if family == "logistic":
         q[:, 0, 1:] = beta * 40          # large |eta| rows
     elif C >= 2:
         q[:, C - 2, d + 1] = -6.0        # log sigma: exp(-u) scales every term
         q[:, C - 1, d + 1] = 6.0
     else:
-        q[:, 0, d + 1] = np.where(np.arange(len(ROWS)) % 2 == 0, -6.0, 6.0)
+        q[:, 0, d + 1] = np.where(np.arange(len(rows)) % 2 == 0, -6.0, 6.0)
     return shards, oms, q
 
 

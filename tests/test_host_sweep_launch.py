@@ -7,6 +7,7 @@ import os
 
 import pytest
 
+import test_gpu_sweep_widths as SW
 from conftest import GOLDEN
 from test_gpu_sweep16w import WIDTHS, _shape
 from test_gpu_sweep_shards import ROWS, SHAPES
@@ -85,6 +86,70 @@ def test_grouped_sweep_chunks_are_what_the_comment_says():
             assert G == [3, 1, 3, 1, 2], (d, C, G)
         else:
             assert G[0] > 3 and min(G) < max(G), (d, C, G)
+
+
+# ---------------------------------------------------------------- test_gpu_sweep_widths.py
+def _launch_class(d, C):
+    """What picks a sweep's code at (d, C) on the long shard of test_gpu_sweep_widths.py: the kernel, C,
+    rows per tile, the parity of d (16-B or 8-B rows) and the LD handed to the kernel (v1, v2: the LDS row
+    stride; v3: the ring depth; k_sweep16w: waves per block); v3's DMA count per sub-tile; k_sweep16's
+    KF and d mod 4; the 64-chain passes' column tile, k_gemm_bwd<256>'s column blocks and whether pass F
+    has 8 or more 16-column steps."""
+    from stark_amd import engine
+    p = engine.sweep_launch(SW.ROWS[0], d, C)
+    cls = (p["kind"], C, p["T"], d % 2, p["LD"])
+    if p["kind"] == V3:
+        cls += (-(-d // 16),)
+    elif p["kind"] == S16:
+        cls += ((d + 3) // 4, d % 4)
+    elif p["kind"] == GEMM64:
+        cls += (64 if d <= 64 else (128 if d <= 128 else 256), -(-d // 256), -(-d // 16) >= 8)
+    return cls
+
+
+def test_sweep_widths_hold_both_ends_of_every_launch_class():
+    """d = 1 .. 1024 x every batch size: the first and the last d of every class are cases of
+    test_gpu_sweep_widths.py; k_sweep3 shows every ring depth and every DMA count there; and no refusal
+    hides a width (every batch size is one launch at every d)."""
+    first, last = {}, {}
+    for C in SW.PLAN:
+        for d in range(1, 1025):
+            cls = _launch_class(d, C)
+            first.setdefault(cls, d)
+            last[cls] = d
+    assert len(set(SW.WIDTHS)) == len(SW.WIDTHS) and SW.WIDTHS[:128] == list(range(1, 129))
+    missing = sorted({d for cls in first for d in (first[cls], last[cls])} - set(SW.WIDTHS))
+    assert not missing, missing
+    assert {cls[0] for cls in first} == {V1, V2, V3, S16, GEMM64, S16W}
+    v3 = [cls for cls in first if cls[0] == V3]
+    assert {cls[1] for cls in v3} == {1, 2, 4}
+    for C in (1, 2, 4):
+        assert {cls[4] for cls in v3 if cls[1] == C} == {3, 4, 5}                  # ring depths
+        assert {cls[5] for cls in v3 if cls[1] == C} == set(range(1, 8))           # DMAs of X per sub-tile
+    assert {cls[5] for cls in first if cls[0] == S16} == set(range(1, 33))         # every KF
+    assert {cls[2] for cls in first if cls[0] == V1} == {64, 32, 16, 8}
+
+
+def test_sweep_widths_rows_are_what_the_planner_makes_of_them():
+    """Why 1483 and 77 rows (the docstring of test_gpu_sweep_widths.py), at every width of the file."""
+    from stark_amd import engine
+    n, short = SW.ROWS
+    assert -(-n // 64) == 24 and n % 64 == 11                      # 24 tiles of 64 rows, 11 rows in the last
+    for d in SW.WIDTHS:
+        assert engine.chain_batches(SW.POINTS, d) == SW.PLAN
+        for C in SW.PLAN:
+            p, ps = engine.sweep_launch(n, d, C), engine.sweep_launch(short, d, C)
+            assert ps["kind"] == p["kind"] and ps["G"] < p["G"], (d, C, p, ps)     # grouped; Gs above the short shard's G
+            if p["kind"] in (V2, V3, S16) or (p["kind"] == V1 and p["T"] == 64):
+                assert p["G"] == 3, (d, C, p)                      # 3 chunks of 8 tiles: 32 sub-tiles of 16 rows, 8 per
+                if p["kind"] == V3:                                # wave of k_sweep16
+                    assert 3 <= p["LD"] <= 5, (d, C, p)            # a chunk's 8 tiles wrap every ring depth
+            elif p["kind"] == GEMM64:
+                assert p["G"] == 6, (d, C, p)
+            elif p["kind"] == V1:
+                assert p["G"] == -(-n // (8 * p["T"])) > 3, (d, C, p)
+            else:
+                assert p["kind"] == S16W and p["G"] == 2, (d, C, p)
 
 
 def test_wide_sixteen_widths_reach_k_sweep16w():
