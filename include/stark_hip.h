@@ -88,7 +88,7 @@ enum {
 };
 
 /* Model families. */
-enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4 };
+enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEGBIN = 5 };
 /* STK_POISSON: y ~ poisson_log(alpha + x * beta), the unconstrained parameters (alpha, beta[1..d]) in
  * the logistic layout (D = d + 1, P = d + 2: alpha, beta, lp__).  With eta_i = alpha + x_i . beta and
  * mu_i = exp(eta_i), lp = sum_i (y_i eta_i - mu_i) (+ the normal(0, s) prior terms of
@@ -101,6 +101,31 @@ enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4 };
  * metrics, both U-turn criteria, saved states), with two refusals, each STK_E_ARG with a message that
  * names the family: stk_model_create_synthetic (the generator has no Poisson form) and
  * stk_sampler_set_allreduce (full-data mode stays logistic-only). */
+/* STK_NEGBIN: y ~ neg_binomial_2_log(alpha + x * beta, phi), the unconstrained parameters (alpha,
+ * beta[1..d], v = log phi) in the linear layout with phi where sigma is (D = d + 2, P = d + 3: alpha,
+ * beta, phi = e^v, lp__).  With eta_i = alpha + x_i . beta, t_i = eta_i - v, sp(t) = log(1 + e^t) and
+ * sigma(t) = 1 / (1 + e^-t), Stan's neg_binomial_2_log_lpmf<propto = true> (it drops lgamma(y + 1);
+ * logsumexp(eta, log phi) = v + sp(t); parity unpinned at Stan, as for Poisson) is
+ *   ll_i       = sum_{j < y_i} log1p(j / phi) + y_i eta_i - (y_i + phi) sp(t_i)
+ *   d ll_i / d eta = y_i - (y_i + phi) sigma(t_i)          -> d alpha = sum_i, d beta = X^T (.)
+ *   d lp / d v = phi sum_i [psi(y_i + phi) - psi(phi)] - d alpha_lik - phi sum_i sp(t_i) + (prior) + 1
+ *   lp         = sum_i ll_i + priors + v                   (the Jacobian of phi = e^v)
+ * a form without cancelling y v terms.  The phi-only sums depend on the shard's count histogram alone:
+ * with T_j = #{i : y_i > j}, sum_i sum_{j < y_i} log1p(j / phi) = sum_j T_j log1p(j / phi) and sum_i
+ * [psi(y_i + phi) - psi(phi)] = sum_j T_j / (phi + j).  stk_model_create builds each shard's table once
+ * (T_j for j < 1024; the distinct counts past that with their multiplicities, whose remaining terms come
+ * from the asymptotic series of lgamma and digamma); it lives on the device next to the shard, is
+ * released with the model and is no part of the fingerprint.  The sweep evaluates neither lgamma nor
+ * digamma: the table terms are added once per (shard, chain) in the reduce.
+ * Priors: stk_model_set_prior (normal on alpha and beta) and stk_model_set_prior_phi (gamma on phi; flat by
+ * default, as Stan runs the flat program: the posterior is then improper in phi).
+ * There is no switch to Poisson at large phi.  Where e^v overflows or underflows to 0, or a row's exp
+ * overflows, lp is NaN or -inf: never a finite number and never +inf.
+ * The sampler (any chains, the three metrics, both U-turn criteria, saved states), the gradient hooks,
+ * data copy-out and the fingerprints work for the family.  Refused by name with STK_E_ARG, before any
+ * work: stk_model_create_synthetic, stk_sampler_set_allreduce and the analysis sweeps
+ * (stk_log_density_hessian, stk_log_predictive, stk_loo, stk_log_density_draws,
+ * stk_log_density_grad_boot, stk_posterior_predict). */
 
 /* One data shard (= one Spark partition, stark/stark.py:35).
  *   schools: n_rows = J, y[J], sigma[J]                   (example/stark_ex.py:8-11)
@@ -109,7 +134,8 @@ enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4 };
  *   poisson: x[n_rows * n_cols] row-major, y_int[n_rows] >= 0 (checked on the device copy: the
  *            first negative row is named in the error); y and sigma must be NULL -- counts
  *            handed over as doubles as well as ints are refused (STK_E_ARG), here and by
- *            stk_shard_fingerprint_host, instead of one of the two being ignored      */
+ *            stk_shard_fingerprint_host, instead of one of the two being ignored
+ *   negbin : as poisson (x, y_int >= 0, y and sigma NULL)                            */
 typedef struct {
   int64_t n_rows;
   int32_t n_cols;
@@ -219,6 +245,13 @@ STK_API int stk_gen_beta(uint64_t data_seed, int32_t n_cols, double* beta);   /*
  * the default) -- the priors of a `model` block the front end recognises (stark/stark.py:37-39
  * setStanModel of such a program).  Applies to every shard, before sampling. */
 STK_API int stk_model_set_prior(stk_model* m, double alpha_scale, double beta_scale);
+/* STK_NEGBIN only: phi ~ gamma(shape, rate), which adds (shape - 1) v - rate e^v to lp (exponential(r)
+ * is gamma(1, r)).  shape > 0, rate >= 0; (1, 0) is flat, the default.  Every shard, before sampling. */
+STK_API int stk_model_set_prior_phi(stk_model* m, double shape, double rate);
+/* The two phi-only sums of STK_NEGBIN over n counts y_int >= 0 at phi > 0, computed on the host by the
+ * code the device runs (its table builder and term functions): out[0] = sum_i sum_{j < y_i} log1p(j / phi),
+ * out[1] = sum_i [psi(y_i + phi) - psi(phi)].  No device is touched. */
+STK_API int stk_negbin_phi_terms_host(const int32_t* y_int, int64_t n, double phi, double* out);
 STK_API int stk_model_destroy(stk_model* m);
 STK_API int stk_model_info(const stk_model* m, int shard, int32_t* D, int32_t* P, int64_t* n_rows);
 STK_API int stk_model_copy_data(stk_model* m, int shard, double* x, double* y, int32_t* y_int);
@@ -244,10 +277,10 @@ STK_API int stk_model_device_bytes(const stk_model* m, int64_t* bytes);
  * reduction order gives the same bits.
  *
  *   shard fingerprint = fmix( words([family, n_rows, n_cols], 0, 0)     n_cols = 0 for schools; family is
- *                                                                        the STK_* value (poisson: 4)
+ *                                                                        the STK_* value (poisson: 4, negbin: 5)
  *                           + words(x: n_rows * n_cols doubles, row-major, 1, 0)   regressions
  *                           + words(y doubles, 2, 0)                    linreg, schools
- *                           + words(y_int int32, 3, 0)                  logreg, poisson
+ *                           + words(y_int int32, 3, 0)                  logreg, poisson, negbin
  *                           + words(sigma doubles, 4, 0) )              schools
  *
  * Priors are not part of it (the saved state's geometry check covers them).

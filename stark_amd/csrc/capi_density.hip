@@ -43,7 +43,7 @@ int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int
       b.groups.push_back(gr);
       sh += gr.nsh;
     }
-    cp->partial_bytes += sizeof(double) * (size_t)m->nshards * b.Gs * sz * (m->d + 2);
+    cp->partial_bytes += sizeof(double) * (size_t)m->nshards * b.Gs * sz * sweep_pw(m->family, m->d);
     cp->Ct += sz;
     cp->batches.push_back(std::move(b));
   }
@@ -52,7 +52,8 @@ int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int
 }
 // Every batch's sweep over every shard group; then (plan_reduces) every batch's reduction.  `run`
 // holds the run's buffers; a batch's partial-sum region, stride and first chain are filled in here.
-static SweepCall batch_call(const ChainPlan& cp, const ChainBatch& b, SweepCall c) {
+static SweepCall batch_call(const stk_model* m, const ChainPlan& cp, const ChainBatch& b, SweepCall c) {
+  c.nb = m->nb_dev.as<NbShardDev>();   // NULL but for the negative binomial, whose reduce reads it
   c.partial += b.part_off;
   c.Gs = b.Gs;
   c.Ct = cp.Ct;
@@ -61,7 +62,7 @@ static SweepCall batch_call(const ChainPlan& cp, const ChainBatch& b, SweepCall 
 }
 hipError_t plan_sweeps(const stk_model* m, const ChainPlan& cp, const SweepCall& run, hipStream_t st) {
   for (const auto& b : cp.batches) {
-    const SweepCall c = batch_call(cp, b, run);
+    const SweepCall c = batch_call(m, cp, b, run);
     for (const auto& gr : b.groups)
       if (const hipError_t e = stk_launch_sweep(m->family, gr.launch, gr.shard0, gr.nsh, c, st)) return e;
   }
@@ -70,7 +71,7 @@ hipError_t plan_sweeps(const stk_model* m, const ChainPlan& cp, const SweepCall&
 hipError_t plan_reduces(const stk_model* m, const ChainPlan& cp, const SweepCall& run, double* lp, double* g,
                         hipStream_t st) {
   for (const auto& b : cp.batches) {
-    const SweepCall c = batch_call(cp, b, run);
+    const SweepCall c = batch_call(m, cp, b, run);
     for (const auto& gr : b.groups)
       if (const hipError_t e = stk_launch_sweep_reduce(m->family, gr.launch, gr.shard0, gr.nsh, c, lp, g, st)) return e;
   }
@@ -217,7 +218,7 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
 // group's own G.
 int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_shards: bad arguments");
-  ARG_CHECK(is_regression(m->family), "stk_log_density_grad_shards: regression families only");
+  ARG_CHECK(is_sweep_family(m->family), "stk_log_density_grad_shards: regression families only");
   ARG_CHECK(hook_single_launch(C, m->d), "points per shard must be a single batch size here: 1, 2, 4, 8, 16 (d <= 128) or 64");
   return hook_every_shard(m, {C}, q, lp, grad);
 }
@@ -226,7 +227,7 @@ int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double
 // run at chains = C.
 int stk_log_density_grad_chains(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_chains: bad arguments");
-  ARG_CHECK(is_regression(m->family), "stk_log_density_grad_chains: regression families only");
+  ARG_CHECK(is_sweep_family(m->family), "stk_log_density_grad_chains: regression families only");
   ARG_CHECK(!chain_batches(C, m->d).empty(), "no sweep covers %d covariates (1..1024)", m->d);
   return hook_every_shard(m, chain_batches(C, m->d), q, lp, grad);
 }

@@ -94,6 +94,8 @@ struct stk_model {
   std::vector<ShardDev> sh;
   std::vector<DevBuf> bufs;
   DevBuf sh_dev;
+  std::vector<NbShardDev> nb;   // STK_NEGBIN: per shard, the count table (in bufs) and the phi prior; derived data
+  DevBuf nb_dev;                // its device copy, what the reduce reads
   int64_t bytes = 0;
   std::vector<uint64_t> fp;   // shard fingerprints, computed on first use (the data never changes)
   std::vector<char> fp_ok;
@@ -114,7 +116,7 @@ struct ChainBatch {
 struct ChainPlan {
   std::vector<ChainBatch> batches;
   int Ct = 0;
-  size_t partial_bytes = 0;   // every batch's [nshards][Gs][C][d + 2] doubles
+  size_t partial_bytes = 0;   // every batch's [nshards][Gs][C][sweep_pw] doubles
   SweepLaunch ws_at{};        // the 64-batch launch of the shard with the most rows (kind 0: no workspace)
   size_t ws_bytes = 0;        // its workspace for every shard of the model
 };
@@ -166,7 +168,8 @@ bool is_device_ptr(const void* p, int device);
 
 // ---- capi_model.hip
 const char* family_name(int family);
-bool is_regression(int family);
+bool is_regression(int family);     // linear, logistic, poisson: every regression entry point
+bool is_sweep_family(int family);   // those and neg_binomial: the gradient sweeps, the sampler, the priors
 void model_release(stk_model* m);
 int model_fingerprint(stk_model* m, int shard, uint64_t* out);   // cached
 // shard == -1 means every shard: the first shard, how many, and the largest per-shard chunk count.

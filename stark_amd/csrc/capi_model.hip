@@ -8,11 +8,15 @@ const char* family_name(int family) {
     case STK_LINREG: return "linear";
     case STK_LOGREG: return "logistic";
     case STK_POISSON: return "poisson";
+    case STK_NEGBIN: return "neg_binomial";
   }
   return "unknown";
 }
 
+// The families every regression entry point serves (the analysis sweeps among them)...
 bool is_regression(int family) { return family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON; }
+// ...and those the gradient sweeps, the sampler and the priors serve: the negative binomial too.
+bool is_sweep_family(int family) { return is_regression(family) || family == STK_NEGBIN; }
 
 ShardRange shard_range(const stk_model* m, int shard, int (*chunks)(int64_t n)) {
   ShardRange r{shard < 0 ? 0 : shard, shard < 0 ? m->nshards : 1, 1};
@@ -26,6 +30,7 @@ static int family_dims(int family, int64_t n, int d, int* D, int* P) {
     case STK_LINREG: *D = d + 2; *P = d + 3; return STK_OK;
     case STK_LOGREG: *D = d + 1; *P = d + 2; return STK_OK;
     case STK_POISSON: *D = d + 1; *P = d + 2; return STK_OK;   // the logistic layout: alpha, beta, lp__
+    case STK_NEGBIN: *D = d + 2; *P = d + 3; return STK_OK;    // the linear layout: alpha, beta, phi (v = log phi), lp__
   }
   stk_set_error("unknown model family %d", family);
   return STK_E_ARG;
@@ -43,13 +48,24 @@ static stk_model* model_new(stk_ctx* ctx, int family, int nshards, int d) {
   return m;
 }
 
+static int upload_nb_table(stk_model* m);
 static int upload_shard_table(stk_model* m) {
   for (auto& s : m->sh) {
     m->Dmax = std::max(m->Dmax, s.D);
     m->Pmax = std::max(m->Pmax, s.P);
   }
+  if (m->family == STK_NEGBIN) RC(upload_nb_table(m));
   RC(m->sh_dev.ensure(sizeof(ShardDev) * m->sh.size()));
   STK_HIP_CHECK(hipMemcpyAsync(m->sh_dev.p, m->sh.data(), sizeof(ShardDev) * m->sh.size(), hipMemcpyHostToDevice,
+                               m->ctx->stream));
+  STK_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  return STK_OK;
+}
+
+// The model's [nshards] NbShardDev (count tables and phi priors) to the device; again after a prior changes.
+static int upload_nb_table(stk_model* m) {
+  RC(m->nb_dev.ensure(sizeof(NbShardDev) * m->nb.size()));
+  STK_HIP_CHECK(hipMemcpyAsync(m->nb_dev.p, m->nb.data(), sizeof(NbShardDev) * m->nb.size(), hipMemcpyHostToDevice,
                                m->ctx->stream));
   STK_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
   return STK_OK;
@@ -79,7 +95,7 @@ static int upload(stk_model* m, const T* src, size_t count, const T** dst) {
 
 // bernoulli_logit: y in {0, 1} (the sweeps read y as a sign bit); poisson_log: y >= 0.  Checked on the
 // device copy by a reduction that returns the first bad row (8 bytes back, not the shard).
-static int check_y_int(stk_model* m, int s, const int32_t* yi, int64_t n, bool pois) {
+static int check_y_int(stk_model* m, int s, const int32_t* yi, int64_t n, bool pois, const char* pois_rule) {
   hipStream_t st = m->ctx->stream;
   DevBuf flag;
   RC(flag.ensure(sizeof(int64_t)));
@@ -95,7 +111,53 @@ static int check_y_int(stk_model* m, int s, const int32_t* yi, int64_t n, bool p
     return STK_E_HIP;
   }
   ARG_CHECK(bad < 0 || bad >= n, "shard %d: y_int[%lld] = %d; %s", s, (long long)bad, v,
-            pois ? "poisson_log needs y >= 0" : "bernoulli_logit needs 0 or 1");
+            pois ? pois_rule : "bernoulli_logit needs 0 or 1");
+  return STK_OK;
+}
+
+// The count table of a negative-binomial shard (negbin_math.h) from its n counts, all >= 0: the tail
+// counts T_j = #{i : y_i > j} for j < ncap = min(max y, NB_CAP), then (value, multiplicity) of every
+// distinct count past NB_CAP, ascending.
+static void nb_build_table(const int32_t* y, int64_t n, std::vector<double>* tab, int* ncap, int* nbig) {
+  std::vector<int64_t> hist(NB_CAP + 1, 0);   // hist[k] = #{y_i = k}, k <= NB_CAP; the rest in `big`
+  std::vector<int32_t> big;
+  int32_t ymax = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    ymax = std::max(ymax, y[i]);
+    if (y[i] <= NB_CAP) hist[y[i]]++;
+    else big.push_back(y[i]);
+  }
+  *ncap = std::min<int32_t>(ymax, NB_CAP);
+  tab->assign(*ncap, 0.0);
+  int64_t above = (int64_t)big.size();        // #{y_i > j}, from j = ncap - 1 down
+  for (int j = *ncap - 1; j >= 0; --j) {
+    above += hist[j + 1];
+    (*tab)[j] = (double)above;
+  }
+  std::sort(big.begin(), big.end());
+  *nbig = 0;
+  for (size_t i = 0; i < big.size();) {
+    size_t k = i;
+    while (k < big.size() && big[k] == big[i]) ++k;
+    tab->push_back((double)big[i]);
+    tab->push_back((double)(k - i));
+    ++*nbig;
+    i = k;
+  }
+}
+
+// Build shard s's table from its device copy of y_int (checked >= 0) and keep it next to the shard.
+static int attach_nb_table(stk_model* m, const int32_t* yi_dev, int64_t n) {
+  std::vector<int32_t> y((size_t)n);
+  STK_HIP_CHECK(hipMemcpyAsync(y.data(), yi_dev, sizeof(int32_t) * n, hipMemcpyDeviceToHost, m->ctx->stream));
+  STK_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  std::vector<double> tab;
+  NbShardDev nb{};
+  nb_build_table(y.data(), n, &tab, &nb.ncap, &nb.nbig);
+  if (tab.empty()) tab.push_back(0.0);   // all counts zero: an empty table (ncap = nbig = 0)
+  RC(upload(m, tab.data(), tab.size(), &nb.tab));
+  STK_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));   // tab is a local: the copy must have read it
+  m->nb.push_back(nb);
   return STK_OK;
 }
 
@@ -117,13 +179,15 @@ static int upload_shard(stk_model* m, int s, const stk_shard& in) {
     ARG_CHECK(in.x && in.n_cols > 0, "shard %d: regression needs x", s);
     ARG_CHECK(stk_sweep_supported(1, in.n_cols), "n_cols %d unsupported (1..1024)", in.n_cols);
     RC(upload(m, in.x, n * in.n_cols, &sd.x));
-    if (family == STK_LOGREG || family == STK_POISSON) {
-      const bool pois = family == STK_POISSON;
-      ARG_CHECK(in.y_int, "shard %d: %s needs y_int", s, pois ? "poisson" : "logreg");
+    if (family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN) {
+      const bool pois = family != STK_LOGREG;   // a count family
+      const char* fam = family == STK_NEGBIN ? "neg_binomial" : pois ? "poisson" : "logreg";
+      ARG_CHECK(in.y_int, "shard %d: %s needs y_int", s, fam);
       // counts handed over as doubles too: say so, do not pick one of the two
-      ARG_CHECK(!pois || (!in.y && !in.sigma), "shard %d: poisson takes its counts in y_int alone; y and sigma must be NULL", s);
+      ARG_CHECK(!pois || (!in.y && !in.sigma), "shard %d: %s takes its counts in y_int alone; y and sigma must be NULL", s, fam);
       RC(upload(m, in.y_int, n, &sd.yi));
-      RC(check_y_int(m, s, sd.yi, in.n_rows, pois));
+      RC(check_y_int(m, s, sd.yi, in.n_rows, pois, family == STK_NEGBIN ? "neg_binomial_2_log needs y >= 0" : "poisson_log needs y >= 0"));
+      if (family == STK_NEGBIN) RC(attach_nb_table(m, sd.yi, in.n_rows));
     } else {   // family_dims knows every family: a new one must say here which y it takes
       ARG_CHECK(family == STK_LINREG, "shard %d: model family %d has no data layout", s, family);
       ARG_CHECK(in.y, "shard %d: linreg needs y", s);
@@ -180,6 +244,7 @@ void model_release(stk_model* m) {
   hipStreamSynchronize(c->stream);
   for (auto& b : m->bufs) b.release();
   m->sh_dev.release();
+  m->nb_dev.release();
   delete m;
   ctx_release(c);
 }
@@ -289,7 +354,7 @@ int stk_model_copy_data(stk_model* m, int shard, double* x, double* y, int32_t* 
 
 int stk_model_set_prior(stk_model* m, double alpha_scale, double beta_scale) {
   ARG_CHECK(m, "stk_model_set_prior: NULL model");
-  ARG_CHECK(is_regression(m->family), "priors apply to the regression families");
+  ARG_CHECK(is_sweep_family(m->family), "priors apply to the regression families");
   ARG_CHECK(alpha_scale >= 0.0 && beta_scale >= 0.0, "prior scales must be >= 0 (0 or inf: flat)");
   auto prec = [](double sc) { return (sc == 0.0 || std::isinf(sc)) ? 0.0 : 1.0 / (sc * sc); };
   for (auto& sd : m->sh) {
@@ -298,6 +363,41 @@ int stk_model_set_prior(stk_model* m, double alpha_scale, double beta_scale) {
   }
   STK_HIP_CHECK(hipSetDevice(m->ctx->device));
   STK_HIP_CHECK(hipMemcpy(m->sh_dev.p, m->sh.data(), sizeof(ShardDev) * m->sh.size(), hipMemcpyHostToDevice));
+  return STK_OK;
+}
+
+int stk_model_set_prior_phi(stk_model* m, double shape, double rate) {
+  ARG_CHECK(m, "stk_model_set_prior_phi: NULL model");
+  ARG_CHECK(m->family == STK_NEGBIN, "stk_model_set_prior_phi: a prior on phi is for the neg_binomial family, not for the %s family (%d)",
+            family_name(m->family), m->family);
+  ARG_CHECK(shape > 0.0 && std::isfinite(shape) && rate >= 0.0 && std::isfinite(rate),
+            "stk_model_set_prior_phi: phi ~ gamma(shape, rate) needs shape > 0 and rate >= 0 (1, 0: flat), got (%g, %g)", shape, rate);
+  for (auto& nb : m->nb) {
+    nb.pr_a1 = shape - 1.0;
+    nb.pr_b = rate;
+  }
+  STK_HIP_CHECK(hipSetDevice(m->ctx->device));
+  return upload_nb_table(m);
+}
+
+int stk_negbin_phi_terms_host(const int32_t* y_int, int64_t n, double phi, double* out) {
+  ARG_CHECK(y_int && out && n > 0, "stk_negbin_phi_terms_host: bad arguments");
+  ARG_CHECK(phi > 0.0 && std::isfinite(phi), "stk_negbin_phi_terms_host: phi must be positive and finite, got %g", phi);
+  for (int64_t i = 0; i < n; ++i)
+    ARG_CHECK(y_int[i] >= 0, "stk_negbin_phi_terms_host: y_int[%lld] = %d; neg_binomial_2_log needs y >= 0", (long long)i, y_int[i]);
+  std::vector<double> tab;
+  int ncap = 0, nbig = 0;
+  nb_build_table(y_int, n, &tab, &ncap, &nbig);
+  const double v = log(phi);
+  double a1 = 0.0, a2 = 0.0;
+  for (int e = 0; e < ncap + nbig; ++e) {
+    double t1, t2;
+    nb_entry_term(tab.data(), ncap, e, phi, v, &t1, &t2);
+    a1 += t1;
+    a2 += t2;
+  }
+  out[0] = a1;
+  out[1] = a2 / phi;   // the device keeps phi sum [psi(y + phi) - psi(phi)], what d lp / d v takes
   return STK_OK;
 }
 
@@ -355,7 +455,7 @@ int stk_fingerprint_words(stk_ctx* ctx, const void* buf, int64_t count, int32_t 
 
 int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
   ARG_CHECK(sh && out, "stk_shard_fingerprint_host: bad arguments");
-  ARG_CHECK(family == STK_SCHOOLS || family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON,
+  ARG_CHECK(family == STK_SCHOOLS || family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN,
             "unknown model family %d", family);
   ARG_CHECK(sh->n_rows > 0, "stk_shard_fingerprint_host: n_rows must be positive");
   uint64_t acc = fp_shard_header(family, sh->n_rows, sh->n_cols);
@@ -365,10 +465,11 @@ int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
   } else {
     ARG_CHECK(sh->x && sh->n_cols > 0, "stk_shard_fingerprint_host: regression needs x");
     acc += stk_fp_words_host(sh->x, sh->n_rows * sh->n_cols, 8, 1, 0);
-    if (family == STK_LOGREG || family == STK_POISSON) {
-      ARG_CHECK(sh->y_int, "stk_shard_fingerprint_host: %s needs y_int", family == STK_POISSON ? "poisson" : "logreg");
-      ARG_CHECK(family != STK_POISSON || (!sh->y && !sh->sigma),
-                "stk_shard_fingerprint_host: poisson takes its counts in y_int alone; y and sigma must be NULL");
+    if (family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN) {
+      const char* fam = family == STK_NEGBIN ? "neg_binomial" : family == STK_POISSON ? "poisson" : "logreg";
+      ARG_CHECK(sh->y_int, "stk_shard_fingerprint_host: %s needs y_int", fam);
+      ARG_CHECK(family == STK_LOGREG || (!sh->y && !sh->sigma),
+                "stk_shard_fingerprint_host: %s takes its counts in y_int alone; y and sigma must be NULL", fam);
       acc += stk_fp_words_host(sh->y_int, sh->n_rows, 4, 3, 0);
     } else {
       ARG_CHECK(sh->y, "stk_shard_fingerprint_host: linreg needs y");

@@ -3,6 +3,7 @@
 // that drifts is a compile error instead of a second overload that links and runs.
 #pragma once
 #include "common.h"
+#include "negbin_math.h"
 
 namespace stk {
 
@@ -47,7 +48,12 @@ struct SweepCall {
   int Dp;
   int Gs;                 // partial-sum stride in chunks per shard: the largest G of the batch's groups
   int Ct, c0;             // chains per shard in q / lp / grad, first chain of this batch
+  const NbShardDev* nb = nullptr;   // STK_NEGBIN: the model's [nshards] count tables and phi priors (the reduce reads them)
 };
+
+// Columns of a chunk's partial row per chain: d alpha, d beta[1..d], the lp sum -- and, for the
+// negative binomial, the unweighted sum of sp(t) that its v gradient needs.
+inline int sweep_pw(int family, int d) { return d + (family == STK_NEGBIN ? 3 : 2); }
 
 }  // namespace stk
 
@@ -67,12 +73,18 @@ hipError_t stk_launch_sweep_poisson(const stk::SweepLaunch& p, const stk::SweepA
 hipError_t stk_launch_gemm_fwd_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
 hipError_t stk_launch_sweep_reduce_poisson(const stk::SweepArgs& A, int nblocks_x, int nblocks_y, double* lp_out,
                                            double* g_out, int C, hipStream_t st);
+// ---- sweep_nb.hip (sweep.hip's negative-binomial translation unit): the same, and its own reduce
+hipError_t stk_launch_sweep_negbin(const stk::SweepLaunch& p, const stk::SweepArgs& A, int nblocks, hipStream_t st);
+hipError_t stk_launch_gemm_fwd_negbin(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
+hipError_t stk_launch_sweep_reduce_negbin(const stk::SweepArgs& A, const stk::NbShardDev* nb, int nchains, int d,
+                                          double* lp_out, double* g_out, int C, hipStream_t st);
 
 // ---- sweep16.hip: shapes k_sweep16 covers, its LDS bytes, its launch
 bool stk_sweep16_supported(int d);
 size_t stk_sweep16_lds_bytes(int family, int d);
 hipError_t stk_launch_sweep16(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
 hipError_t stk_launch_sweep16_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16_pois.hip
+hipError_t stk_launch_sweep16_negbin(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);    // sweep16_nb.hip
 
 // ---- sweep16w.hip (128 < d <= 1024): waves per block, chunks per shard, LDS bytes, launch
 bool stk_sweep16w_supported(int d);
@@ -81,6 +93,7 @@ int stk_sweep16w_chunks(int64_t n);
 size_t stk_sweep16w_lds_bytes(int family, int d);
 hipError_t stk_launch_sweep16w(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
 hipError_t stk_launch_sweep16w_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16w_pois.hip
+hipError_t stk_launch_sweep16w_negbin(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);    // sweep16w_nb.hip
 
 // ---- hessian.hip (regressions, d <= 128): the analytic Hessian sweep's geometry and launch
 bool stk_hessian_supported(int d);

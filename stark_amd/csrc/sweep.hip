@@ -24,13 +24,22 @@
 #include <set>
 #include <type_traits>
 
+// A family's own translation unit (sweep_pois.hip, sweep_nb.hip) holds that family's instantiations
+// and launchers only: what is not a template is defined once, in sweep.hip itself.
+#if defined(STK_SWEEP_POISSON_TU) || defined(STK_SWEEP_NEGBIN_TU)
+#define STK_SWEEP_FAMILY_TU 1
+#endif
+
 namespace stk {
 
 // A family is a residual, not a kernel: every sweep takes FAM and must know it.
 template <int FAM>
-constexpr bool fam_known = FAM == STK_LINREG || FAM == STK_LOGREG || FAM == STK_POISSON;
+constexpr bool fam_known = FAM == STK_LINREG || FAM == STK_LOGREG || FAM == STK_POISSON || FAM == STK_NEGBIN;
 template <int FAM>
-constexpr bool fam_yint = FAM == STK_LOGREG || FAM == STK_POISSON;   // y is the shard's int32 y_int
+constexpr bool fam_yint = FAM == STK_LOGREG || FAM == STK_POISSON || FAM == STK_NEGBIN;   // y is the shard's int32 y_int
+// The scalar next to beta, q[d + 1], as the kernels carry it per chain in their inv_s slot: linear
+// 1 / sigma = exp(-u); negative binomial v = log phi itself, with phi = exp(v) kept beside it (once per
+// chain, not per element); the others have none.
 
 template <int FAM, int C, int T, int JPT, int VEC>
 __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
@@ -58,7 +67,16 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
   if (tid < C) {
     const double* qc = A.q + chain_row(A, shard, tid) * A.Dp;
     Al[tid] = qc[0];
-    Al[C + tid] = (FAM == STK_LINREG) ? exp(-qc[d + 1]) : 0.0;
+    Al[C + tid] = (FAM == STK_LINREG) ? exp(-qc[d + 1]) : (FAM == STK_NEGBIN) ? qc[d + 1] : 0.0;
+  }
+  constexpr bool NB = FAM == STK_NEGBIN;
+  double nbphi[NB ? C : 1], ssa[NB ? C : 1];   // negative binomial: phi_c, sum of sp
+  if constexpr (NB) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      nbphi[c] = exp(A.q[chain_row(A, shard, c) * A.Dp + d + 1]);
+      ssa[c] = 0.0;
+    }
   }
 
   // per-thread accumulators
@@ -158,6 +176,8 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
             const double mu = exp(eta);
             lpa[c] = fma(yc, eta, lpa[c] - mu);
             de = yc - mu;
+          } else if constexpr (NB) {
+            de = negbin_resid_libm(eta, (double)gp(sh.yi)[row], Al[C + c], nbphi[c], lpa[c], ssa[c]);
           } else {
             static_assert(fam_known<FAM>, "k_sweep: unknown family");
             const double is = Al[C + c];
@@ -220,6 +240,17 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
     for (int i = 0; i < NT; ++i) v += src[i];
     out[(size_t)c * A.PW + (is_lp ? d + 1 : 0)] = v;
   }
+  if constexpr (NB) {   // the third scalar sum, column d + 2, through the same area
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < C; ++c) red[(size_t)c * NT + tid] = ssa[c];
+    __syncthreads();
+    if (tid < C) {
+      double v = 0.0;
+      for (int i = 0; i < NT; ++i) v += red[(size_t)tid * NT + i];
+      out[(size_t)tid * A.PW + d + 2] = v;
+    }
+  }
 }
 
 // v2 sweep for d <= 128 (T = 64-row tiles, 4 waves):
@@ -229,8 +260,10 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
 //   backward  wave w owns rows [16w, 16w+16), lane = column (JPT = 2), residuals broadcast.
 // LDS row stride LD is odd, so lane-per-row reads and lane-per-column reads are both free of
 // bank conflicts; tiles are register-prefetched one ahead (global_load_dwordx4).
+// (The negative binomial at C = 8 keeps phi_c beside v_c and a third sum: one block per CU's worth of
+// registers there, instead of spilling.)
 template <int FAM, int C>
-__global__ __launch_bounds__(256, 2) void k_sweep2(SweepArgs A) {
+__global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_sweep2(SweepArgs A) {
   constexpr int T = 64, NT = 256, JPT = 2;
   constexpr int CP = (T * C + NT - 1) / NT;       // residual pairs per thread
   constexpr int NVMAX = (T * 128 / 2 + NT - 1) / NT;
@@ -258,7 +291,15 @@ __global__ __launch_bounds__(256, 2) void k_sweep2(SweepArgs A) {
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     alpha[c] = qs[(size_t)c * A.Dp];
-    inv_s[c] = (FAM == STK_LINREG) ? exp(-qs[(size_t)c * A.Dp + d + 1]) : 0.0;
+    inv_s[c] = (FAM == STK_LINREG) ? exp(-qs[(size_t)c * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)c * A.Dp + d + 1] : 0.0;
+  }
+  constexpr bool NB = FAM == STK_NEGBIN;
+  double nbphi[NB ? C : 1], ssa[NB ? CP : 1];   // negative binomial: phi_c, sum of sp per residual pair
+  if constexpr (NB) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) nbphi[c] = exp(inv_s[c]);
+#pragma unroll
+    for (int i = 0; i < CP; ++i) ssa[i] = 0.0;
   }
 
   double gacc[JPT][C];
@@ -351,6 +392,12 @@ __global__ __launch_bounds__(256, 2) void k_sweep2(SweepArgs A) {
             const double mu = exp(eta);
             lpa[i] = fma(yc, eta, lpa[i] - mu);
             de = yc - mu;
+          } else if constexpr (NB) {
+            double ph = nbphi[0];
+#pragma unroll
+            for (int cc = 1; cc < C; ++cc)
+              if (cc == c) ph = nbphi[cc];
+            de = negbin_resid_libm(eta, (double)ycur, is, ph, lpa[i], ssa[i]);
           } else {
             const double z = (ycur - eta) * is;
             lpa[i] += z * z;
@@ -412,6 +459,18 @@ __global__ __launch_bounds__(256, 2) void k_sweep2(SweepArgs A) {
     double v = 0.0;
     for (int k = 0; k < 64; ++k) v += src[k];
     out[(size_t)c * A.PW + (kind == 0 ? d + 1 : 0)] = v;
+  }
+  if constexpr (NB) {   // the third scalar sum, column d + 2, through the same area
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < CP; ++i) red[(size_t)i * NT + tid] = ssa[i];
+    __syncthreads();
+    if (tid < C) {
+      const double* src = red + (size_t)((tid * 64) / NT) * NT + (tid * 64) % NT;
+      double v = 0.0;
+      for (int k = 0; k < 64; ++k) v += src[k];
+      out[(size_t)tid * A.PW + d + 2] = v;
+    }
   }
 }
 
@@ -520,7 +579,10 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
   }
   const int rc = fi < C ? fi : 0;                        // residual chain of this lane
   const double alpha = qs[(size_t)rc * A.Dp];
-  const double inv_s = (FAM == STK_LINREG) ? exp(-qs[(size_t)rc * A.Dp + d + 1]) : 0.0;
+  const double inv_s = (FAM == STK_LINREG) ? exp(-qs[(size_t)rc * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)rc * A.Dp + d + 1] : 0.0;
+  constexpr bool NEGB = FAM == STK_NEGBIN;
+  double nbphi = 0.0, ssa = 0.0;                          // negative binomial: phi of chain rc, sum of sp
+  if constexpr (NEGB) nbphi = exp(inv_s);
   __builtin_amdgcn_s_waitcnt(0xF70);                      // ordinary loads retired before the DMAs start
 
   // ---- DMA issue: sub-tile t of this wave = rows [64 t + 8 w, 64 t + 8 w + 8) of the chunk:
@@ -606,6 +668,8 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
           const double mu = exp(eta);
           lpa = fma(yc, eta, lpa - mu);
           de = yc - mu;
+        } else if constexpr (NEGB) {
+          de = negbin_resid_libm(eta, (double)*reinterpret_cast<const int32_t*>(ys + frow * 4), inv_s, nbphi, lpa, ssa);
         } else {
           const double yv = *reinterpret_cast<const double*>(ys + frow * 8);
           const double z = (yv - eta) * inv_s;
@@ -669,6 +733,17 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
       for (int g = 0; g < 8; ++g) v += red2[(size_t)(ww * 64 + g * 8 + c) * 2 + kind];
     out[(size_t)c * A.PW + (kind == 0 ? d + 1 : 0)] = v;
   }
+  if constexpr (NEGB) {   // the third scalar sum, column d + 2, through the same area
+    __syncthreads();
+    red2[(size_t)tid * 2] = ssa;
+    __syncthreads();
+    if (tid < C) {
+      double v = 0.0;
+      for (int ww = 0; ww < NW; ++ww)
+        for (int g = 0; g < 8; ++g) v += red2[(size_t)(ww * 64 + g * 8 + tid) * 2];
+      out[(size_t)tid * A.PW + d + 2] = v;
+    }
+  }
 }
 
 
@@ -698,7 +773,7 @@ __device__ __forceinline__ int g5_chain_off(int r, int c) { return r * 512 + (((
 
 // beta^T images for pass F: qT[shard][k][.] = beta_c[k] (0 for k >= d), swizzled as g5_chain_off.
 // (Not a template: defined once, in sweep.hip itself.)
-#ifndef STK_SWEEP_POISSON_TU
+#ifndef STK_SWEEP_FAMILY_TU
 __global__ __launch_bounds__(256) void k_qt_swizzle(SweepArgs A, int d) {
   const int shard = A.shard0 + blockIdx.y;
   if (A.req_step && A.req_step[shard] != A.step_id - 1) return;
@@ -748,8 +823,10 @@ __device__ __forceinline__ void dma16_lds(__amdgpu_buffer_rsrc_t r, char* dst, i
 // (a store still in flight only makes the count larger).  DESIGN.md section 3.
 // (Template geometry for tools/gemm_fwd_ab.py's A/B arms: NW waves of RT 16-row tiles, KCF-column
 // stages, an NS-deep ring; the product launches the defaults with SPLIT 0 or 1.)
+// (The negative binomial's residual -- a log1p per element, phi and a third sum per chain tile -- does
+// not fit beside the 128 accumulator and parked-eta registers at two blocks per CU: it runs one.)
 template <int FAM, int NW = G5_FW, int RT = 2, int KCF = G5_FKC, int NS = G5_FS, int SPLIT = 0>
-__global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
+__global__ __launch_bounds__(64 * NW, FAM == STK_NEGBIN ? 1 : 8 / NW) void k_gemm_fwd(SweepArgs A) {
   constexpr int NCT = 4, TR = 16 * RT * NW;
   constexpr int XB = TR * KCF * 8, BB = KCF * 512, STG = XB + BB;
   constexpr int PPR = KCF / 2;                          // 16-B pieces per X row in the stage (8)
@@ -781,14 +858,21 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
   char* const stg = reinterpret_cast<char*>(lds);      // NS stages of STG bytes
   double* const sptab = reinterpret_cast<double*>(stg + NS * STG);
   static_assert(fam_known<FAM>, "k_gemm_fwd: unknown family");
-  if constexpr (FAM == STK_LOGREG || FAM == STK_POISSON) exp_table_init(sptab);
+  if constexpr (FAM == STK_LOGREG || FAM == STK_POISSON || FAM == STK_NEGBIN) exp_table_init(sptab);
   // per-lane chain constants: chain 16 c2 + lr
   const double* qb = A.q + chain_row(A, shard) * A.Dp;
   double alpha[NCT], inv_s[NCT];
 #pragma unroll
   for (int c2 = 0; c2 < NCT; ++c2) {
     alpha[c2] = qb[(size_t)(16 * c2 + lr) * A.Dp];
-    inv_s[c2] = (FAM == STK_LINREG) ? exp(-qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1]) : 0.0;
+    inv_s[c2] = (FAM == STK_LINREG) ? exp(-qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1])
+                : (FAM == STK_NEGBIN) ? qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1] : 0.0;
+  }
+  constexpr bool NB = FAM == STK_NEGBIN;
+  double nbphi[NB ? NCT : 1];                          // negative binomial: phi of the lane's chains (inv_s holds v)
+  if constexpr (NB) {
+#pragma unroll
+    for (int c2 = 0; c2 < NCT; ++c2) nbphi[c2] = exp(inv_s[c2]);
   }
   __syncthreads();
   __builtin_amdgcn_s_waitcnt(0xF70);
@@ -812,7 +896,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
     for (int i = 0; i < NDB; ++i) dma16_lds(br, b + XB + (w * NDB + i) * 1024, lane * 16, kc * KCF * 512 + (w * NDB + i) * 1024);
   };
   // per chain tile: logistic lm = sum(t - |t|) - 2 sum(flushed log1p(sp)), sp = prod(1 + e) - 1
-  // (residual v4, sweep_common.h); linear: lm = sum z^2; poisson: lm = sum (y eta - mu), the lp itself
+  // (residual v4, sweep_common.h); linear: lm = sum z^2; poisson: lm = sum (y eta - mu), the lp itself;
+  // negative binomial: lm = sum (y eta - (y + phi) sp(t)) and sp = sum sp(t)
   double lm[NCT], sp[NCT], gaa[NCT];
 #pragma unroll
   for (int c2 = 0; c2 < NCT; ++c2) lm[c2] = sp[c2] = gaa[c2] = 0.0;
@@ -842,6 +927,11 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
         double lm2 = lm[c2];
         dv = pois_resid(eta, pyc[rt][i], sptab, lm2);
         lm[c2] = valid ? lm2 : lm[c2];
+      } else if constexpr (NB) {
+        double lm2 = lm[c2], sp2 = sp[c2];
+        dv = negbin_resid(eta, pyc[rt][i], inv_s[c2], nbphi[c2], sptab, lm2, sp2);
+        lm[c2] = valid ? lm2 : lm[c2];
+        sp[c2] = valid ? sp2 : sp[c2];
       } else {
         const double z = (pyt[rt][i] - eta) * inv_s[c2];
         lm[c2] += valid ? z * z : 0.0;
@@ -883,7 +973,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
         for (int i = 0; i < 4; ++i) {
           const int64_t grow = (int64_t)(st / NKC) * TR + 16 * RT * w + 16 * rt + lh + 4 * i;
           if constexpr (FAM == STK_LOGREG) ybit |= (grow < nrows ? (uint32_t)sh.yi[r0 + grow] & 1u : 0u) << (4 * rt + i);
-          else if constexpr (FAM == STK_POISSON) yc[rt][i] = grow < nrows ? sh.yi[r0 + grow] : 0;
+          else if constexpr (FAM == STK_POISSON || NB) yc[rt][i] = grow < nrows ? sh.yi[r0 + grow] : 0;
           else yt[rt][i] = grow < nrows ? sh.y[r0 + grow] : 0.0;
         }
     }
@@ -915,7 +1005,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
         for (int i = 0; i < 4; ++i) pend[rt][c2][i] = acc[rt][c2][i] + alpha[c2];
 #pragma unroll
       for (int i = 0; i < 4; ++i) pyt[rt][i] = yt[rt][i];
-      if constexpr (FAM == STK_POISSON) {
+      if constexpr (FAM == STK_POISSON || NB) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) pyc[rt][i] = yc[rt][i];
       }
@@ -963,6 +1053,19 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void k_gemm_fwd(SweepArgs A) {
     for (int ww = 0; ww < NW; ++ww)
       for (int h = 0; h < 4; ++h) v += red[((ww * 64 + h * 16 + l) * NCT + c2) * 2 + kind];
     A.partial[(((size_t)shard * A.Gs + chunk) * G5_C + c) * A.PW + (kind == 0 ? d + 1 : 0)] = v;
+  }
+  if constexpr (NB) {   // the third scalar sum, column d + 2, through the same area
+    __syncthreads();
+#pragma unroll
+    for (int c2 = 0; c2 < NCT; ++c2) red[((w * 64 + lane) * NCT + c2) * 2] = sp[c2];
+    __syncthreads();
+    if (tid < G5_C) {
+      const int c2 = tid >> 4, l = tid & 15;
+      double v = 0.0;
+      for (int ww = 0; ww < NW; ++ww)
+        for (int h = 0; h < 4; ++h) v += red[((ww * 64 + h * 16 + l) * NCT + c2) * 2];
+      A.partial[(((size_t)shard * A.Gs + chunk) * G5_C + tid) * A.PW + d + 2] = v;
+    }
   }
 }
 
@@ -1141,18 +1244,127 @@ __global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce(SweepArgs A, double*
   }
 }
 
+// The negative binomial's reduce (k_sweep_reduce<STK_NEGBIN>'s place): the chunk sums as above, then
+// the family's finish.  grid (nshards*C, ceil((d + 1)/64) + 1): blocks y < gridDim.y - 1 sum the
+// gradient columns 0 .. d (alpha, beta) and add the normal priors; the last block is the chain's
+// scalar block.  Its lanes 0, 1, 2 sum columns 0 (d alpha of the likelihood), d + 1 (sum of y eta -
+// (y + phi) sp) and d + 2 (sum of sp) in the same chunk order; all 512 threads share the shard's
+// count table (entry e to thread e % 512, summed per thread, per 8 threads, then in order: a fixed
+// order), so the phi-only terms cost one pass over the distinct counts, never over the rows; thread 0
+// finishes
+//   lp      = S_lik + A1 + priors + v                                   (Jacobian of phi = e^v)
+//   d lp/dv = A2 - d alpha_lik - phi S_sp + (a - 1) - b phi + 1
+// with phi ~ gamma(a, b) adding (a - 1) v - b phi to lp.  phi = 0 or inf: lp and d lp/dv are NaN.
+#if defined(STK_SWEEP_NEGBIN_TU) || !defined(STK_POISSON_OWN_TU)
+constexpr int RDN_W = 8;   // 512 threads: the table terms' log / log1p want more registers than 16 waves leave
+__global__ __launch_bounds__(64 * RDN_W) void k_sweep_reduce_nb(SweepArgs A, const NbShardDev* nbs, double* lp_out,
+                                                               double* g_out, int C) {
+  const int gidl = blockIdx.x;
+  const int shard = A.shard0 + gidl / C, c = gidl % C;
+  if (A.req_step && A.req_step[shard] != A.step_id - 1) return;
+  const ShardDev sh = A.shards[shard];
+  const int d = sh.d;
+  const bool scalar = blockIdx.y == gridDim.y - 1;
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  // column of this lane: a gradient column, or one of the scalar block's three (-1: none)
+  const int o = scalar ? (l == 0 ? 0 : l == 1 ? d + 1 : l == 2 ? d + 2 : -1) : ((int)blockIdx.y * 64 + l <= d ? (int)blockIdx.y * 64 + l : -1);
+  __shared__ double part[RDN_W][64];
+  __shared__ double ta[2][64 * RDN_W];
+  double v = 0.0;
+  if (o >= 0) {
+    const int per = (A.G + RDN_W - 1) / RDN_W;
+    const int k0 = w * per, k1 = min(A.G, k0 + per);
+    const double* src = A.partial + ((size_t)shard * A.Gs * C + c) * A.PW + o;
+    const size_t stride = (size_t)C * A.PW;
+    int k = k0;
+    for (; k + 8 <= k1; k += 8) {
+      double a[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) a[i] = src[(size_t)(k + i) * stride];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v += a[i];
+    }
+    for (; k < k1; ++k) v += src[(size_t)k * stride];
+  }
+  part[w][l] = v;
+  const size_t gid = chain_row(A, shard, c);
+  double* g = g_out + gid * A.Dp;
+  const double* qc = A.q + gid * A.Dp;
+  if (!scalar) {
+    __syncthreads();
+    if (w != 0 || o < 0) return;
+    double t = part[0][l];
+#pragma unroll
+    for (int i = 1; i < RDN_W; ++i) t += part[i][l];
+    g[o] = t - (o == 0 ? sh.pa : sh.pb) * qc[o];       // flat: the precision is 0 (a non-finite q is NaN either way)
+    return;
+  }
+  const NbShardDev nb = nbs[shard];
+  const double vq = qc[d + 1], phi = exp(vq);
+  double a1 = 0.0, a2 = 0.0;
+  for (int e = threadIdx.x; e < nb.ncap + nb.nbig; e += 64 * RDN_W) {
+    double t1, t2;
+    nb_entry_term(nb.tab, nb.ncap, e, phi, vq, &t1, &t2);
+    a1 += t1;
+    a2 += t2;
+  }
+  ta[0][threadIdx.x] = a1;
+  ta[1][threadIdx.x] = a2;
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    a1 = a2 = 0.0;
+    for (int i = 0; i < RDN_W; ++i) {
+      a1 += ta[0][threadIdx.x * RDN_W + i];
+      a2 += ta[1][threadIdx.x * RDN_W + i];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    ta[0][threadIdx.x] = a1;
+    ta[1][threadIdx.x] = a2;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  a1 = a2 = 0.0;
+#pragma unroll 4   // (fully unrolled, the 128 reads are hoisted and spill)
+  for (int i = 0; i < 64; ++i) {
+    a1 += ta[0][i];
+    a2 += ta[1][i];
+  }
+  double t[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    t[j] = part[0][j];
+    for (int i = 1; i < RDN_W; ++i) t[j] += part[i][j];
+  }
+  double prior_lp = 0.0;
+  if (sh.pa != 0.0 || sh.pb != 0.0) {
+    double sb = 0.0;
+    for (int j = 1; j <= d; ++j) sb = fma(qc[j], qc[j], sb);
+    prior_lp = -0.5 * (sh.pa * qc[0] * qc[0] + sh.pb * sb);
+  }
+  const bool ok = phi > 0.0 && phi < __builtin_inf();
+  const double nan = __builtin_nan("");
+  const double lp = ((t[1] + a1) + prior_lp) + (nb.pr_a1 * vq - nb.pr_b * phi) + vq;
+  const double gv = ((a2 - t[0]) - phi * t[2]) + (nb.pr_a1 - nb.pr_b * phi) + 1.0;
+  lp_out[gid] = ok ? lp : nan;
+  g[d + 1] = ok ? gv : nan;
+}
+#endif
+
 }  // namespace stk
 
 #include "launchers.h"
 using namespace stk;
 
+// (The negative binomial's follow the same rule in sweep_nb.hip, with STK_SWEEP_NEGBIN_TU.)
 // In the library (the Makefile's -DSTK_POISSON_OWN_TU) the Poisson instantiations of every kernel
 // above live in their own translation unit, sweep_pois.hip (this file with STK_SWEEP_POISSON_TU: the
 // launch templates below and the three stk_launch_*_poisson entry points), so this file's code
 // object holds the logistic and linear kernels it always did.  Built on its own, without either
 // macro -- the stand-alone tools under tools/ include this file as one translation unit -- it
 // defines the three entry points itself and links as before.
-#ifndef STK_SWEEP_POISSON_TU
+#ifndef STK_SWEEP_FAMILY_TU
 // The single-launch chain counts a sweep covers at d covariates (the batch sizes of the sampler).
 bool stk_sweep_supported(int C, int d) {
   if (C == G5_C) return d >= 1 && d <= 4096;
@@ -1268,13 +1480,13 @@ SweepWs stk_sweep_ws(void* base, const SweepLaunch& at_nmax, int nshards) {
   return w;
 }
 
-static SweepArgs sweep_args(const SweepLaunch& p, int shard0, const SweepCall& c, int LD) {
-  SweepArgs A{c.shards, c.q, c.partial, c.req_step, c.step_id, p.C, c.Dp, p.G, LD, p.d + 2, shard0, c.Gs, c.ran};
+static SweepArgs sweep_args(int family, const SweepLaunch& p, int shard0, const SweepCall& c, int LD) {
+  SweepArgs A{c.shards, c.q, c.partial, c.req_step, c.step_id, p.C, c.Dp, p.G, LD, sweep_pw(family, p.d), shard0, c.Gs, c.ran};
   A.Ct = c.Ct;
   A.c0 = c.c0;
   return A;
 }
-#endif  // STK_SWEEP_POISSON_TU
+#endif  // STK_SWEEP_FAMILY_TU
 
 template <int FAM, int C, int T, int JPT>
 static hipError_t pick_vec(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
@@ -1356,12 +1568,26 @@ hipError_t stk_launch_sweep_reduce_poisson(const SweepArgs& A, int nblocks_x, in
   return launch_reduce<STK_POISSON>(A, dim3(nblocks_x, nblocks_y), lp_out, g_out, C, st);
 }
 #endif
-#ifndef STK_SWEEP_POISSON_TU
+#if defined(STK_SWEEP_NEGBIN_TU) || !defined(STK_POISSON_OWN_TU)
+hipError_t stk_launch_sweep_negbin(const SweepLaunch& p, const SweepArgs& A, int nblocks, hipStream_t st) {
+  return pick_c<STK_NEGBIN>(p, A, nblocks, st);
+}
+hipError_t stk_launch_gemm_fwd_negbin(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  return launch_gemm_fwd<STK_NEGBIN>(A, d, nblocks, lds, st);
+}
+hipError_t stk_launch_sweep_reduce_negbin(const SweepArgs& A, const NbShardDev* nb, int nchains, int d, double* lp_out,
+                                          double* g_out, int C, hipStream_t st) {
+  if (!nb) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_sweep_reduce_nb, dim3(nchains, (d + 1 + 63) / 64 + 1), dim3(64 * RDN_W), 0, st, A, nb, lp_out, g_out, C);
+  return hipGetLastError();
+}
+#endif
+#ifndef STK_SWEEP_FAMILY_TU
 // Launch the plan's sweep over `nsh` shards starting at shard0 (all of the plan's n) for the batch
 // of p.C chains that starts at chain c.c0 of every shard's c.Ct.
 hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int nsh, const SweepCall& c, hipStream_t st) {
-  if (family != STK_LOGREG && family != STK_LINREG && family != STK_POISSON) return hipErrorInvalidValue;
-  SweepArgs A = sweep_args(p, shard0, c, stk_sweep_args_ld(p));
+  if (family != STK_LOGREG && family != STK_LINREG && family != STK_POISSON && family != STK_NEGBIN) return hipErrorInvalidValue;
+  SweepArgs A = sweep_args(family, p, shard0, c, stk_sweep_args_ld(p));
   const int nblocks = nsh * p.G, d = p.d;
   if (p.kind == SWEEP_GEMM64) {
     if (!c.ws || !c.ws->qT || !c.ws->R || c.ws->Rrows < p.Rrows) return hipErrorInvalidValue;
@@ -1372,6 +1598,7 @@ hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int ns
     hipLaunchKernelGGL(k_qt_swizzle, dim3((g5_kp(d) * G5_C + 255) / 256, nsh), dim3(256), 0, st, A, d);
     const hipError_t ef = family == STK_LOGREG   ? launch_gemm_fwd<STK_LOGREG>(A, d, nblocks, p.lds, st)
                           : family == STK_LINREG ? launch_gemm_fwd<STK_LINREG>(A, d, nblocks, p.lds, st)
+                          : family == STK_NEGBIN ? stk_launch_gemm_fwd_negbin(A, d, nblocks, p.lds, st)
                                                  : stk_launch_gemm_fwd_poisson(A, d, nblocks, p.lds, st);
     if (ef != hipSuccess) return ef;
     auto kb = bjb == 64 ? k_gemm_bwd<64> : bjb == 128 ? k_gemm_bwd<128> : k_gemm_bwd<256>;
@@ -1381,17 +1608,19 @@ hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int ns
   }
   if (family == STK_LOGREG) return pick_c<STK_LOGREG>(p, A, nblocks, st);
   if (family == STK_LINREG) return pick_c<STK_LINREG>(p, A, nblocks, st);
+  if (family == STK_NEGBIN) return stk_launch_sweep_negbin(p, A, nblocks, st);
   return stk_launch_sweep_poisson(p, A, nblocks, st);
 }
 
 hipError_t stk_launch_sweep_reduce(int family, const SweepLaunch& p, int shard0, int nsh, const SweepCall& c,
                                    double* lp_out, double* g_out, hipStream_t st) {
-  SweepArgs A = sweep_args(p, shard0, c, 0);
+  SweepArgs A = sweep_args(family, p, shard0, c, 0);
   A.ran = nullptr;
   dim3 grid(nsh * p.C, (p.d + 2 + 63) / 64);
   if (family == STK_LOGREG) return launch_reduce<STK_LOGREG>(A, grid, lp_out, g_out, p.C, st);
   if (family == STK_LINREG) return launch_reduce<STK_LINREG>(A, grid, lp_out, g_out, p.C, st);
   if (family == STK_POISSON) return stk_launch_sweep_reduce_poisson(A, grid.x, grid.y, lp_out, g_out, p.C, st);
+  if (family == STK_NEGBIN) return stk_launch_sweep_reduce_negbin(A, c.nb, nsh * p.C, p.d, lp_out, g_out, p.C, st);
   return hipErrorInvalidValue;
 }
-#endif  // STK_SWEEP_POISSON_TU
+#endif  // STK_SWEEP_FAMILY_TU

@@ -34,6 +34,12 @@
 #include <math.h>
 #include <algorithm>
 
+// A family's own translation unit (sweep16_pois.hip, sweep16_nb.hip) holds that family's instantiations and
+// launcher only.
+#if defined(STK_SWEEP16_POISSON_TU) || defined(STK_SWEEP16_NEGBIN_TU)
+#define STK_SWEEP16_FAMILY_TU 1
+#endif
+
 namespace stk {
 
 // exp table, logistic residual v4 (logit_resid4): sweep_common.h (shared with the 64-chain pass F)
@@ -57,14 +63,15 @@ __host__ __device__ constexpr S16Geom s16_geom(int KF) {
 // (profiles/r04q_*, r04s_*).
 // Poisson keeps the logistic rule: its residual is lighter (KF = 27: 248 VGPRs against 256), but
 // beta and the operands are the same 4 JTM + KF doubles.
-__host__ __device__ constexpr bool s16_pre(int FAM, int KF) { return FAM == STK_LINREG || KF <= 27; }
+// The negative binomial's residual is the heaviest (a log1p per element, phi beside v): KF <= 25.
+__host__ __device__ constexpr bool s16_pre(int FAM, int KF) { return FAM == STK_LINREG || KF <= (FAM == STK_NEGBIN ? 25 : 27); }
 constexpr int S16_FLUSH = 64;                   // sub-tiles between log1p flushes (4 elements each)
 
 template <int FAM, int KF, bool PRE = s16_pre(FAM, KF), int NACC = 2>
 __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   constexpr S16Geom g = s16_geom(KF);
   constexpr int C = SM_C, NW = SM_W, JTM = g.JTM;
-  constexpr bool LOGI = FAM == STK_LOGREG, POIS = FAM == STK_POISSON;
+  constexpr bool LOGI = FAM == STK_LOGREG, NB = FAM == STK_NEGBIN, POIS = FAM == STK_POISSON || NB;   // POIS: whole int32 counts
   static_assert(LOGI || POIS || FAM == STK_LINREG, "k_sweep16: unknown family");
   const int shard = A.shard0 + blockIdx.x / A.G;
   const int chunk = blockIdx.x % A.G;
@@ -96,7 +103,10 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
     bf[s] = col < d ? qs[(size_t)lr * A.Dp + 1 + col] : 0.0;
   }
   const double alpha = qs[(size_t)lr * A.Dp];
-  const double inv_s = FAM == STK_LINREG ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : 0.0;
+  // linear: 1 / sigma; negative binomial: v = log phi itself, with phi beside it (a lane is one chain)
+  const double inv_s = FAM == STK_LINREG ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
+  double nbphi = 0.0;
+  if constexpr (NB) nbphi = exp(inv_s);
   __syncthreads();
   __builtin_amdgcn_s_waitcnt(0xF70);
 
@@ -202,6 +212,9 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
       for (int i = 0; i < 4; ++i) {
         if constexpr (LOGI) {
           de[i] = logit_resid4(eta4[i], ym[i], tab, lm, sp);
+        } else if constexpr (NB) {
+          de[i] = negbin_resid(eta4[i], (int32_t)ym[i], inv_s, nbphi, tab, lm, sp);
+          __builtin_amdgcn_sched_barrier(0);   // one element's temporaries at a time: interleaved, the four spill
         } else if constexpr (POIS) {
           de[i] = pois_resid(eta4[i], (int32_t)ym[i], tab, lm);
         } else {
@@ -218,6 +231,9 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
         double lm2 = lm, sp2 = sp, dv;
         if constexpr (LOGI) {
           dv = logit_resid4(eta4[i], ym[i], tab, lm2, sp2);
+        } else if constexpr (NB) {
+          dv = negbin_resid(eta4[i], (int32_t)ym[i], inv_s, nbphi, tab, lm2, sp2);
+          __builtin_amdgcn_sched_barrier(0);
         } else if constexpr (POIS) {
           dv = pois_resid(eta4[i], (int32_t)ym[i], tab, lm2);
         } else {
@@ -318,6 +334,17 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
       for (int h = 0; h < 4; ++h) v += red2[(size_t)(ww * 64 + h * 16 + c) * 2 + kind];
     out[(size_t)c * A.PW + (kind == 0 ? d + 1 : 0)] = v;
   }
+  if constexpr (NB) {   // the third scalar sum (sp holds sum sp(t)), column d + 2, through the same area
+    __syncthreads();
+    red2[(size_t)tid * 2] = sp;
+    __syncthreads();
+    if (tid < C) {
+      double v = 0.0;
+      for (int ww = 0; ww < NW; ++ww)
+        for (int h = 0; h < 4; ++h) v += red2[(size_t)(ww * 64 + h * 16 + tid) * 2];
+      out[(size_t)tid * A.PW + d + 2] = v;
+    }
+  }
 }
 
 }  // namespace stk
@@ -325,7 +352,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
 #include "launchers.h"
 using namespace stk;
 
-#ifndef STK_SWEEP16_POISSON_TU
+#ifndef STK_SWEEP16_FAMILY_TU
 // LDS bytes of k_sweep16 at d (the main loop's slots + table + remainder scratch, or the block
 // reduction's area, whichever is larger).
 size_t stk_sweep16_lds_bytes(int family, int d) {
@@ -367,13 +394,19 @@ hipError_t stk_launch_sweep16_poisson(const SweepArgs& A, int d, int nblocks, si
   return launch16<STK_POISSON>(A, d, nblocks, lds, st);
 }
 #endif
-#ifndef STK_SWEEP16_POISSON_TU
+#if defined(STK_SWEEP16_NEGBIN_TU) || !defined(STK_POISSON_OWN_TU)   // sweep16_nb.hip, by the same rule
+hipError_t stk_launch_sweep16_negbin(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  return launch16<STK_NEGBIN>(A, d, nblocks, lds, st);
+}
+#endif
+#ifndef STK_SWEEP16_FAMILY_TU
 bool stk_sweep16_supported(int d) { return d >= 1 && d <= 128; }
 
 hipError_t stk_launch_sweep16(int family, const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
   if (family == STK_LOGREG) return launch16<STK_LOGREG>(A, d, nblocks, lds, st);
   if (family == STK_LINREG) return launch16<STK_LINREG>(A, d, nblocks, lds, st);
   if (family == STK_POISSON) return stk_launch_sweep16_poisson(A, d, nblocks, lds, st);
+  if (family == STK_NEGBIN) return stk_launch_sweep16_negbin(A, d, nblocks, lds, st);
   return hipErrorInvalidValue;
 }
 #endif

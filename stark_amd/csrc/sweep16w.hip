@@ -32,6 +32,12 @@
 #include <math.h>
 #include <algorithm>
 
+// A family's own translation unit (sweep16w_pois.hip, sweep16w_nb.hip) holds that family's instantiations and
+// launcher only.
+#if defined(STK_SWEEP16W_POISSON_TU) || defined(STK_SWEEP16W_NEGBIN_TU)
+#define STK_SWEEP16W_FAMILY_TU 1
+#endif
+
 namespace stk {
 
 constexpr int SW_FLUSH = 32;    // sub-tiles between log1p flushes: 128 factors per lane, 1 + sp < 2^128
@@ -58,7 +64,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   constexpr int RSB = sw_row_bytes(DW), SLOTB = sw_slot_bytes(DW);
   constexpr int PPR = DW / 2 + 1;                   // 16-B pieces per padded row
   constexpr int NI = (SM_R * PPR + 63) / 64;        // DMA instructions per slot; the last one has 16 lanes
-  constexpr bool LOGI = FAM == STK_LOGREG, POIS = FAM == STK_POISSON;
+  constexpr bool LOGI = FAM == STK_LOGREG, NB = FAM == STK_NEGBIN, POIS = FAM == STK_POISSON || NB;   // POIS: whole int32 counts
   static_assert(LOGI || POIS || FAM == STK_LINREG, "k_sweep16w: unknown family");
   constexpr int YB = (LOGI || POIS) ? 4 : 8;        // int32 y (logistic, poisson) or double y
   static_assert(KF % 4 == 0 && DW <= 128 && (SM_R * PPR) % 64 == 16, "slab geometry");
@@ -93,7 +99,10 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
     bf[s] = col < d ? qs[(size_t)lr * A.Dp + 1 + col] : 0.0;
   }
   const double alpha = w == 0 ? qs[(size_t)lr * A.Dp] : 0.0;   // wave 0's partial starts at alpha
-  const double inv_s = FAM == STK_LINREG ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : 0.0;
+  // linear: 1 / sigma; negative binomial: v = log phi itself, with phi beside it (a lane is one chain)
+  const double inv_s = FAM == STK_LINREG ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
+  double nbphi = 0.0;
+  if constexpr (NB) nbphi = exp(inv_s);
   __syncthreads();
   __builtin_amdgcn_s_waitcnt(0xF70);
 
@@ -103,17 +112,25 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   // piece p = 64 j + lane of the slot image is piece p % PPR of row p / PPR; the pad piece and the
   // pieces past column d - 1 repeat the row's last valid piece (finite data under a zero beta)
   const int pmax = std::min(DW / 2 - 1, (dwv + 1) / 2 - 1);
-  int voff[NI];
+  // LEAN (the negative binomial at the widest slab, whose residual leaves no room for them): the NI offsets
+  // are recomputed at every issue instead of held in registers across the loop
+  constexpr bool LEAN = NB && KF == 32;
+  auto voff_at = [&](int j) {
+    int ln = lane;
+    if constexpr (LEAN) asm volatile("" : "+v"(ln));   // opaque: else the offsets are hoisted out of the loop again
+    const int p = j * 64 + ln, row = std::min(p / PPR, SM_R - 1), pr = std::min(p % PPR, pmax);
+    return row * d * 8 + pr * 16;
+  };
+  int voff[LEAN ? 1 : NI];
+  if constexpr (!LEAN) {
 #pragma unroll
-  for (int j = 0; j < NI; ++j) {
-    const int p = j * 64 + lane, row = std::min(p / PPR, SM_R - 1), pr = std::min(p % PPR, pmax);
-    voff[j] = row * d * 8 + pr * 16;
+    for (int j = 0; j < NI; ++j) voff[j] = voff_at(j);
   }
   auto issue = [&](int u) {           // 1 KiB per DMA instruction
     const int soff = u * SM_R * d * 8 + j0 * 8;
 #pragma unroll
-    for (int j = 0; j < NI - 1; ++j) sw_dma16(xr, slot + j * 1024, voff[j], soff);
-    if (lane < 16) sw_dma16(xr, slot + (NI - 1) * 1024, voff[NI - 1], soff);
+    for (int j = 0; j < NI - 1; ++j) sw_dma16(xr, slot + j * 1024, LEAN ? voff_at(j) : voff[j], soff);
+    if (lane < 16) sw_dma16(xr, slot + (NI - 1) * 1024, LEAN ? voff_at(NI - 1) : voff[NI - 1], soff);
     if (w == 0 && lane < SM_R * YB / 4) sw_dma4(yr, ybuf, lane * 4, u * SM_R * YB);
   };
 
@@ -166,6 +183,9 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
       for (int i = 0; i < 4; ++i) {
         if constexpr (LOGI) {
           de[i] = logit_resid4(eta4[i], ym[i], tab, lm, sp);
+        } else if constexpr (NB) {
+          de[i] = negbin_resid(eta4[i], (int32_t)ym[i], inv_s, nbphi, tab, lm, sp);
+          __builtin_amdgcn_sched_barrier(0);   // one element's temporaries at a time: interleaved, the four spill
         } else if constexpr (POIS) {
           de[i] = pois_resid(eta4[i], (int32_t)ym[i], tab, lm);
         } else {
@@ -182,6 +202,9 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
         double lm2 = lm, sp2 = sp, dv;
         if constexpr (LOGI) {
           dv = logit_resid4(eta4[i], ym[i], tab, lm2, sp2);
+        } else if constexpr (NB) {
+          dv = negbin_resid(eta4[i], (int32_t)ym[i], inv_s, nbphi, tab, lm2, sp2);
+          __builtin_amdgcn_sched_barrier(0);
         } else if constexpr (POIS) {
           dv = pois_resid(eta4[i], (int32_t)ym[i], tab, lm2);
         } else {
@@ -241,6 +264,11 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
       out[d + 1] = lpa;
       out[0] = ga;
     }
+    if constexpr (NB) {   // the third scalar sum (sp holds sum sp(t)), column d + 2, joined the same way
+      sp += __shfl_xor(sp, 16);
+      sp += __shfl_xor(sp, 32);
+      if (lh == 0) out[d + 2] = sp;
+    }
   }
 }
 
@@ -249,7 +277,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
 #include "launchers.h"
 using namespace stk;
 
-#ifndef STK_SWEEP16W_POISSON_TU
+#ifndef STK_SWEEP16W_FAMILY_TU
 bool stk_sweep16w_supported(int d) { return d > 128 && d <= 128 * SW_MAXW; }
 int stk_sweep16w_waves(int d) { return sw_waves(d); }
 int stk_sweep16w_chunks(int64_t n) {                  // >= SW_TILES tiles of 64 rows per chunk
@@ -291,13 +319,19 @@ hipError_t stk_launch_sweep16w_poisson(const SweepArgs& A, int d, int nblocks, s
   return launch16w<STK_POISSON>(A, d, nblocks, lds, st);   // the caller (stk_launch_sweep16w) checked the shape
 }
 #endif
-#ifndef STK_SWEEP16W_POISSON_TU
+#if defined(STK_SWEEP16W_NEGBIN_TU) || !defined(STK_POISSON_OWN_TU)   // sweep16w_nb.hip, by the same rule
+hipError_t stk_launch_sweep16w_negbin(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  return launch16w<STK_NEGBIN>(A, d, nblocks, lds, st);
+}
+#endif
+#ifndef STK_SWEEP16W_FAMILY_TU
 hipError_t stk_launch_sweep16w(int family, const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
   if (!stk_sweep16w_supported(d) || A.LD != sw_waves(d) || lds < stk_sweep16w_lds_bytes(family, d) || lds > BIG_LDS_BYTES)
     return hipErrorInvalidValue;
   if (family == STK_LOGREG) return launch16w<STK_LOGREG>(A, d, nblocks, lds, st);
   if (family == STK_LINREG) return launch16w<STK_LINREG>(A, d, nblocks, lds, st);
   if (family == STK_POISSON) return stk_launch_sweep16w_poisson(A, d, nblocks, lds, st);
+  if (family == STK_NEGBIN) return stk_launch_sweep16w_negbin(A, d, nblocks, lds, st);
   return hipErrorInvalidValue;
 }
 #endif

@@ -3,6 +3,8 @@
 // the measurement tools in tools/.
 #pragma once
 #include "common.h"
+#include "predictive_math.h"
+#include "negbin_math.h"
 
 namespace stk {
 
@@ -168,6 +170,61 @@ __device__ __forceinline__ double pois_resid(double eta, int32_t y, const double
   const double mu = __builtin_amdgcn_ldexp(tab[ni & (EX_TAB - 1)] * p, ni >> 10);
   lm = fma(yd, eta, lm - mu);
   return yd - mu;
+}
+
+// Negative-binomial residual: Stan's neg_binomial_2_log term in the form of include/stark_hip.h
+// (STK_NEGBIN) and its derivative for one (row, chain), t = eta - v, v = log phi:
+//   lt = y eta - (y + phi) sp(t),   dv = y - (y + phi) sigma(t)     (returned)
+//   lm <- lm + lt,  ss <- ss + sp(t)     (ss: the unweighted sum the v gradient needs)
+// The phi-only terms (sum_j log1p(j / phi), the digamma difference) are not here: k_sweep_reduce adds
+// them once per (shard, chain) from the shard's count table (negbin_math.h).
+// From e = exp(-|t|) by the table exp of logit_resid4 (|t| clamped to 800, where e is 0):
+//   sp(t) = max(t, 0) + log1p(e)     max(t, 0) as (t + |t|) / 2: a NaN t stays NaN, t = +inf gives +inf
+//   lt = y eta - (y + phi) log1p(e) (t < 0),  y v - phi t - (y + phi) log1p(e) (t >= 0)
+// -- for t >= 0 the product (y + phi) t is multiplied out and y eta - y t = y v taken exactly: at |eta| ~ 1e150 and a
+// count of 2^31 the two products would cancel seven digits of lp.  The y v this leaves cancels against the table's
+// sum_j T_j log1p(j / phi) only where |v| is large, and then to within eps |v| of lp.
+//   dv = (y e - phi) / (1 + e) (t >= 0), (y - phi e) / (1 + e) (t < 0)     v_rcp_f64 + two Newton steps
+// -- y - (y + phi) sigma(t) with sigma(t) = 1 / (1 + e) or e / (1 + e) multiplied out, so that a count of 2^31
+// does not turn the last ulp of sigma into 2e-7 of d eta: what cancels is y e against phi, both to an ulp.
+// log1p(e) by pd_log1p01 (predictive_math.h: e in [0, 1], relative accuracy kept as e -> 0, so
+// (y + phi) sp(t) -> mu (1 + y / phi) at large phi without a switch to Poisson).  The weight y + phi
+// differs per row, so logit_resid4's running product cannot carry the weighted sum; with log1p(e)
+// at hand the unweighted sum costs one add.  phi = inf (t = -inf) gives sp = NaN; phi = 0 leaves the
+// sums finite and the reduce makes lp NaN.  About 74 vector instructions per element over the linear kernel's
+// by the ISA count of k_sweep16<FAM, 25>, against 64 for logistic counted the same way.
+__device__ __forceinline__ double negbin_resid(double eta, int32_t y, double v, double phi, const double* tab, double& lm,
+                                               double& ss) {
+  constexpr double MAGIC = 6755399441055744.0;            // 1.5 * 2^52
+  constexpr double INV_L = 1477.3197218702985;            // 1024 / ln 2
+  constexpr double L = 0.0006769015435155716;             // ln 2 / 1024
+  constexpr double C2 = 0.5000000039583942, C3 = 0.16666666713444417;   // e^r on |r| <= ln2/2048 (fit)
+  const double yd = (double)y;                            // v_cvt_f64_i32: exact for every int32
+  const double t = eta - v;
+  const double a = fmin_abs(t, 800.0);                    // NaN -> 800 (the NaN stays in sp through t)
+  const double sn = fma(-a, INV_L, MAGIC);
+  const int ni = (int)(uint32_t)__builtin_bit_cast(uint64_t, sn);
+  const double n = sn - MAGIC;
+  const double r = fma(-n, L, -a);
+  const double p = fma(fma(fma(C3, r, C2), r, 1.0), r, 1.0);
+  const double e = __builtin_amdgcn_ldexp(tab[ni & (EX_TAB - 1)] * p, ni >> 10);
+  const uint32_t tneg = (uint32_t)((int32_t)(__builtin_bit_cast(uint64_t, t) >> 32) >> 31);   // ~0u when t < 0
+  const double l1 = pd_log1p01(e);
+  lm = fma(-(yd + phi), l1, lm) + blend(tneg, yd * eta, fma(yd, v, -phi * t));
+  ss += fma(0.5, t, 0.5 * fabs(t)) + l1;
+  const double num = blend(tneg, fma(-phi, e, yd), fma(yd, e, -phi));
+  return num * pd_rcp(1.0 + e);
+}
+
+// The same terms with libm's exp and log1p, for the VALU sweeps (k_sweep, k_sweep2, k_sweep3: C <= 8),
+// which keep no exp table.
+__device__ __forceinline__ double negbin_resid_libm(double eta, double yd, double v, double phi, double& lm, double& ss) {
+  const double t = eta - v;
+  const double e = exp(-fabs(t));
+  const double l1 = log1p(e);
+  lm = fma(-(yd + phi), l1, lm) + (t < 0.0 ? yd * eta : fma(yd, v, -phi * t));
+  ss += fma(0.5, t, 0.5 * fabs(t)) + l1;
+  return (t < 0.0 ? fma(-phi, e, yd) : fma(yd, e, -phi)) / (1.0 + e);
 }
 
 }  // namespace stk

@@ -14,10 +14,11 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_POISSON, STK_SCHOOLS, Config, RunInfo, Shard,
+from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_NEGBIN, STK_POISSON, STK_SCHOOLS, Config, RunInfo, Shard,
                    StarkHipError, check)
 
-FAMILIES = {"schools": STK_SCHOOLS, "linear": STK_LINREG, "logistic": STK_LOGREG, "poisson": STK_POISSON}
+FAMILIES = {"schools": STK_SCHOOLS, "linear": STK_LINREG, "logistic": STK_LOGREG, "poisson": STK_POISSON,
+            "neg_binomial": STK_NEGBIN}
 
 # Live library handles, closed in dependency order (samplers, models, contexts) before the
 # HIP runtime's own exit handlers run; after that every close() is a no-op.
@@ -215,10 +216,11 @@ def _host_shard(family, sh):
         if np.any((y != 0) & (y != 1)):
             raise ValueError("bernoulli_logit: y must be 0 or 1")
         shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, None, y.ctypes.data, None)
-    elif family == STK_POISSON:
+    elif family in (STK_POISSON, STK_NEGBIN):
         y = np.asarray(sh["y"])
         if y.dtype.kind not in "iuf" or not np.all(y == np.round(y)) or np.any(y < 0) or np.any(y > np.iinfo(np.int32).max):
-            raise ValueError("poisson_log: y must hold integers in 0 .. 2^31 - 1")
+            raise ValueError(("poisson_log" if family == STK_POISSON else "neg_binomial_2_log") +
+                             ": y must hold integers in 0 .. 2^31 - 1")
         y = np.ascontiguousarray(y, np.int32)
         shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, None, y.ctypes.data, None)
     else:
@@ -374,8 +376,8 @@ class Model:
             y = np.empty(n)
             check(lib.stk_model_copy_data(self._h, shard, None, y.ctypes.data, None))
             return {"y": y}
-        yint = self.family in (STK_LOGREG, STK_POISSON)
-        d = D - (1 if yint else 2)
+        yint = self.family in (STK_LOGREG, STK_POISSON, STK_NEGBIN)
+        d = D - (2 if self.family in (STK_LINREG, STK_NEGBIN) else 1)
         x = np.empty((n, d))
         if yint:
             y = np.empty(n, np.int32)
@@ -562,10 +564,15 @@ class Model:
             out.append(np.ascontiguousarray(yr.T))
         return tuple(out)
 
-    def set_prior(self, alpha=None, beta=None):
-        """normal(0, s) priors on alpha and beta (regressions); None or 0: flat."""
+    def set_prior(self, alpha=None, beta=None, phi=None):
+        """normal(0, s) priors on alpha and beta (regressions); None or 0: flat.  phi=(shape, rate): the negative
+        binomial's phi ~ gamma(shape, rate) (None: flat; exponential(r) is (1, r)); the library refuses it for
+        every other family."""
         check(_lib.load().stk_model_set_prior(self._h, float(alpha or 0.0), float(beta or 0.0)))
         self.prior = {"alpha": alpha, "beta": beta}
+        if phi is not None:
+            check(_lib.load().stk_model_set_prior_phi(self._h, float(phi[0]), float(phi[1])))
+            self.prior["phi"] = (float(phi[0]), float(phi[1]))
         return self
 
     def sampler(self, **cfg) -> "Sampler":
@@ -1012,6 +1019,16 @@ def ppc(stats, obs) -> dict:
         out[k] = {"obs": float(To[k]), "rep": Tr[k], "p": float(np.count_nonzero(Tr[k] >= To[k])) / S}
     out["chi2"] = {"obs": ps[:, 6].copy(), "rep": ps[:, 5].copy(), "p": float(np.count_nonzero(ps[:, 5] >= ps[:, 6])) / S}
     return out
+
+
+def negbin_phi_terms(y, phi: float) -> "tuple[float, float]":
+    """The negative binomial's two phi-only sums over the counts y (integers >= 0) at phi > 0, computed on the host
+    by the code the reduce kernel runs (stk_negbin_phi_terms_host): (sum_i sum_{j < y_i} log1p(j / phi),
+    sum_i [psi(y_i + phi) - psi(phi)]).  Needs no device."""
+    y = np.ascontiguousarray(y, np.int32).reshape(-1)
+    out = np.zeros(2)
+    check(_lib.load().stk_negbin_phi_terms_host(y.ctypes.data, int(y.shape[0]), float(phi), out.ctypes.data))
+    return float(out[0]), float(out[1])
 
 
 def boot_poisson_thresholds() -> np.ndarray:

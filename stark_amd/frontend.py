@@ -53,13 +53,21 @@ _NUM = r"([0-9]+(?:\.[0-9]*)?(?:[eE][-+]?[0-9]+)?|\.[0-9]+(?:[eE][-+]?[0-9]+)?)"
 _PRIOR = re.compile(r"(alpha|beta)~normal\(0(?:\.0*)?," + _NUM + r"\)$")
 
 
+# phi ~ gamma(a, b) or phi ~ exponential(r) = gamma(1, r): the negative binomial's only phi priors
+_PRIOR_PHI = re.compile(r"phi~(?:gamma\(" + _NUM + "," + _NUM + r"\)|exponential\(" + _NUM + r"\))$")
+
+
 def _split_priors(stmts):
-    """Separate `alpha ~ normal(0, s)` / `beta ~ normal(0, s)` statements (s > 0) from the rest."""
+    """Separate `alpha ~ normal(0, s)` / `beta ~ normal(0, s)` statements (s > 0) and `phi ~ gamma(a, b)` /
+    `phi ~ exponential(r)` (a, b, r > 0; stored as 'phi': (a, b)) from the rest."""
     priors, rest = {}, []
     for st in stmts:
         m = _PRIOR.match(st)
+        mp = _PRIOR_PHI.match(st)
         if m and float(m.group(2)) > 0 and m.group(1) not in priors:
             priors[m.group(1)] = float(m.group(2))
+        elif mp and "phi" not in priors and all(float(g) > 0 for g in mp.groups() if g is not None):
+            priors["phi"] = (float(mp.group(1)), float(mp.group(2))) if mp.group(1) is not None else (1.0, float(mp.group(3)))
         else:
             rest.append(st)
     return priors, rest
@@ -67,24 +75,28 @@ def _split_priors(stmts):
 
 def program_info(model_code: str):
     """(family, priors) of a supported Stan program; priors = {'alpha': s, 'beta': s} for the
-    regressions' optional `alpha ~ normal(0, s)` / `beta ~ normal(0, s)` statements (absent: flat)."""
+    regressions' optional `alpha ~ normal(0, s)` / `beta ~ normal(0, s)` statements (absent: flat), and
+    'phi': (a, b) for the negative binomial's `phi ~ gamma(a, b)` / `phi ~ exponential(b)`."""
     code = _strip(model_code)
     b = _blocks(code)
     priors, rest = _split_priors(_stmts(b.get("model", "")))
     fam = _recognise_blocks(b, sorted(rest))
     if fam == "schools" and priors:
         fam = None
+    if fam != "neg_binomial" and "phi" in priors:   # a phi prior belongs to the negative binomial alone
+        fam = None
     if fam is None:
         raise NotImplementedError(
-            "stark_amd runs a fixed set of model families on the GPU (8 schools, Bayesian linear, logistic and "
-            "Poisson (poisson_log) regression with flat or normal(0, s) priors on alpha and beta; see "
-            "stark_amd/models/*.stan).  This Stan program is not one of them; pass "
-            "family='schools'|'linear'|'logistic'|'poisson' if it is an equivalent program.")
+            "stark_amd runs a fixed set of model families on the GPU (8 schools, Bayesian linear, logistic, "
+            "Poisson (poisson_log) and negative-binomial (neg_binomial_2_log) regression with flat or normal(0, s) "
+            "priors on alpha and beta, and for the negative binomial a flat, gamma(a, b) or exponential(r) prior on "
+            "phi; see stark_amd/models/*.stan).  This Stan program is not one of them; pass "
+            "family='schools'|'linear'|'logistic'|'poisson'|'neg_binomial' if it is an equivalent program.")
     return fam, priors
 
 
 def recognise(model_code: str) -> str:
-    """Return 'schools', 'linear', 'logistic' or 'poisson' for a supported Stan program."""
+    """Return 'schools', 'linear', 'logistic', 'poisson' or 'neg_binomial' for a supported Stan program."""
     return program_info(model_code)[0]
 
 
@@ -108,6 +120,12 @@ def _recognise_blocks(b: dict, stm: list):
             # are other programs to this recogniser)
             if not _decl(params, r"sigma") and _decl(b.get("data", ""), r"(int<lower=0>y\[N\]|array\[N\]int<lower=0>y)(;|$)"):
                 return "poisson"
+        if stm in (["y~neg_binomial_2_log(alpha+x*beta,phi)"], ["y~neg_binomial_2_log(x*beta+alpha,phi)"]):
+            # phi is the dispersion itself, real<lower=0> phi (neg_binomial_2(exp(...), phi), neg_binomial_2_log_glm
+            # and a reciprocal dispersion are other programs to this recogniser); counts as for poisson_log
+            if (not _decl(params, r"sigma") and _decl(params, r"(^|;)real<lower=0>phi(;|$)") and not b.get("transformed parameters")
+                    and _decl(b.get("data", ""), r"(int<lower=0>y\[N\]|array\[N\]int<lower=0>y)(;|$)")):
+                return "neg_binomial"
         if stm in (["y~normal(alpha+x*beta,sigma)"], ["y~normal(x*beta+alpha,sigma)"]):
             if _decl(params, r"real<lower=0>sigma"):
                 return "linear"
@@ -116,9 +134,9 @@ def _recognise_blocks(b: dict, stm: list):
 
 def load_program_info(file=None, model_code=None, family=None, priors=None, **_ignored):
     """Mirror of pystan.StanModel(file=..., model_code=...) argument handling -> (family, priors).
-    family= (and priors={'alpha': s, 'beta': s}) override recognition."""
+    family= (and priors={'alpha': s, 'beta': s}, for 'neg_binomial' also 'phi': (shape, rate)) override recognition."""
     if family is not None:
-        if family not in ("schools", "linear", "logistic", "poisson"):
+        if family not in ("schools", "linear", "logistic", "poisson", "neg_binomial"):
             raise ValueError(f"unknown family {family!r}")
         return family, dict(priors or {})
     if model_code is None:
@@ -157,14 +175,15 @@ def pack_data(family: str, data: dict) -> dict:
         if not np.all(yf == np.round(yf)) or np.any((yf != 0) & (yf != 1)):
             raise ValueError("bernoulli_logit data: y must hold the integers 0 and 1")
         return {"x": x, "y": yf.astype(np.int32)}
-    if family == "poisson":
+    if family in ("poisson", "neg_binomial"):
         y = np.asarray(data["y"]).reshape(-1)
         if y.shape[0] != N:
             raise ValueError("y must have N entries")
         # int<lower=0> y[N]: pystan rejects non-integer or negative values; the shard stores int32
         yf = y.astype(np.float64)
         if not np.all(yf == np.round(yf)) or np.any(yf < 0) or np.any(yf > 2147483647):
-            raise ValueError("poisson_log data: y must hold integers >= 0 (and <= 2^31 - 1)")
+            raise ValueError(("poisson_log" if family == "poisson" else "neg_binomial_2_log") +
+                             " data: y must hold integers >= 0 (and <= 2^31 - 1)")
         return {"x": x, "y": yf.astype(np.int32)}
     y = np.asarray(data["y"], np.float64).reshape(-1)
     if y.shape[0] != N:
@@ -182,6 +201,8 @@ def column_names(family: str, data: dict) -> list:
     cols = ["alpha"] + [f"beta[{k}]" for k in range(1, K + 1)]
     if family == "linear":
         cols.append("sigma")
+    if family == "neg_binomial":
+        cols.append("phi")
     return cols + ["lp__"]
 
 

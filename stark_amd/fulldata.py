@@ -13,7 +13,8 @@ without a host sync).  All ranks then run the NUTS step on bitwise-identical inp
 chain states never diverge and no other exchange is needed.
 
 The log density must be a pure sum over rows: the logistic family (flat priors, no Jacobian).
-The Poisson family's is one too, but full-data mode stays logistic-only: it is refused by name.
+The Poisson family's is one too, but full-data mode stays logistic-only: it is refused by name, and so
+is the negative binomial (its log density has a Jacobian and phi-only terms that are not sums over rows).
 """
 from __future__ import annotations
 
@@ -51,7 +52,9 @@ class FullDataSampler:
 
     def __init__(self, model: engine.Model, group=None, force_exchange: bool = False, **cfg):
         if model.family != engine.FAMILIES["logistic"]:
-            raise ValueError("full-data mode needs the logistic family (a log density that is a pure sum over rows)")
+            name = {v: k for k, v in engine.FAMILIES.items()}.get(model.family, model.family)
+            raise ValueError("full-data mode needs the logistic family (a log density that is a pure sum over rows)"
+                             f", not the {name} family")
         if model.nshards != 1:
             raise ValueError("full-data mode: one shard (this rank's rows) per model")
         cfg = dict(cfg)

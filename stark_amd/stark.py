@@ -112,34 +112,51 @@ def _unconstrain(family, data, init_dict):
     v = [float(init_dict.get("alpha", 0.0))] + list(np.asarray(init_dict.get("beta", np.zeros(K)), np.float64).reshape(K))
     if family == "linear":
         v.append(np.log(float(init_dict.get("sigma", 1.0))))
+    if family == "neg_binomial":
+        v.append(np.log(float(init_dict.get("phi", 1.0))))
     return np.asarray(v)
+
+
+NO_ANALYSIS_FAMILY = "neg_binomial"   # samples and combines; the analysis sweeps do not cover it
+
+
+def _refuse_analysis(family, what):
+    """ValueError, before any sampling, where `what` is asked of the negative binomial: the Hessian, log-predictive,
+    PSIS-LOO, per-draw log-density, bootstrap and posterior predictive sweeps cover linear, logistic and poisson."""
+    if family == NO_ANALYSIS_FAMILY:
+        raise ValueError(f"{what} is not available for the neg_binomial family: the analysis sweeps (Hessian, "
+                         "log-predictive, PSIS-LOO, per-draw log density, bootstrap, posterior predictive) cover the "
+                         "linear, logistic and poisson families; sample it with NUTS and combine by consensus or "
+                         "combiner='semiparametric'")
 
 
 def unconstrain_draws(family, samples, n_cols=None):
     """The P x S constrained matrix ``concensusWeight`` returns (rows alpha, beta[1..d], [sigma], lp__)
     as the [S][D] unconstrained draws ``engine.Model.log_predictive`` scores: lp__ is dropped and
-    linear's sigma becomes u = log sigma.  n_cols: the model's covariate count d, when known
+    linear's sigma becomes u = log sigma (the negative binomial's phi, in sigma's row, v = log phi: its draws
+    convert, though no analysis sweep scores them).  n_cols: the model's covariate count d, when known
     (``Stark.waic`` passes it); None takes it from the row count.
     ValueError for 8 schools (no log-predictive sweep), for P != D + 1 -- the draws of a ``pars=``
     selection cannot be scored: every parameter is needed -- and for a sigma <= 0 (names the draw)."""
-    if family not in ("linear", "logistic", "poisson"):
+    if family not in ("linear", "logistic", "poisson", "neg_binomial"):
         raise ValueError(f"draws of the {family} family cannot be scored: the log-predictive sweep covers the "
                          "regression families (linear, logistic, poisson), not 8 schools")
     m = np.asarray(samples, np.float64)
     if m.ndim != 2:
         raise ValueError(f"samples must be the P x S draw matrix, got shape {m.shape}")
-    extra = 2 if family == "linear" else 1              # parameters besides beta
+    scale = {"linear": "sigma", "neg_binomial": "phi"}.get(family)   # the positive parameter after beta, if any
+    extra = 2 if scale else 1                           # parameters besides beta
     d = int(n_cols) if n_cols is not None else m.shape[0] - 1 - extra
     D = d + extra
     if d < 1 or m.shape[0] != D + 1:
         raise ValueError(f"samples has {m.shape[0]} rows, the {family} model with {max(d, 0)} covariates has D + 1 = "
-                         f"{D + 1} (alpha, beta, {'sigma, ' if family == 'linear' else ''}lp__): the draws of a pars= "
+                         f"{D + 1} (alpha, beta, {scale + ', ' if scale else ''}lp__): the draws of a pars= "
                          "selection cannot be scored")
     q = np.ascontiguousarray(m[:D].T)
-    if family == "linear":
+    if scale:
         bad = np.flatnonzero(~(q[:, -1] > 0))
         if bad.size:
-            raise ValueError(f"draw {int(bad[0])}: sigma = {q[bad[0], -1]!r} is not positive")
+            raise ValueError(f"draw {int(bad[0])}: {scale} = {q[bad[0], -1]!r} is not positive")
         q[:, -1] = np.log(q[:, -1])
     return q
 
@@ -499,6 +516,7 @@ class Stark:
             if method == "laplace":
                 if self.family is None:
                     raise RuntimeError("call setStanModel() first")
+                _refuse_analysis(self.family, "method='laplace'")
                 if self.family == "schools":
                     raise ValueError("method='laplace' needs a regression family (linear, logistic, poisson): "
                                      "8 schools has no Hessian or per-draw log-density sweep")
@@ -514,6 +532,7 @@ class Stark:
         if method == "laplace":
             if self.family is None:
                 raise RuntimeError("call setStanModel() first")
+            _refuse_analysis(self.family, "method='laplace'")
             if self.family == "schools":
                 raise ValueError("method='laplace' needs a regression family (linear, logistic, poisson): "
                                  "8 schools has no Hessian or per-draw log-density sweep")
@@ -528,6 +547,7 @@ class Stark:
         if weights == "laplace":
             if self.family is None:
                 raise RuntimeError("call setStanModel() first")
+            _refuse_analysis(self.family, "weights='laplace'")
             if self.family == "schools":
                 raise ValueError("weights='laplace' needs a regression family (linear, logistic, poisson): "
                                  "8 schools has no Hessian sweep")
@@ -562,6 +582,7 @@ class Stark:
         says which draws cannot be scored."""
         if self.family is None:
             raise RuntimeError("call setStanModel() first")
+        _refuse_analysis(self.family, "waic")
         if self.family == "schools":
             unconstrain_draws(self.family, samples)       # raises: names the family
         parts = _rdd.partitions_of(self.rdd)
@@ -599,6 +620,7 @@ class Stark:
         with at most 128 covariates and at most 1024 draws: more columns raise ValueError."""
         if self.family is None:
             raise RuntimeError("call setStanModel() first")
+        _refuse_analysis(self.family, "loo")
         if self.family == "schools":
             unconstrain_draws(self.family, samples)       # raises: names the family
         S = np.asarray(samples).shape[-1] if np.ndim(samples) == 2 else 0
@@ -635,6 +657,7 @@ class Stark:
         with at most 128 covariates: ValueError otherwise, before a model is built."""
         if self.family is None:
             raise RuntimeError("call setStanModel() first")
+        _refuse_analysis(self.family, "ppc")
         if self.family not in ("linear", "logistic", "poisson"):
             raise ValueError(f"no ppc for the {self.family} family: the posterior predictive sweep covers the "
                              "regression families (linear, logistic, poisson), not 8 schools")
@@ -684,6 +707,7 @@ class Stark:
         Regression families with at most 128 covariates: ValueError otherwise, before a model is built."""
         if self.family is None:
             raise RuntimeError("call setStanModel() first")
+        _refuse_analysis(self.family, "bootstrap")
         if self.family not in ("linear", "logistic", "poisson"):
             raise ValueError(f"no bootstrap for the {self.family} family: the weighted bootstrap sweep covers the "
                              "regression families (linear, logistic, poisson), not 8 schools")

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Sweep time per step of the Poisson and the logistic family on the same rows, in one process.
+"""Sweep time per step of the Poisson, the negative-binomial and the logistic family on the same rows, in
+one process.
 
-Both models hold the same X (host rows: the Poisson family has no synthetic generator) and counts
-y ~ Poisson(exp(eta)) / their indicator y > 0, so the two sweeps stream the same n (8d + 4) bytes and
-differ in the residual only.  Per arm a fresh adaptive sampler runs --steps state-machine steps with
+The models hold the same X (host rows: the count families have no synthetic generator) and counts
+y ~ Poisson(exp(eta)) / their indicator y > 0, so the sweeps stream the same n (8d + 4) bytes and
+differ in the residual only (the negative binomial also in its reduce, which adds the count table's terms).  Per arm a fresh adaptive sampler runs --steps state-machine steps with
 HIP events around every step's sweeps (stk_ctx_set_profiling); the figure is sweep_ms / sweeps.  Arms
 alternate, --repeats times.  One JSON line on stdout, the same object to --out.
 """
@@ -37,24 +38,29 @@ for s in range(a.shards):
     pois.append({"x": X, "y": y})
     logi.append({"x": X, "y": (y > 0).astype(np.int32)})
 ctx = engine.Context(0, profiling=True)
-models = {"poisson": engine.Model(ctx, "poisson", pois), "logistic": engine.Model(ctx, "logistic", logi)}
+models = {"poisson": engine.Model(ctx, "poisson", pois), "neg_binomial": engine.Model(ctx, "neg_binomial", pois),
+          "logistic": engine.Model(ctx, "logistic", logi)}
 del pois, logi
 launch = engine.sweep_launch(n, d, a.chains if a.chains in (1, 2, 4, 8, 16, 64) else engine.chain_batches(a.chains, d)[0])
-ms = {"poisson": [], "logistic": []}
+ms = {"poisson": [], "neg_binomial": [], "logistic": []}
 for r in range(a.repeats):
-    for fam in ("poisson", "logistic"):
+    for fam in ("poisson", "neg_binomial", "logistic"):
         s = models[fam].sampler(num_warmup=150, num_samples=105, chains=a.chains, seed=20241 + r,
                                 shard_ids=list(range(a.shards)))
         s.run(255, max_steps=a.steps)
         info = s.info()
         s.close()
         ms[fam].append(info["sweep_ms"] / max(info["sweeps"], 1))
-out = {"what": "sweep time per step (sweep_ms / sweeps, HIP events around every step's sweeps), poisson and "
-               "logistic models on the same X in one process, arms alternating",
+out = {"what": "sweep time per step (sweep_ms / sweeps, HIP events around every step's sweeps), poisson, neg_binomial "
+               "and logistic models on the same X in one process, arms alternating",
        "rows_per_shard": n, "d": d, "shards": a.shards, "chains": a.chains, "steps": a.steps, "sweep": launch,
        "bytes_per_sweep": a.shards * n * (8 * d + 4),
        "poisson_ms": ms["poisson"], "logistic_ms": ms["logistic"],
-       "poisson_over_logistic": [x / y for x, y in zip(ms["poisson"], ms["logistic"])]}
+       "neg_binomial_ms": ms["neg_binomial"],
+       "poisson_over_logistic": [x / y for x, y in zip(ms["poisson"], ms["logistic"])],
+       "neg_binomial_over_logistic": [x / y for x, y in zip(ms["neg_binomial"], ms["logistic"])],
+       "neg_binomial_over_poisson": [x / y for x, y in zip(ms["neg_binomial"], ms["poisson"])],
+       "median_ms": {k: float(np.median(v)) for k, v in ms.items()}}
 line = json.dumps(out)
 if a.out:
     with open(a.out, "w") as f:
