@@ -88,7 +88,7 @@ enum {
 };
 
 /* Model families. */
-enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEGBIN = 5 };
+enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEGBIN = 5, STK_STUDENT = 6 };
 /* STK_POISSON: y ~ poisson_log(alpha + x * beta), the unconstrained parameters (alpha, beta[1..d]) in
  * the logistic layout (D = d + 1, P = d + 2: alpha, beta, lp__).  With eta_i = alpha + x_i . beta and
  * mu_i = exp(eta_i), lp = sum_i (y_i eta_i - mu_i) (+ the normal(0, s) prior terms of
@@ -126,6 +126,28 @@ enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEG
  * work: stk_model_create_synthetic, stk_sampler_set_allreduce and the analysis sweeps
  * (stk_log_density_hessian, stk_log_predictive, stk_loo, stk_log_density_draws,
  * stk_log_density_grad_boot, stk_posterior_predict). */
+/* STK_STUDENT: y ~ student_t(nu, alpha + x * beta, sigma) with nu > 0 a constant of the model
+ * (stk_model_set_student_nu; never a parameter), the unconstrained parameters (alpha, beta[1..d],
+ * s = log sigma) in the linear layout (D = d + 2, P = d + 3: alpha, beta, sigma = e^s, lp__) and the
+ * shard's double y, as linear.  With eta_i = alpha + x_i . beta, z_i = (y_i - eta_i) / sigma and
+ * w_i = z_i^2 / nu, the `~` statement's density on the unconstrained scale is
+ *   lp             = -(nu + 1)/2 sum_i log1p(w_i) - n s + s    (+ the normal(0, scale) priors of stk_model_set_prior)
+ *   d lp / d eta_i = (nu + 1) z_i / (sigma (nu + z_i^2))       -> d alpha = sum_i, d beta = X^T (.)
+ *   d lp / d s     = (nu + 1) sum_i z_i^2 / (nu + z_i^2) - n + 1
+ * (the last s and + 1: the Jacobian of sigma = e^s).  lgamma((nu + 1)/2) - lgamma(nu/2) - log(nu pi)/2 per row
+ * is a constant under `~` with nu as data: Stan drops it and so does the library.  The row term needs a log1p
+ * over the whole half-line (an outlier's w is large, a large nu's tiny): st_log1p of csrc/student_math.h, a few
+ * ulp from 0 to +inf, so that at nu = 1e6 the density tends to the linear family's without losing digits.
+ * The posterior is not log-concave.  Where z_i^2 overflows a double lp is -inf or NaN: never a finite wrong
+ * number and never +inf.
+ * There is no default nu: until stk_model_set_student_nu has been called every density, transition and sampler
+ * entry point refuses the model (STK_E_ARG) with a message that says so.  nu is part of what
+ * stk_sampler_load_state compares: a state saved at nu = 4 is refused by a model at nu = 5.
+ * The sampler (any chains, the three metrics, both U-turn criteria, saved states), the gradient hooks,
+ * stk_model_set_prior, data copy-out and the fingerprints treat the family as they treat STK_LINREG.  Refused by
+ * name with STK_E_ARG, before any work: stk_model_create_synthetic, stk_sampler_set_allreduce and the analysis
+ * sweeps (stk_log_density_hessian, stk_log_predictive, stk_loo, stk_log_density_draws,
+ * stk_log_density_grad_boot, stk_posterior_predict). */
 
 /* One data shard (= one Spark partition, stark/stark.py:35).
  *   schools: n_rows = J, y[J], sigma[J]                   (example/stark_ex.py:8-11)
@@ -135,7 +157,8 @@ enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEG
  *            first negative row is named in the error); y and sigma must be NULL -- counts
  *            handed over as doubles as well as ints are refused (STK_E_ARG), here and by
  *            stk_shard_fingerprint_host, instead of one of the two being ignored
- *   negbin : as poisson (x, y_int >= 0, y and sigma NULL)                            */
+ *   negbin : as poisson (x, y_int >= 0, y and sigma NULL)
+ *   student: as linreg (x, y)                                                        */
 typedef struct {
   int64_t n_rows;
   int32_t n_cols;
@@ -248,6 +271,10 @@ STK_API int stk_model_set_prior(stk_model* m, double alpha_scale, double beta_sc
 /* STK_NEGBIN only: phi ~ gamma(shape, rate), which adds (shape - 1) v - rate e^v to lp (exponential(r)
  * is gamma(1, r)).  shape > 0, rate >= 0; (1, 0) is flat, the default.  Every shard, before sampling. */
 STK_API int stk_model_set_prior_phi(stk_model* m, double shape, double rate);
+/* STK_STUDENT only: the degrees of freedom nu of y ~ student_t(nu, ., sigma), finite and > 0 (else STK_E_ARG
+ * with the value in the message; any other family is refused by name).  Required before any density,
+ * transition or sampler call: there is no default.  Every shard, before sampling. */
+STK_API int stk_model_set_student_nu(stk_model* m, double nu);
 /* The two phi-only sums of STK_NEGBIN over n counts y_int >= 0 at phi > 0, computed on the host by the
  * code the device runs (its table builder and term functions): out[0] = sum_i sum_{j < y_i} log1p(j / phi),
  * out[1] = sum_i [psi(y_i + phi) - psi(phi)].  No device is touched. */
@@ -277,9 +304,9 @@ STK_API int stk_model_device_bytes(const stk_model* m, int64_t* bytes);
  * reduction order gives the same bits.
  *
  *   shard fingerprint = fmix( words([family, n_rows, n_cols], 0, 0)     n_cols = 0 for schools; family is
- *                                                                        the STK_* value (poisson: 4, negbin: 5)
+ *                                                                        the STK_* value (poisson: 4, negbin: 5, student: 6)
  *                           + words(x: n_rows * n_cols doubles, row-major, 1, 0)   regressions
- *                           + words(y doubles, 2, 0)                    linreg, schools
+ *                           + words(y doubles, 2, 0)                    linreg, student, schools
  *                           + words(y_int int32, 3, 0)                  logreg, poisson, negbin
  *                           + words(sigma doubles, 4, 0) )              schools
  *

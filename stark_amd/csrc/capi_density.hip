@@ -28,6 +28,7 @@ std::vector<int> chain_batches(int C, int d) {
 // Refuses, before anything is launched, a shard that no sweep covers at its n, d and batch size.
 int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int count, ChainPlan* cp) {
   *cp = ChainPlan();
+  RC(model_ready(m));   // every density, transition and sampler entry point of a regression plans its sweeps here
   for (const int sz : sizes) {
     ChainBatch b;
     b.c0 = cp->Ct;

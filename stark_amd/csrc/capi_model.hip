@@ -9,14 +9,21 @@ const char* family_name(int family) {
     case STK_LOGREG: return "logistic";
     case STK_POISSON: return "poisson";
     case STK_NEGBIN: return "neg_binomial";
+    case STK_STUDENT: return "student_t";
   }
   return "unknown";
 }
 
 // The families every regression entry point serves (the analysis sweeps among them)...
 bool is_regression(int family) { return family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON; }
-// ...and those the gradient sweeps, the sampler and the priors serve: the negative binomial too.
-bool is_sweep_family(int family) { return is_regression(family) || family == STK_NEGBIN; }
+// ...and those the gradient sweeps, the sampler and the priors serve: the negative binomial and Student-t too.
+bool is_sweep_family(int family) { return is_regression(family) || family == STK_NEGBIN || family == STK_STUDENT; }
+
+int model_ready(const stk_model* m) {
+  ARG_CHECK(m->family != STK_STUDENT || m->nu > 0.0,
+            "the student_t model's nu has not been set: call stk_model_set_student_nu first (there is no default)");
+  return STK_OK;
+}
 
 ShardRange shard_range(const stk_model* m, int shard, int (*chunks)(int64_t n)) {
   ShardRange r{shard < 0 ? 0 : shard, shard < 0 ? m->nshards : 1, 1};
@@ -31,6 +38,7 @@ static int family_dims(int family, int64_t n, int d, int* D, int* P) {
     case STK_LOGREG: *D = d + 1; *P = d + 2; return STK_OK;
     case STK_POISSON: *D = d + 1; *P = d + 2; return STK_OK;   // the logistic layout: alpha, beta, lp__
     case STK_NEGBIN: *D = d + 2; *P = d + 3; return STK_OK;    // the linear layout: alpha, beta, phi (v = log phi), lp__
+    case STK_STUDENT: *D = d + 2; *P = d + 3; return STK_OK;   // the linear layout itself: alpha, beta, sigma (s = log sigma), lp__
   }
   stk_set_error("unknown model family %d", family);
   return STK_E_ARG;
@@ -189,8 +197,8 @@ static int upload_shard(stk_model* m, int s, const stk_shard& in) {
       RC(check_y_int(m, s, sd.yi, in.n_rows, pois, family == STK_NEGBIN ? "neg_binomial_2_log needs y >= 0" : "poisson_log needs y >= 0"));
       if (family == STK_NEGBIN) RC(attach_nb_table(m, sd.yi, in.n_rows));
     } else {   // family_dims knows every family: a new one must say here which y it takes
-      ARG_CHECK(family == STK_LINREG, "shard %d: model family %d has no data layout", s, family);
-      ARG_CHECK(in.y, "shard %d: linreg needs y", s);
+      ARG_CHECK(family == STK_LINREG || family == STK_STUDENT, "shard %d: model family %d has no data layout", s, family);
+      ARG_CHECK(in.y, "shard %d: %s needs y", s, family == STK_STUDENT ? "student_t" : "linreg");
       RC(upload(m, in.y, n, &sd.y));
     }
   }
@@ -273,7 +281,7 @@ int model_fingerprint(stk_model* m, int shard, uint64_t* out) {
     if (s.x) STK_HIP_CHECK(stk_launch_fp_words(s.x, s.n * s.d, 8, 1, 0, sum, st));
     if (s.y) STK_HIP_CHECK(stk_launch_fp_words(s.y, s.n, 8, 2, 0, sum, st));
     if (s.yi) STK_HIP_CHECK(stk_launch_fp_words(s.yi, s.n, 4, 3, 0, sum, st));
-    if (s.sigma) STK_HIP_CHECK(stk_launch_fp_words(s.sigma, s.n, 8, 4, 0, sum, st));
+    if (m->family == STK_SCHOOLS) STK_HIP_CHECK(stk_launch_fp_words(s.sigma, s.n, 8, 4, 0, sum, st));   // the only family with a sigma array
     unsigned long long v = 0;
     STK_HIP_CHECK(hipMemcpyAsync(&v, sum, sizeof(v), hipMemcpyDeviceToHost, st));
     STK_HIP_CHECK(hipStreamSynchronize(st));
@@ -380,6 +388,17 @@ int stk_model_set_prior_phi(stk_model* m, double shape, double rate) {
   return upload_nb_table(m);
 }
 
+int stk_model_set_student_nu(stk_model* m, double nu) {
+  ARG_CHECK(m, "stk_model_set_student_nu: NULL model");
+  ARG_CHECK(m->family == STK_STUDENT, "stk_model_set_student_nu: nu is for the student_t family, not for the %s family (%d)",
+            family_name(m->family), m->family);
+  ARG_CHECK(std::isfinite(nu) && nu > 0.0, "stk_model_set_student_nu: nu must be finite and > 0, got %g", nu);
+  m->nu = nu;
+  for (auto& sd : m->sh) shard_set_nu(sd, nu);
+  STK_HIP_CHECK(hipSetDevice(m->ctx->device));
+  return upload_shard_table(m);
+}
+
 int stk_negbin_phi_terms_host(const int32_t* y_int, int64_t n, double phi, double* out) {
   ARG_CHECK(y_int && out && n > 0, "stk_negbin_phi_terms_host: bad arguments");
   ARG_CHECK(phi > 0.0 && std::isfinite(phi), "stk_negbin_phi_terms_host: phi must be positive and finite, got %g", phi);
@@ -404,7 +423,7 @@ int stk_negbin_phi_terms_host(const int32_t* y_int, int64_t n, double phi, doubl
 int stk_model_shard_arrays(const stk_model* m, int shard, stk_shard* out) {
   ARG_CHECK(m && out && shard >= 0 && shard < m->nshards, "stk_model_shard_arrays: bad arguments");
   const ShardDev& s = m->sh[shard];
-  *out = stk_shard{s.n, s.d, s.x, s.y, s.yi, s.sigma};
+  *out = stk_shard{s.n, s.d, s.x, s.y, s.yi, m->family == STK_SCHOOLS ? s.sigma : nullptr};
   return STK_OK;
 }
 
@@ -455,7 +474,8 @@ int stk_fingerprint_words(stk_ctx* ctx, const void* buf, int64_t count, int32_t 
 
 int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
   ARG_CHECK(sh && out, "stk_shard_fingerprint_host: bad arguments");
-  ARG_CHECK(family == STK_SCHOOLS || family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN,
+  ARG_CHECK(family == STK_SCHOOLS || family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN ||
+                family == STK_STUDENT,
             "unknown model family %d", family);
   ARG_CHECK(sh->n_rows > 0, "stk_shard_fingerprint_host: n_rows must be positive");
   uint64_t acc = fp_shard_header(family, sh->n_rows, sh->n_cols);
@@ -472,7 +492,7 @@ int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
                 "stk_shard_fingerprint_host: %s takes its counts in y_int alone; y and sigma must be NULL", fam);
       acc += stk_fp_words_host(sh->y_int, sh->n_rows, 4, 3, 0);
     } else {
-      ARG_CHECK(sh->y, "stk_shard_fingerprint_host: linreg needs y");
+      ARG_CHECK(sh->y, "stk_shard_fingerprint_host: %s needs y", family == STK_STUDENT ? "student_t" : "linreg");
       acc += stk_fp_words_host(sh->y, sh->n_rows, 8, 2, 0);
     }
   }

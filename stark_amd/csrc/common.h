@@ -46,13 +46,18 @@ struct ShardDev {
   const double* x;      // n x d row-major (regressions)
   const double* y;      // schools y / linreg y
   const int32_t* yi;    // logreg y
-  const double* sigma;  // schools sigma
+  const double* sigma;  // schools sigma; student_t: the bits of nu (shard_nu below)
   int64_t n;            // rows (J for schools)
   int d;                // covariates
   int D;                // unconstrained dimension
   int P;                // output columns (params + transformed params + lp__)
   double pa, pb;        // regressions: prior precisions 1/s^2 of alpha ~ normal(0, s_a), beta ~ normal(0, s_b) (0: flat)
 };
+
+// student_t's one constant, the degrees of freedom nu (0: not set), rides in the eight bytes of `sigma`, which no
+// regression reads: ShardDev keeps the size and the offsets every kernel was built with.
+__host__ __device__ inline double shard_nu(const ShardDev& s) { return __builtin_bit_cast(double, s.sigma); }
+inline void shard_set_nu(ShardDev& s, double nu) { s.sigma = __builtin_bit_cast(const double*, nu); }
 
 // Workspace of the two-pass (v5, 64-chain) sweep: beta^T images and the residual matrix.
 struct SweepWs {

@@ -52,8 +52,9 @@ struct SweepCall {
 };
 
 // Columns of a chunk's partial row per chain: d alpha, d beta[1..d], the lp sum -- and, for the
-// negative binomial, the unweighted sum of sp(t) that its v gradient needs.
-inline int sweep_pw(int family, int d) { return d + (family == STK_NEGBIN ? 3 : 2); }
+// negative binomial, the unweighted sum of sp(t) that its v gradient needs; for student_t, the sum of
+// z^2 / (nu + z^2) that its log-sigma gradient needs.
+inline int sweep_pw(int family, int d) { return d + ((family == STK_NEGBIN || family == STK_STUDENT) ? 3 : 2); }
 
 }  // namespace stk
 
@@ -78,6 +79,11 @@ hipError_t stk_launch_sweep_negbin(const stk::SweepLaunch& p, const stk::SweepAr
 hipError_t stk_launch_gemm_fwd_negbin(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
 hipError_t stk_launch_sweep_reduce_negbin(const stk::SweepArgs& A, const stk::NbShardDev* nb, int nchains, int d,
                                           double* lp_out, double* g_out, int C, hipStream_t st);
+// ---- sweep_st.hip (sweep.hip's student_t translation unit): the same three
+hipError_t stk_launch_sweep_student(const stk::SweepLaunch& p, const stk::SweepArgs& A, int nblocks, hipStream_t st);
+hipError_t stk_launch_gemm_fwd_student(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
+hipError_t stk_launch_sweep_reduce_student(const stk::SweepArgs& A, int nblocks_x, int nblocks_y, double* lp_out,
+                                           double* g_out, int C, hipStream_t st);
 
 // ---- sweep16.hip: shapes k_sweep16 covers, its LDS bytes, its launch
 bool stk_sweep16_supported(int d);
@@ -85,6 +91,7 @@ size_t stk_sweep16_lds_bytes(int family, int d);
 hipError_t stk_launch_sweep16(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
 hipError_t stk_launch_sweep16_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16_pois.hip
 hipError_t stk_launch_sweep16_negbin(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);    // sweep16_nb.hip
+hipError_t stk_launch_sweep16_student(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16_st.hip
 
 // ---- sweep16w.hip (128 < d <= 1024): waves per block, chunks per shard, LDS bytes, launch
 bool stk_sweep16w_supported(int d);
@@ -94,6 +101,7 @@ size_t stk_sweep16w_lds_bytes(int family, int d);
 hipError_t stk_launch_sweep16w(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
 hipError_t stk_launch_sweep16w_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16w_pois.hip
 hipError_t stk_launch_sweep16w_negbin(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);    // sweep16w_nb.hip
+hipError_t stk_launch_sweep16w_student(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16w_st.hip
 
 // ---- hessian.hip (regressions, d <= 128): the analytic Hessian sweep's geometry and launch
 bool stk_hessian_supported(int d);

@@ -26,7 +26,7 @@
 
 // A family's own translation unit (sweep_pois.hip, sweep_nb.hip) holds that family's instantiations
 // and launchers only: what is not a template is defined once, in sweep.hip itself.
-#if defined(STK_SWEEP_POISSON_TU) || defined(STK_SWEEP_NEGBIN_TU)
+#if defined(STK_SWEEP_POISSON_TU) || defined(STK_SWEEP_NEGBIN_TU) || defined(STK_SWEEP_STUDENT_TU)
 #define STK_SWEEP_FAMILY_TU 1
 #endif
 
@@ -34,12 +34,17 @@ namespace stk {
 
 // A family is a residual, not a kernel: every sweep takes FAM and must know it.
 template <int FAM>
-constexpr bool fam_known = FAM == STK_LINREG || FAM == STK_LOGREG || FAM == STK_POISSON || FAM == STK_NEGBIN;
+constexpr bool fam_known = FAM == STK_LINREG || FAM == STK_LOGREG || FAM == STK_POISSON || FAM == STK_NEGBIN || FAM == STK_STUDENT;
 template <int FAM>
 constexpr bool fam_yint = FAM == STK_LOGREG || FAM == STK_POISSON || FAM == STK_NEGBIN;   // y is the shard's int32 y_int
 // The scalar next to beta, q[d + 1], as the kernels carry it per chain in their inv_s slot: linear
 // 1 / sigma = exp(-u); negative binomial v = log phi itself, with phi = exp(v) kept beside it (once per
-// chain, not per element); the others have none.
+// chain, not per element); student_t 1 / sigma as linear (its y is the shard's double y too; nu, nu + 1 and
+// 1 / nu are wave-uniform, read once from the shard's entry); the others have none.
+template <int FAM>
+constexpr bool fam_inv_sigma = FAM == STK_LINREG || FAM == STK_STUDENT;
+template <int FAM>
+constexpr bool fam_sum3 = FAM == STK_NEGBIN || FAM == STK_STUDENT;   // a third partial sum per chain, column d + 2
 
 template <int FAM, int C, int T, int JPT, int VEC>
 __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
@@ -67,16 +72,22 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
   if (tid < C) {
     const double* qc = A.q + chain_row(A, shard, tid) * A.Dp;
     Al[tid] = qc[0];
-    Al[C + tid] = (FAM == STK_LINREG) ? exp(-qc[d + 1]) : (FAM == STK_NEGBIN) ? qc[d + 1] : 0.0;
+    Al[C + tid] = fam_inv_sigma<FAM> ? exp(-qc[d + 1]) : (FAM == STK_NEGBIN) ? qc[d + 1] : 0.0;
   }
-  constexpr bool NB = FAM == STK_NEGBIN;
-  double nbphi[NB ? C : 1], ssa[NB ? C : 1];   // negative binomial: phi_c, sum of sp
+  constexpr bool NB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
+  double nbphi[NB ? C : 1], ssa[fam_sum3<FAM> ? C : 1];   // negative binomial: phi_c, sum of sp; student_t: sum z^2 / (nu + z^2)
   if constexpr (NB) {
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       nbphi[c] = exp(A.q[chain_row(A, shard, c) * A.Dp + d + 1]);
       ssa[c] = 0.0;
     }
+  }
+  double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;
+  if constexpr (ST) {
+    nu = shard_nu(sh), nu1 = nu + 1.0, inv_nu = 1.0 / nu;
+#pragma unroll
+    for (int c = 0; c < C; ++c) ssa[c] = 0.0;
   }
 
   // per-thread accumulators
@@ -178,6 +189,8 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
             de = yc - mu;
           } else if constexpr (NB) {
             de = negbin_resid_libm(eta, (double)gp(sh.yi)[row], Al[C + c], nbphi[c], lpa[c], ssa[c]);
+          } else if constexpr (ST) {
+            de = student_resid_libm(eta, gp(sh.y)[row], Al[C + c], nu, nu1, inv_nu, lpa[c], ssa[c]);
           } else {
             static_assert(fam_known<FAM>, "k_sweep: unknown family");
             const double is = Al[C + c];
@@ -240,7 +253,7 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
     for (int i = 0; i < NT; ++i) v += src[i];
     out[(size_t)c * A.PW + (is_lp ? d + 1 : 0)] = v;
   }
-  if constexpr (NB) {   // the third scalar sum, column d + 2, through the same area
+  if constexpr (fam_sum3<FAM>) {   // the third scalar sum, column d + 2, through the same area
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < C; ++c) red[(size_t)c * NT + tid] = ssa[c];
@@ -291,13 +304,19 @@ __global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     alpha[c] = qs[(size_t)c * A.Dp];
-    inv_s[c] = (FAM == STK_LINREG) ? exp(-qs[(size_t)c * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)c * A.Dp + d + 1] : 0.0;
+    inv_s[c] = fam_inv_sigma<FAM> ? exp(-qs[(size_t)c * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)c * A.Dp + d + 1] : 0.0;
   }
-  constexpr bool NB = FAM == STK_NEGBIN;
-  double nbphi[NB ? C : 1], ssa[NB ? CP : 1];   // negative binomial: phi_c, sum of sp per residual pair
+  constexpr bool NB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
+  double nbphi[NB ? C : 1], ssa[fam_sum3<FAM> ? CP : 1];   // negative binomial: phi_c; the third sum per residual pair
   if constexpr (NB) {
 #pragma unroll
     for (int c = 0; c < C; ++c) nbphi[c] = exp(inv_s[c]);
+#pragma unroll
+    for (int i = 0; i < CP; ++i) ssa[i] = 0.0;
+  }
+  double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;
+  if constexpr (ST) {
+    nu = shard_nu(sh), nu1 = nu + 1.0, inv_nu = 1.0 / nu;
 #pragma unroll
     for (int i = 0; i < CP; ++i) ssa[i] = 0.0;
   }
@@ -398,6 +417,8 @@ __global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_
             for (int cc = 1; cc < C; ++cc)
               if (cc == c) ph = nbphi[cc];
             de = negbin_resid_libm(eta, (double)ycur, is, ph, lpa[i], ssa[i]);
+          } else if constexpr (ST) {
+            de = student_resid_libm(eta, ycur, is, nu, nu1, inv_nu, lpa[i], ssa[i]);
           } else {
             const double z = (ycur - eta) * is;
             lpa[i] += z * z;
@@ -460,7 +481,7 @@ __global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_
     for (int k = 0; k < 64; ++k) v += src[k];
     out[(size_t)c * A.PW + (kind == 0 ? d + 1 : 0)] = v;
   }
-  if constexpr (NB) {   // the third scalar sum, column d + 2, through the same area
+  if constexpr (fam_sum3<FAM>) {   // the third scalar sum, column d + 2, through the same area
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < CP; ++i) red[(size_t)i * NT + tid] = ssa[i];
@@ -579,10 +600,12 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
   }
   const int rc = fi < C ? fi : 0;                        // residual chain of this lane
   const double alpha = qs[(size_t)rc * A.Dp];
-  const double inv_s = (FAM == STK_LINREG) ? exp(-qs[(size_t)rc * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)rc * A.Dp + d + 1] : 0.0;
-  constexpr bool NEGB = FAM == STK_NEGBIN;
-  double nbphi = 0.0, ssa = 0.0;                          // negative binomial: phi of chain rc, sum of sp
+  const double inv_s = fam_inv_sigma<FAM> ? exp(-qs[(size_t)rc * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)rc * A.Dp + d + 1] : 0.0;
+  constexpr bool NEGB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
+  double nbphi = 0.0, ssa = 0.0;                          // negative binomial: phi of chain rc, sum of sp (student_t: of z^2 / (nu + z^2))
   if constexpr (NEGB) nbphi = exp(inv_s);
+  double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;
+  if constexpr (ST) nu = shard_nu(sh), nu1 = nu + 1.0, inv_nu = 1.0 / nu;
   __builtin_amdgcn_s_waitcnt(0xF70);                      // ordinary loads retired before the DMAs start
 
   // ---- DMA issue: sub-tile t of this wave = rows [64 t + 8 w, 64 t + 8 w + 8) of the chunk:
@@ -670,6 +693,8 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
           de = yc - mu;
         } else if constexpr (NEGB) {
           de = negbin_resid_libm(eta, (double)*reinterpret_cast<const int32_t*>(ys + frow * 4), inv_s, nbphi, lpa, ssa);
+        } else if constexpr (ST) {
+          de = student_resid_libm(eta, *reinterpret_cast<const double*>(ys + frow * 8), inv_s, nu, nu1, inv_nu, lpa, ssa);
         } else {
           const double yv = *reinterpret_cast<const double*>(ys + frow * 8);
           const double z = (yv - eta) * inv_s;
@@ -733,7 +758,7 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
       for (int g = 0; g < 8; ++g) v += red2[(size_t)(ww * 64 + g * 8 + c) * 2 + kind];
     out[(size_t)c * A.PW + (kind == 0 ? d + 1 : 0)] = v;
   }
-  if constexpr (NEGB) {   // the third scalar sum, column d + 2, through the same area
+  if constexpr (fam_sum3<FAM>) {   // the third scalar sum, column d + 2, through the same area
     __syncthreads();
     red2[(size_t)tid * 2] = ssa;
     __syncthreads();
@@ -824,9 +849,10 @@ __device__ __forceinline__ void dma16_lds(__amdgpu_buffer_rsrc_t r, char* dst, i
 // (Template geometry for tools/gemm_fwd_ab.py's A/B arms: NW waves of RT 16-row tiles, KCF-column
 // stages, an NS-deep ring; the product launches the defaults with SPLIT 0 or 1.)
 // (The negative binomial's residual -- a log1p per element, phi and a third sum per chain tile -- does
-// not fit beside the 128 accumulator and parked-eta registers at two blocks per CU: it runs one.)
+// not fit beside the 128 accumulator and parked-eta registers at two blocks per CU: it runs one.  So does
+// student_t's, a full-range log1p and a reciprocal per element: at two blocks it spilt 33 VGPRs.)
 template <int FAM, int NW = G5_FW, int RT = 2, int KCF = G5_FKC, int NS = G5_FS, int SPLIT = 0>
-__global__ __launch_bounds__(64 * NW, FAM == STK_NEGBIN ? 1 : 8 / NW) void k_gemm_fwd(SweepArgs A) {
+__global__ __launch_bounds__(64 * NW, (FAM == STK_NEGBIN || FAM == STK_STUDENT) ? 1 : 8 / NW) void k_gemm_fwd(SweepArgs A) {
   constexpr int NCT = 4, TR = 16 * RT * NW;
   constexpr int XB = TR * KCF * 8, BB = KCF * 512, STG = XB + BB;
   constexpr int PPR = KCF / 2;                          // 16-B pieces per X row in the stage (8)
@@ -865,10 +891,12 @@ __global__ __launch_bounds__(64 * NW, FAM == STK_NEGBIN ? 1 : 8 / NW) void k_gem
 #pragma unroll
   for (int c2 = 0; c2 < NCT; ++c2) {
     alpha[c2] = qb[(size_t)(16 * c2 + lr) * A.Dp];
-    inv_s[c2] = (FAM == STK_LINREG) ? exp(-qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1])
+    inv_s[c2] = fam_inv_sigma<FAM> ? exp(-qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1])
                 : (FAM == STK_NEGBIN) ? qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1] : 0.0;
   }
-  constexpr bool NB = FAM == STK_NEGBIN;
+  constexpr bool NB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
+  double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;            // student_t: wave-uniform, read once
+  if constexpr (ST) nu = shard_nu(sh), nu1 = nu + 1.0, inv_nu = 1.0 / nu;
   double nbphi[NB ? NCT : 1];                          // negative binomial: phi of the lane's chains (inv_s holds v)
   if constexpr (NB) {
 #pragma unroll
@@ -897,7 +925,8 @@ __global__ __launch_bounds__(64 * NW, FAM == STK_NEGBIN ? 1 : 8 / NW) void k_gem
   };
   // per chain tile: logistic lm = sum(t - |t|) - 2 sum(flushed log1p(sp)), sp = prod(1 + e) - 1
   // (residual v4, sweep_common.h); linear: lm = sum z^2; poisson: lm = sum (y eta - mu), the lp itself;
-  // negative binomial: lm = sum (y eta - (y + phi) sp(t)) and sp = sum sp(t)
+  // negative binomial: lm = sum (y eta - (y + phi) sp(t)) and sp = sum sp(t);
+  // student_t: lm = sum log1p(z^2 / nu) and sp = sum z^2 / (nu + z^2)
   double lm[NCT], sp[NCT], gaa[NCT];
 #pragma unroll
   for (int c2 = 0; c2 < NCT; ++c2) lm[c2] = sp[c2] = gaa[c2] = 0.0;
@@ -930,6 +959,11 @@ __global__ __launch_bounds__(64 * NW, FAM == STK_NEGBIN ? 1 : 8 / NW) void k_gem
       } else if constexpr (NB) {
         double lm2 = lm[c2], sp2 = sp[c2];
         dv = negbin_resid(eta, pyc[rt][i], inv_s[c2], nbphi[c2], sptab, lm2, sp2);
+        lm[c2] = valid ? lm2 : lm[c2];
+        sp[c2] = valid ? sp2 : sp[c2];
+      } else if constexpr (ST) {
+        double lm2 = lm[c2], sp2 = sp[c2];
+        dv = student_resid(eta, pyt[rt][i], inv_s[c2], nu, nu1, inv_nu, lm2, sp2);
         lm[c2] = valid ? lm2 : lm[c2];
         sp[c2] = valid ? sp2 : sp[c2];
       } else {
@@ -1054,7 +1088,7 @@ __global__ __launch_bounds__(64 * NW, FAM == STK_NEGBIN ? 1 : 8 / NW) void k_gem
       for (int h = 0; h < 4; ++h) v += red[((ww * 64 + h * 16 + l) * NCT + c2) * 2 + kind];
     A.partial[(((size_t)shard * A.Gs + chunk) * G5_C + c) * A.PW + (kind == 0 ? d + 1 : 0)] = v;
   }
-  if constexpr (NB) {   // the third scalar sum, column d + 2, through the same area
+  if constexpr (fam_sum3<FAM>) {   // the third scalar sum, column d + 2, through the same area
     __syncthreads();
 #pragma unroll
     for (int c2 = 0; c2 < NCT; ++c2) red[((w * 64 + lane) * NCT + c2) * 2] = sp[c2];
@@ -1229,7 +1263,15 @@ __global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce(SweepArgs A, double*
     }
   }
   static_assert(fam_known<FAM>, "k_sweep_reduce: unknown family");
-  if (FAM == STK_LOGREG || FAM == STK_POISSON) {   // the sums are lp and the gradient themselves
+  if constexpr (FAM == STK_STUDENT) {
+    // student_t (PW = d + 3): column d + 1 is sum log1p(z^2 / nu), column d + 2 is sum z^2 / (nu + z^2); with
+    // sigma = exp(u) and its Jacobian, lp = -(nu + 1)/2 S1 - N u + u and d lp / d u = (nu + 1) S2 - N + 1
+    const double u = qc[d + 1];
+    const double N = (double)sh.n, nu1 = shard_nu(sh) + 1.0;
+    if (o == d + 1) lp_out[gid] = -0.5 * nu1 * t - N * u + u + prior_lp;
+    else if (o == d + 2) g[d + 1] = fma(nu1, t, -N) + 1.0;
+    else g[o] = t + prior_g;
+  } else if (FAM == STK_LOGREG || FAM == STK_POISSON) {   // the sums are lp and the gradient themselves
     if (o == d + 1) lp_out[gid] = t + prior_lp;
     else g[o] = t + prior_g;
   } else {                                         // linear: sigma = exp(u) and its Jacobian
@@ -1582,11 +1624,24 @@ hipError_t stk_launch_sweep_reduce_negbin(const SweepArgs& A, const NbShardDev* 
   return hipGetLastError();
 }
 #endif
+#if defined(STK_SWEEP_STUDENT_TU) || !defined(STK_POISSON_OWN_TU)   // sweep_st.hip, by the same rule
+hipError_t stk_launch_sweep_student(const SweepLaunch& p, const SweepArgs& A, int nblocks, hipStream_t st) {
+  return pick_c<STK_STUDENT>(p, A, nblocks, st);
+}
+hipError_t stk_launch_gemm_fwd_student(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  return launch_gemm_fwd<STK_STUDENT>(A, d, nblocks, lds, st);
+}
+hipError_t stk_launch_sweep_reduce_student(const SweepArgs& A, int nblocks_x, int nblocks_y, double* lp_out, double* g_out,
+                                           int C, hipStream_t st) {
+  return launch_reduce<STK_STUDENT>(A, dim3(nblocks_x, nblocks_y), lp_out, g_out, C, st);
+}
+#endif
 #ifndef STK_SWEEP_FAMILY_TU
 // Launch the plan's sweep over `nsh` shards starting at shard0 (all of the plan's n) for the batch
 // of p.C chains that starts at chain c.c0 of every shard's c.Ct.
 hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int nsh, const SweepCall& c, hipStream_t st) {
-  if (family != STK_LOGREG && family != STK_LINREG && family != STK_POISSON && family != STK_NEGBIN) return hipErrorInvalidValue;
+  if (family != STK_LOGREG && family != STK_LINREG && family != STK_POISSON && family != STK_NEGBIN && family != STK_STUDENT)
+    return hipErrorInvalidValue;
   SweepArgs A = sweep_args(family, p, shard0, c, stk_sweep_args_ld(p));
   const int nblocks = nsh * p.G, d = p.d;
   if (p.kind == SWEEP_GEMM64) {
@@ -1599,6 +1654,7 @@ hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int ns
     const hipError_t ef = family == STK_LOGREG   ? launch_gemm_fwd<STK_LOGREG>(A, d, nblocks, p.lds, st)
                           : family == STK_LINREG ? launch_gemm_fwd<STK_LINREG>(A, d, nblocks, p.lds, st)
                           : family == STK_NEGBIN ? stk_launch_gemm_fwd_negbin(A, d, nblocks, p.lds, st)
+                          : family == STK_STUDENT ? stk_launch_gemm_fwd_student(A, d, nblocks, p.lds, st)
                                                  : stk_launch_gemm_fwd_poisson(A, d, nblocks, p.lds, st);
     if (ef != hipSuccess) return ef;
     auto kb = bjb == 64 ? k_gemm_bwd<64> : bjb == 128 ? k_gemm_bwd<128> : k_gemm_bwd<256>;
@@ -1609,6 +1665,7 @@ hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int ns
   if (family == STK_LOGREG) return pick_c<STK_LOGREG>(p, A, nblocks, st);
   if (family == STK_LINREG) return pick_c<STK_LINREG>(p, A, nblocks, st);
   if (family == STK_NEGBIN) return stk_launch_sweep_negbin(p, A, nblocks, st);
+  if (family == STK_STUDENT) return stk_launch_sweep_student(p, A, nblocks, st);
   return stk_launch_sweep_poisson(p, A, nblocks, st);
 }
 
@@ -1621,6 +1678,8 @@ hipError_t stk_launch_sweep_reduce(int family, const SweepLaunch& p, int shard0,
   if (family == STK_LINREG) return launch_reduce<STK_LINREG>(A, grid, lp_out, g_out, p.C, st);
   if (family == STK_POISSON) return stk_launch_sweep_reduce_poisson(A, grid.x, grid.y, lp_out, g_out, p.C, st);
   if (family == STK_NEGBIN) return stk_launch_sweep_reduce_negbin(A, c.nb, nsh * p.C, p.d, lp_out, g_out, p.C, st);
+  if (family == STK_STUDENT)   // PW = d + 3 columns
+    return stk_launch_sweep_reduce_student(A, grid.x, (p.d + 3 + 63) / 64, lp_out, g_out, p.C, st);
   return hipErrorInvalidValue;
 }
 #endif  // STK_SWEEP_FAMILY_TU

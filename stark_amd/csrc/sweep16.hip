@@ -36,7 +36,7 @@
 
 // A family's own translation unit (sweep16_pois.hip, sweep16_nb.hip) holds that family's instantiations and
 // launcher only.
-#if defined(STK_SWEEP16_POISSON_TU) || defined(STK_SWEEP16_NEGBIN_TU)
+#if defined(STK_SWEEP16_POISSON_TU) || defined(STK_SWEEP16_NEGBIN_TU) || defined(STK_SWEEP16_STUDENT_TU)
 #define STK_SWEEP16_FAMILY_TU 1
 #endif
 
@@ -64,7 +64,11 @@ __host__ __device__ constexpr S16Geom s16_geom(int KF) {
 // Poisson keeps the logistic rule: its residual is lighter (KF = 27: 248 VGPRs against 256), but
 // beta and the operands are the same 4 JTM + KF doubles.
 // The negative binomial's residual is the heaviest (a log1p per element, phi beside v): KF <= 25.
-__host__ __device__ constexpr bool s16_pre(int FAM, int KF) { return FAM == STK_LINREG || KF <= (FAM == STK_NEGBIN ? 25 : 27); }
+// Student-t has the linear layout but a residual of the negative binomial's weight (a full-range log1p and a
+// reciprocal per element): it takes the negative binomial's rule.
+__host__ __device__ constexpr bool s16_pre(int FAM, int KF) {
+  return FAM == STK_LINREG || KF <= ((FAM == STK_NEGBIN || FAM == STK_STUDENT) ? 25 : 27);
+}
 constexpr int S16_FLUSH = 64;                   // sub-tiles between log1p flushes (4 elements each)
 
 template <int FAM, int KF, bool PRE = s16_pre(FAM, KF), int NACC = 2>
@@ -72,7 +76,8 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   constexpr S16Geom g = s16_geom(KF);
   constexpr int C = SM_C, NW = SM_W, JTM = g.JTM;
   constexpr bool LOGI = FAM == STK_LOGREG, NB = FAM == STK_NEGBIN, POIS = FAM == STK_POISSON || NB;   // POIS: whole int32 counts
-  static_assert(LOGI || POIS || FAM == STK_LINREG, "k_sweep16: unknown family");
+  constexpr bool ST = FAM == STK_STUDENT;                // the linear layout (double y, 1 / sigma per chain), its own residual
+  static_assert(LOGI || POIS || ST || FAM == STK_LINREG, "k_sweep16: unknown family");
   const int shard = A.shard0 + blockIdx.x / A.G;
   const int chunk = blockIdx.x % A.G;
   if (A.req_step && A.req_step[shard] != A.step_id - 1) return;
@@ -104,9 +109,11 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   }
   const double alpha = qs[(size_t)lr * A.Dp];
   // linear: 1 / sigma; negative binomial: v = log phi itself, with phi beside it (a lane is one chain)
-  const double inv_s = FAM == STK_LINREG ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
+  const double inv_s = (FAM == STK_LINREG || ST) ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
   double nbphi = 0.0;
   if constexpr (NB) nbphi = exp(inv_s);
+  double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;              // student_t: wave-uniform, read once
+  if constexpr (ST) nu = shard_nu(sh), nu1 = nu + 1.0, inv_nu = 1.0 / nu;
   __syncthreads();
   __builtin_amdgcn_s_waitcnt(0xF70);
 
@@ -215,6 +222,8 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
         } else if constexpr (NB) {
           de[i] = negbin_resid(eta4[i], (int32_t)ym[i], inv_s, nbphi, tab, lm, sp);
           __builtin_amdgcn_sched_barrier(0);   // one element's temporaries at a time: interleaved, the four spill
+        } else if constexpr (ST) {
+          de[i] = student_resid(eta4[i], yv[i], inv_s, nu, nu1, inv_nu, lm, sp);
         } else if constexpr (POIS) {
           de[i] = pois_resid(eta4[i], (int32_t)ym[i], tab, lm);
         } else {
@@ -234,6 +243,8 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
         } else if constexpr (NB) {
           dv = negbin_resid(eta4[i], (int32_t)ym[i], inv_s, nbphi, tab, lm2, sp2);
           __builtin_amdgcn_sched_barrier(0);
+        } else if constexpr (ST) {
+          dv = student_resid(eta4[i], yv[i], inv_s, nu, nu1, inv_nu, lm2, sp2);
         } else if constexpr (POIS) {
           dv = pois_resid(eta4[i], (int32_t)ym[i], tab, lm2);
         } else {
@@ -334,7 +345,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
       for (int h = 0; h < 4; ++h) v += red2[(size_t)(ww * 64 + h * 16 + c) * 2 + kind];
     out[(size_t)c * A.PW + (kind == 0 ? d + 1 : 0)] = v;
   }
-  if constexpr (NB) {   // the third scalar sum (sp holds sum sp(t)), column d + 2, through the same area
+  if constexpr (NB || ST) {   // the third scalar sum (sp holds sum sp(t); student_t: sum z^2 / (nu + z^2)), column d + 2, through the same area
     __syncthreads();
     red2[(size_t)tid * 2] = sp;
     __syncthreads();
@@ -358,7 +369,7 @@ using namespace stk;
 size_t stk_sweep16_lds_bytes(int family, int d) {
   const int KF = (d + 3) / 4;
   const S16Geom g = s16_geom(KF);
-  size_t main = (size_t)SM_W * sweepm_slot_bytes(d) + (family == STK_LINREG ? 0 : EX_TAB * 8);   // logistic, poisson: the exp table
+  size_t main = (size_t)SM_W * sweepm_slot_bytes(d) + ((family == STK_LINREG || family == STK_STUDENT) ? 0 : EX_TAB * 8);   // logistic, poisson: the exp table
   const size_t red = ((size_t)SM_W * g.JT * 16 * 16 + (size_t)SM_W * 64 * 2 + (size_t)SM_W * 4 * 4 * 16) * 8;
   return std::max(main, red);
 }
@@ -399,6 +410,11 @@ hipError_t stk_launch_sweep16_negbin(const SweepArgs& A, int d, int nblocks, siz
   return launch16<STK_NEGBIN>(A, d, nblocks, lds, st);
 }
 #endif
+#if defined(STK_SWEEP16_STUDENT_TU) || !defined(STK_POISSON_OWN_TU)   // sweep16_st.hip, by the same rule
+hipError_t stk_launch_sweep16_student(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  return launch16<STK_STUDENT>(A, d, nblocks, lds, st);
+}
+#endif
 #ifndef STK_SWEEP16_FAMILY_TU
 bool stk_sweep16_supported(int d) { return d >= 1 && d <= 128; }
 
@@ -407,6 +423,7 @@ hipError_t stk_launch_sweep16(int family, const SweepArgs& A, int d, int nblocks
   if (family == STK_LINREG) return launch16<STK_LINREG>(A, d, nblocks, lds, st);
   if (family == STK_POISSON) return stk_launch_sweep16_poisson(A, d, nblocks, lds, st);
   if (family == STK_NEGBIN) return stk_launch_sweep16_negbin(A, d, nblocks, lds, st);
+  if (family == STK_STUDENT) return stk_launch_sweep16_student(A, d, nblocks, lds, st);
   return hipErrorInvalidValue;
 }
 #endif

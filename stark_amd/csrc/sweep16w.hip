@@ -34,7 +34,7 @@
 
 // A family's own translation unit (sweep16w_pois.hip, sweep16w_nb.hip) holds that family's instantiations and
 // launcher only.
-#if defined(STK_SWEEP16W_POISSON_TU) || defined(STK_SWEEP16W_NEGBIN_TU)
+#if defined(STK_SWEEP16W_POISSON_TU) || defined(STK_SWEEP16W_NEGBIN_TU) || defined(STK_SWEEP16W_STUDENT_TU)
 #define STK_SWEEP16W_FAMILY_TU 1
 #endif
 
@@ -65,7 +65,8 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   constexpr int PPR = DW / 2 + 1;                   // 16-B pieces per padded row
   constexpr int NI = (SM_R * PPR + 63) / 64;        // DMA instructions per slot; the last one has 16 lanes
   constexpr bool LOGI = FAM == STK_LOGREG, NB = FAM == STK_NEGBIN, POIS = FAM == STK_POISSON || NB;   // POIS: whole int32 counts
-  static_assert(LOGI || POIS || FAM == STK_LINREG, "k_sweep16w: unknown family");
+  constexpr bool ST = FAM == STK_STUDENT;           // the linear layout (double y, 1 / sigma per chain), its own residual
+  static_assert(LOGI || POIS || ST || FAM == STK_LINREG, "k_sweep16w: unknown family");
   constexpr int YB = (LOGI || POIS) ? 4 : 8;        // int32 y (logistic, poisson) or double y
   static_assert(KF % 4 == 0 && DW <= 128 && (SM_R * PPR) % 64 == 16, "slab geometry");
   const int NW = A.LD;                              // waves per block = column slabs
@@ -100,9 +101,11 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   }
   const double alpha = w == 0 ? qs[(size_t)lr * A.Dp] : 0.0;   // wave 0's partial starts at alpha
   // linear: 1 / sigma; negative binomial: v = log phi itself, with phi beside it (a lane is one chain)
-  const double inv_s = FAM == STK_LINREG ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
+  const double inv_s = (FAM == STK_LINREG || ST) ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
   double nbphi = 0.0;
   if constexpr (NB) nbphi = exp(inv_s);
+  double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;              // student_t: wave-uniform, read once
+  if constexpr (ST) nu = shard_nu(sh), nu1 = nu + 1.0, inv_nu = 1.0 / nu;
   __syncthreads();
   __builtin_amdgcn_s_waitcnt(0xF70);
 
@@ -186,6 +189,8 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
         } else if constexpr (NB) {
           de[i] = negbin_resid(eta4[i], (int32_t)ym[i], inv_s, nbphi, tab, lm, sp);
           __builtin_amdgcn_sched_barrier(0);   // one element's temporaries at a time: interleaved, the four spill
+        } else if constexpr (ST) {
+          de[i] = student_resid(eta4[i], yv[i], inv_s, nu, nu1, inv_nu, lm, sp);
         } else if constexpr (POIS) {
           de[i] = pois_resid(eta4[i], (int32_t)ym[i], tab, lm);
         } else {
@@ -205,6 +210,8 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
         } else if constexpr (NB) {
           dv = negbin_resid(eta4[i], (int32_t)ym[i], inv_s, nbphi, tab, lm2, sp2);
           __builtin_amdgcn_sched_barrier(0);
+        } else if constexpr (ST) {
+          dv = student_resid(eta4[i], yv[i], inv_s, nu, nu1, inv_nu, lm2, sp2);
         } else if constexpr (POIS) {
           dv = pois_resid(eta4[i], (int32_t)ym[i], tab, lm2);
         } else {
@@ -264,7 +271,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
       out[d + 1] = lpa;
       out[0] = ga;
     }
-    if constexpr (NB) {   // the third scalar sum (sp holds sum sp(t)), column d + 2, joined the same way
+    if constexpr (NB || ST) {   // the third scalar sum (sp holds sum sp(t); student_t: sum z^2 / (nu + z^2)), column d + 2, joined the same way
       sp += __shfl_xor(sp, 16);
       sp += __shfl_xor(sp, 32);
       if (lh == 0) out[d + 2] = sp;
@@ -287,7 +294,7 @@ int stk_sweep16w_chunks(int64_t n) {                  // >= SW_TILES tiles of 64
 size_t stk_sweep16w_lds_bytes(int family, int d) {
   const int nw = sw_waves(d);
   return (size_t)nw * sw_slot_bytes(sw_slab(d)) + SW_YB + (size_t)nw * 256 * 8 +
-         (family == STK_LINREG ? 0 : EX_TAB * 8);   // logistic, poisson: the exp table
+         ((family == STK_LINREG || family == STK_STUDENT) ? 0 : EX_TAB * 8);   // logistic, poisson: the exp table
 }
 #endif
 
@@ -324,6 +331,11 @@ hipError_t stk_launch_sweep16w_negbin(const SweepArgs& A, int d, int nblocks, si
   return launch16w<STK_NEGBIN>(A, d, nblocks, lds, st);
 }
 #endif
+#if defined(STK_SWEEP16W_STUDENT_TU) || !defined(STK_POISSON_OWN_TU)   // sweep16w_st.hip, by the same rule
+hipError_t stk_launch_sweep16w_student(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  return launch16w<STK_STUDENT>(A, d, nblocks, lds, st);
+}
+#endif
 #ifndef STK_SWEEP16W_FAMILY_TU
 hipError_t stk_launch_sweep16w(int family, const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
   if (!stk_sweep16w_supported(d) || A.LD != sw_waves(d) || lds < stk_sweep16w_lds_bytes(family, d) || lds > BIG_LDS_BYTES)
@@ -332,6 +344,7 @@ hipError_t stk_launch_sweep16w(int family, const SweepArgs& A, int d, int nblock
   if (family == STK_LINREG) return launch16w<STK_LINREG>(A, d, nblocks, lds, st);
   if (family == STK_POISSON) return stk_launch_sweep16w_poisson(A, d, nblocks, lds, st);
   if (family == STK_NEGBIN) return stk_launch_sweep16w_negbin(A, d, nblocks, lds, st);
+  if (family == STK_STUDENT) return stk_launch_sweep16w_student(A, d, nblocks, lds, st);
   return hipErrorInvalidValue;
 }
 #endif

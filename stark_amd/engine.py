@@ -14,11 +14,11 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_NEGBIN, STK_POISSON, STK_SCHOOLS, Config, RunInfo, Shard,
+from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_NEGBIN, STK_POISSON, STK_SCHOOLS, STK_STUDENT, Config, RunInfo, Shard,
                    StarkHipError, check)
 
 FAMILIES = {"schools": STK_SCHOOLS, "linear": STK_LINREG, "logistic": STK_LOGREG, "poisson": STK_POISSON,
-            "neg_binomial": STK_NEGBIN}
+            "neg_binomial": STK_NEGBIN, "student_t": STK_STUDENT}
 
 # Live library handles, closed in dependency order (samplers, models, contexts) before the
 # HIP runtime's own exit handlers run; after that every close() is a no-op.
@@ -282,15 +282,27 @@ def shard_fingerprint(family, shard) -> np.uint64:
 class Model:
     """Shards of one model family resident on one device (``stk_model``)."""
 
-    def __init__(self, ctx: Context, family, shards=None, _handle=None):
+    def __init__(self, ctx: Context, family, shards=None, _handle=None, nu=None):
+        """nu: the degrees of freedom of the "student_t" family, finite and > 0 -- required there (the library has
+        no default), refused for every other family."""
         self.ctx = ctx
         self.family = FAMILIES.get(family, family)
+        if self.family == STK_STUDENT:
+            if nu is None:
+                raise ValueError("the student_t family needs nu= (the degrees of freedom, > 0): there is no default")
+            if not (np.isfinite(float(nu)) and float(nu) > 0):
+                raise ValueError(f"student_t: nu must be finite and > 0, got {float(nu)!r}")
+        elif nu is not None:
+            raise ValueError(f"nu= is for the student_t family, not for the {FAMILY_NAMES.get(self.family, self.family)} family")
+        self.nu = None if nu is None else float(nu)
         if _handle is not None:
             self._h = _handle
         else:
             self._h = self._create(shards)
         _live["model"].add(self)
         lib = _lib.load()
+        if self.nu is not None:
+            check(lib.stk_model_set_student_nu(self._h, self.nu))
         self.nshards = len(shards) if shards is not None else self._nshards
         self.D, self.P, self.n_rows = [], [], []
         for s in range(self.nshards):
@@ -377,7 +389,7 @@ class Model:
             check(lib.stk_model_copy_data(self._h, shard, None, y.ctypes.data, None))
             return {"y": y}
         yint = self.family in (STK_LOGREG, STK_POISSON, STK_NEGBIN)
-        d = D - (2 if self.family in (STK_LINREG, STK_NEGBIN) else 1)
+        d = D - (2 if self.family in (STK_LINREG, STK_NEGBIN, STK_STUDENT) else 1)
         x = np.empty((n, d))
         if yint:
             y = np.empty(n, np.int32)

@@ -57,6 +57,10 @@ _PRIOR = re.compile(r"(alpha|beta)~normal\(0(?:\.0*)?," + _NUM + r"\)$")
 _PRIOR_PHI = re.compile(r"phi~(?:gamma\(" + _NUM + "," + _NUM + r"\)|exponential\(" + _NUM + r"\))$")
 
 
+# y ~ student_t(nu, alpha + x * beta, sigma): nu a positive literal or the data variable `nu`
+_STUDENT = re.compile(r"y~student_t\((?:" + _NUM + r"|(nu)),(?:alpha\+x\*beta|x\*beta\+alpha),sigma\)$")
+
+
 def _split_priors(stmts):
     """Separate `alpha ~ normal(0, s)` / `beta ~ normal(0, s)` statements (s > 0) and `phi ~ gamma(a, b)` /
     `phi ~ exponential(r)` (a, b, r > 0; stored as 'phi': (a, b)) from the rest."""
@@ -76,11 +80,16 @@ def _split_priors(stmts):
 def program_info(model_code: str):
     """(family, priors) of a supported Stan program; priors = {'alpha': s, 'beta': s} for the
     regressions' optional `alpha ~ normal(0, s)` / `beta ~ normal(0, s)` statements (absent: flat), and
-    'phi': (a, b) for the negative binomial's `phi ~ gamma(a, b)` / `phi ~ exponential(b)`."""
+    'phi': (a, b) for the negative binomial's `phi ~ gamma(a, b)` / `phi ~ exponential(b)`, and 'nu': v for a
+    student_t statement whose nu is the literal v (absent when nu is the data variable: pack_data reads it)."""
     code = _strip(model_code)
     b = _blocks(code)
     priors, rest = _split_priors(_stmts(b.get("model", "")))
     fam = _recognise_blocks(b, sorted(rest))
+    if fam == "student_t":
+        lit = _STUDENT.match(rest[0]).group(1)
+        if lit is not None:
+            priors["nu"] = float(lit)
     if fam == "schools" and priors:
         fam = None
     if fam != "neg_binomial" and "phi" in priors:   # a phi prior belongs to the negative binomial alone
@@ -88,15 +97,16 @@ def program_info(model_code: str):
     if fam is None:
         raise NotImplementedError(
             "stark_amd runs a fixed set of model families on the GPU (8 schools, Bayesian linear, logistic, "
-            "Poisson (poisson_log) and negative-binomial (neg_binomial_2_log) regression with flat or normal(0, s) "
+            "Poisson (poisson_log), negative-binomial (neg_binomial_2_log) and Student-t (student_t with nu a data "
+            "variable or a literal, never a parameter) regression with flat or normal(0, s) "
             "priors on alpha and beta, and for the negative binomial a flat, gamma(a, b) or exponential(r) prior on "
             "phi; see stark_amd/models/*.stan).  This Stan program is not one of them; pass "
-            "family='schools'|'linear'|'logistic'|'poisson'|'neg_binomial' if it is an equivalent program.")
+            "family='schools'|'linear'|'logistic'|'poisson'|'neg_binomial'|'student_t' if it is an equivalent program.")
     return fam, priors
 
 
 def recognise(model_code: str) -> str:
-    """Return 'schools', 'linear', 'logistic', 'poisson' or 'neg_binomial' for a supported Stan program."""
+    """Return 'schools', 'linear', 'logistic', 'poisson', 'neg_binomial' or 'student_t' for a supported Stan program."""
     return program_info(model_code)[0]
 
 
@@ -126,6 +136,15 @@ def _recognise_blocks(b: dict, stm: list):
             if (not _decl(params, r"sigma") and _decl(params, r"(^|;)real<lower=0>phi(;|$)") and not b.get("transformed parameters")
                     and _decl(b.get("data", ""), r"(int<lower=0>y\[N\]|array\[N\]int<lower=0>y)(;|$)")):
                 return "neg_binomial"
+        ms = _STUDENT.match(stm[0]) if len(stm) == 1 else None
+        if ms:
+            # sigma is the scale parameter itself and nu a constant: the data variable real<lower=0> nu, or a positive
+            # literal.  nu in `parameters`, a sigma that is not the parameter, an added offset or a `nu ~ ...` statement
+            # (it stays in stm) are other programs to this recogniser
+            nu_ok = (_decl(b.get("data", ""), r"(^|;)real<lower=0>nu(;|$)") if ms.group(2) else float(ms.group(1)) > 0)
+            if (_decl(params, r"(^|;)real<lower=0>sigma(;|$)") and not _decl(params, r"(^|;)[^;]*[ >\]]nu(;|$)")
+                    and not b.get("transformed parameters") and nu_ok):
+                return "student_t"
         if stm in (["y~normal(alpha+x*beta,sigma)"], ["y~normal(x*beta+alpha,sigma)"]):
             if _decl(params, r"real<lower=0>sigma"):
                 return "linear"
@@ -136,7 +155,7 @@ def load_program_info(file=None, model_code=None, family=None, priors=None, **_i
     """Mirror of pystan.StanModel(file=..., model_code=...) argument handling -> (family, priors).
     family= (and priors={'alpha': s, 'beta': s}, for 'neg_binomial' also 'phi': (shape, rate)) override recognition."""
     if family is not None:
-        if family not in ("schools", "linear", "logistic", "poisson", "neg_binomial"):
+        if family not in ("schools", "linear", "logistic", "poisson", "neg_binomial", "student_t"):
             raise ValueError(f"unknown family {family!r}")
         return family, dict(priors or {})
     if model_code is None:
@@ -152,9 +171,10 @@ def load_program(file=None, model_code=None, family=None, **kw):
     return load_program_info(file=file, model_code=model_code, family=family, **kw)[0]
 
 
-def pack_data(family: str, data: dict) -> dict:
+def pack_data(family: str, data: dict, nu=None) -> dict:
     """Validate a Stan data dict (the prepare_data_callback output, example/stark_ex.py:8-11)
-    and turn it into a shard for stk_model_create."""
+    and turn it into a shard for stk_model_create.  student_t: the shard carries "nu" too -- the statement's
+    literal when the program has one (nu=), else data["nu"] (real<lower=0> nu), which must be there, finite and > 0."""
     if family == "schools":
         J = int(data["J"])
         y = np.asarray(data["y"], np.float64).reshape(-1)
@@ -188,6 +208,15 @@ def pack_data(family: str, data: dict) -> dict:
     y = np.asarray(data["y"], np.float64).reshape(-1)
     if y.shape[0] != N:
         raise ValueError("y must have N entries")
+    if family == "student_t":
+        if nu is None:
+            if "nu" not in data:
+                raise ValueError("student_t data: nu is missing (real<lower=0> nu in the data block)")
+            nu = data["nu"]
+        nu = float(np.asarray(nu, np.float64).reshape(()))
+        if not (np.isfinite(nu) and nu > 0):
+            raise ValueError(f"student_t data: nu must be finite and > 0 (real<lower=0> nu), got {nu!r}")
+        return {"x": x, "y": y, "nu": nu}
     return {"x": x, "y": y}
 
 
@@ -199,7 +228,7 @@ def column_names(family: str, data: dict) -> list:
                 + ["lp__"])
     K = int(data["K"])
     cols = ["alpha"] + [f"beta[{k}]" for k in range(1, K + 1)]
-    if family == "linear":
+    if family in ("linear", "student_t"):
         cols.append("sigma")
     if family == "neg_binomial":
         cols.append("phi")

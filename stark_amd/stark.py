@@ -110,7 +110,7 @@ def _unconstrain(family, data, init_dict):
         return np.concatenate([[float(init_dict.get("mu", 0.0)), np.log(float(init_dict.get("tau", 1.0)))], eta])
     K = int(data["K"])
     v = [float(init_dict.get("alpha", 0.0))] + list(np.asarray(init_dict.get("beta", np.zeros(K)), np.float64).reshape(K))
-    if family == "linear":
+    if family in ("linear", "student_t"):
         v.append(np.log(float(init_dict.get("sigma", 1.0))))
     if family == "neg_binomial":
         v.append(np.log(float(init_dict.get("phi", 1.0))))
@@ -118,13 +118,15 @@ def _unconstrain(family, data, init_dict):
 
 
 NO_ANALYSIS_FAMILY = "neg_binomial"   # samples and combines; the analysis sweeps do not cover it
+NO_ANALYSIS_FAMILIES = (NO_ANALYSIS_FAMILY, "student_t")   # Student-t likewise
 
 
 def _refuse_analysis(family, what):
-    """ValueError, before any sampling, where `what` is asked of the negative binomial: the Hessian, log-predictive,
-    PSIS-LOO, per-draw log-density, bootstrap and posterior predictive sweeps cover linear, logistic and poisson."""
-    if family == NO_ANALYSIS_FAMILY:
-        raise ValueError(f"{what} is not available for the neg_binomial family: the analysis sweeps (Hessian, "
+    """ValueError, before any sampling, where `what` is asked of the negative binomial or of Student-t: the Hessian,
+    log-predictive, PSIS-LOO, per-draw log-density, bootstrap and posterior predictive sweeps cover linear, logistic
+    and poisson."""
+    if family in NO_ANALYSIS_FAMILIES:
+        raise ValueError(f"{what} is not available for the {family} family: the analysis sweeps (Hessian, "
                          "log-predictive, PSIS-LOO, per-draw log density, bootstrap, posterior predictive) cover the "
                          "linear, logistic and poisson families; sample it with NUTS and combine by consensus or "
                          "combiner='semiparametric'")
@@ -133,18 +135,18 @@ def _refuse_analysis(family, what):
 def unconstrain_draws(family, samples, n_cols=None):
     """The P x S constrained matrix ``concensusWeight`` returns (rows alpha, beta[1..d], [sigma], lp__)
     as the [S][D] unconstrained draws ``engine.Model.log_predictive`` scores: lp__ is dropped and
-    linear's sigma becomes u = log sigma (the negative binomial's phi, in sigma's row, v = log phi: its draws
-    convert, though no analysis sweep scores them).  n_cols: the model's covariate count d, when known
+    linear's sigma becomes u = log sigma (the negative binomial's phi, in sigma's row, v = log phi, and student_t's
+    sigma as linear's: their draws convert, though no analysis sweep scores them).  n_cols: the model's covariate count d, when known
     (``Stark.waic`` passes it); None takes it from the row count.
     ValueError for 8 schools (no log-predictive sweep), for P != D + 1 -- the draws of a ``pars=``
     selection cannot be scored: every parameter is needed -- and for a sigma <= 0 (names the draw)."""
-    if family not in ("linear", "logistic", "poisson", "neg_binomial"):
+    if family not in ("linear", "logistic", "poisson", "neg_binomial", "student_t"):
         raise ValueError(f"draws of the {family} family cannot be scored: the log-predictive sweep covers the "
                          "regression families (linear, logistic, poisson), not 8 schools")
     m = np.asarray(samples, np.float64)
     if m.ndim != 2:
         raise ValueError(f"samples must be the P x S draw matrix, got shape {m.shape}")
-    scale = {"linear": "sigma", "neg_binomial": "phi"}.get(family)   # the positive parameter after beta, if any
+    scale = {"linear": "sigma", "neg_binomial": "phi", "student_t": "sigma"}.get(family)   # the positive parameter after beta, if any
     extra = 2 if scale else 1                           # parameters besides beta
     d = int(n_cols) if n_cols is not None else m.shape[0] - 1 - extra
     D = d + extra
@@ -308,14 +310,25 @@ class Stark:
         """The GPU run behind _sample_partitions: every extract() row of every partition.
         laplace: the shards' Laplace covariances are fitted before the model is closed
         (self._laplace_cov, one per data dict)."""
-        shards = [frontend.pack_data(self.family, d) for d in datas]
+        priors = dict(getattr(self, "priors", None) or {})
+        model_kw = {}
+        if self.family == "student_t":
+            # nu: the statement's literal, else every partition's data["nu"] -- one model, so one value
+            shards = [frontend.pack_data(self.family, d, nu=priors.get("nu")) for d in datas]
+            nus = sorted({sh.pop("nu") for sh in shards})
+            if len(nus) != 1:
+                raise ValueError(f"student_t: the partitions' nu differ ({nus}): one model has one nu")
+            model_kw["nu"] = nus[0]
+            priors.pop("nu", None)
+        else:
+            shards = [frontend.pack_data(self.family, d) for d in datas]
         cfg = sampling_config(self.family, datas, **kwargs)
         if shard_ids is not None:
             cfg["shard_ids"] = shard_ids
         thin = cfg.pop("thin", 1)
-        model = engine.Model(engine.default_context(), self.family, shards)
-        if getattr(self, "priors", None):
-            model.set_prior(**self.priors)
+        model = engine.Model(engine.default_context(), self.family, shards, **model_kw)
+        if priors:
+            model.set_prior(**priors)
         try:
             res = model.sample(**cfg)
             if laplace:
