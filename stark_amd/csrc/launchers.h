@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "negbin_math.h"
+#include <type_traits>
 
 namespace stk {
 
@@ -51,10 +52,23 @@ struct SweepCall {
   const NbShardDev* nb = nullptr;   // STK_NEGBIN: the model's [nshards] count tables and phi priors (the reduce reads them)
 };
 
-// Columns of a chunk's partial row per chain: d alpha, d beta[1..d], the lp sum -- and, for the
-// negative binomial, the unweighted sum of sp(t) that its v gradient needs; for student_t, the sum of
-// z^2 / (nu + z^2) that its log-sigma gradient needs.
-inline int sweep_pw(int family, int d) { return d + ((family == STK_NEGBIN || family == STK_STUDENT) ? 3 : 2); }
+// Columns of a chunk's partial row per chain: d alpha, d beta[1..d], the lp sum -- and the family's third
+// sum where it has one (fam_sum3, sweep_common.h).  Defined in sweep.hip.
+int sweep_pw(int family, int d);
+
+// The one place a runtime family id becomes a template argument: f(std::integral_constant<int, FAM>) for
+// the five regression families, hipErrorInvalidValue for anything else.
+template <class F>
+hipError_t sweep_family(int family, F&& f) {
+  switch (family) {
+    case STK_LINREG: return f(std::integral_constant<int, STK_LINREG>());
+    case STK_LOGREG: return f(std::integral_constant<int, STK_LOGREG>());
+    case STK_POISSON: return f(std::integral_constant<int, STK_POISSON>());
+    case STK_NEGBIN: return f(std::integral_constant<int, STK_NEGBIN>());
+    case STK_STUDENT: return f(std::integral_constant<int, STK_STUDENT>());
+  }
+  return hipErrorInvalidValue;
+}
 
 }  // namespace stk
 
@@ -69,39 +83,30 @@ hipError_t stk_launch_sweep(int family, const stk::SweepLaunch& p, int shard0, i
 hipError_t stk_launch_sweep_reduce(int family, const stk::SweepLaunch& p, int shard0, int nsh, const stk::SweepCall& c,
                                    double* lp_out, double* g_out, hipStream_t st);
 
-// ---- sweep_pois.hip (sweep.hip's Poisson translation unit): the VALU sweeps, pass F and the reduce
-hipError_t stk_launch_sweep_poisson(const stk::SweepLaunch& p, const stk::SweepArgs& A, int nblocks, hipStream_t st);
-hipError_t stk_launch_gemm_fwd_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
-hipError_t stk_launch_sweep_reduce_poisson(const stk::SweepArgs& A, int nblocks_x, int nblocks_y, double* lp_out,
-                                           double* g_out, int C, hipStream_t st);
-// ---- sweep_nb.hip (sweep.hip's negative-binomial translation unit): the same, and its own reduce
-hipError_t stk_launch_sweep_negbin(const stk::SweepLaunch& p, const stk::SweepArgs& A, int nblocks, hipStream_t st);
-hipError_t stk_launch_gemm_fwd_negbin(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
-hipError_t stk_launch_sweep_reduce_negbin(const stk::SweepArgs& A, const stk::NbShardDev* nb, int nchains, int d,
-                                          double* lp_out, double* g_out, int C, hipStream_t st);
-// ---- sweep_st.hip (sweep.hip's student_t translation unit): the same three
-hipError_t stk_launch_sweep_student(const stk::SweepLaunch& p, const stk::SweepArgs& A, int nblocks, hipStream_t st);
-hipError_t stk_launch_gemm_fwd_student(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
-hipError_t stk_launch_sweep_reduce_student(const stk::SweepArgs& A, int nblocks_x, int nblocks_y, double* lp_out,
-                                           double* g_out, int C, hipStream_t st);
+// One launcher template per launch point, defined in its kernel file and instantiated in the object that
+// holds the family (STK_SWEEP_TU, sweep_common.h): k_sweep / k_sweep2 / k_sweep3, pass F of the 64-chain
+// sweep, and the reduce (only the negative binomial's reads nb).
+template <int FAM>
+hipError_t stk_launch_sweep_valu(const stk::SweepLaunch& p, const stk::SweepArgs& A, int nblocks, hipStream_t st);
+template <int FAM>
+hipError_t stk_launch_gemm_fwd(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
+template <int FAM>
+hipError_t stk_launch_reduce(const stk::SweepArgs& A, const stk::NbShardDev* nb, int nchains, int d, double* lp_out,
+                             double* g_out, int C, hipStream_t st);
 
 // ---- sweep16.hip: shapes k_sweep16 covers, its LDS bytes, its launch
 bool stk_sweep16_supported(int d);
 size_t stk_sweep16_lds_bytes(int family, int d);
-hipError_t stk_launch_sweep16(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
-hipError_t stk_launch_sweep16_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16_pois.hip
-hipError_t stk_launch_sweep16_negbin(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);    // sweep16_nb.hip
-hipError_t stk_launch_sweep16_student(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16_st.hip
+template <int FAM>
+hipError_t stk_launch_sweep16(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
 
 // ---- sweep16w.hip (128 < d <= 1024): waves per block, chunks per shard, LDS bytes, launch
 bool stk_sweep16w_supported(int d);
 int stk_sweep16w_waves(int d);
 int stk_sweep16w_chunks(int64_t n);
 size_t stk_sweep16w_lds_bytes(int family, int d);
-hipError_t stk_launch_sweep16w(int family, const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
-hipError_t stk_launch_sweep16w_poisson(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16w_pois.hip
-hipError_t stk_launch_sweep16w_negbin(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);    // sweep16w_nb.hip
-hipError_t stk_launch_sweep16w_student(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);   // sweep16w_st.hip
+template <int FAM>
+hipError_t stk_launch_sweep16w(const stk::SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st);
 
 // ---- hessian.hip (regressions, d <= 128): the analytic Hessian sweep's geometry and launch
 bool stk_hessian_supported(int d);

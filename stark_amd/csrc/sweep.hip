@@ -16,6 +16,9 @@
 // (logreg and poisson, int32 y) or n*(8d + 8) (linreg).  Each shard is cut into G chunks that depend
 // only on (n, d); per-chunk partial sums are reduced in chunk order by k_sweep_reduce, so
 // results are bitwise independent of how many shards share a GPU.
+//
+// The library compiles this file once per STK_SWEEP_TU (sweep_common.h): the base object and one object per
+// later family; a tool that includes it without the macro gets every family.
 #include "sweep_common.h"
 #include <math.h>
 #include <stdlib.h>
@@ -24,27 +27,7 @@
 #include <set>
 #include <type_traits>
 
-// A family's own translation unit (sweep_pois.hip, sweep_nb.hip) holds that family's instantiations
-// and launchers only: what is not a template is defined once, in sweep.hip itself.
-#if defined(STK_SWEEP_POISSON_TU) || defined(STK_SWEEP_NEGBIN_TU) || defined(STK_SWEEP_STUDENT_TU)
-#define STK_SWEEP_FAMILY_TU 1
-#endif
-
 namespace stk {
-
-// A family is a residual, not a kernel: every sweep takes FAM and must know it.
-template <int FAM>
-constexpr bool fam_known = FAM == STK_LINREG || FAM == STK_LOGREG || FAM == STK_POISSON || FAM == STK_NEGBIN || FAM == STK_STUDENT;
-template <int FAM>
-constexpr bool fam_yint = FAM == STK_LOGREG || FAM == STK_POISSON || FAM == STK_NEGBIN;   // y is the shard's int32 y_int
-// The scalar next to beta, q[d + 1], as the kernels carry it per chain in their inv_s slot: linear
-// 1 / sigma = exp(-u); negative binomial v = log phi itself, with phi = exp(v) kept beside it (once per
-// chain, not per element); student_t 1 / sigma as linear (its y is the shard's double y too; nu, nu + 1 and
-// 1 / nu are wave-uniform, read once from the shard's entry); the others have none.
-template <int FAM>
-constexpr bool fam_inv_sigma = FAM == STK_LINREG || FAM == STK_STUDENT;
-template <int FAM>
-constexpr bool fam_sum3 = FAM == STK_NEGBIN || FAM == STK_STUDENT;   // a third partial sum per chain, column d + 2
 
 template <int FAM, int C, int T, int JPT, int VEC>
 __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
@@ -72,10 +55,10 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
   if (tid < C) {
     const double* qc = A.q + chain_row(A, shard, tid) * A.Dp;
     Al[tid] = qc[0];
-    Al[C + tid] = fam_inv_sigma<FAM> ? exp(-qc[d + 1]) : (FAM == STK_NEGBIN) ? qc[d + 1] : 0.0;
+    Al[C + tid] = fam_inv_sigma(FAM) ? exp(-qc[d + 1]) : (FAM == STK_NEGBIN) ? qc[d + 1] : 0.0;
   }
   constexpr bool NB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
-  double nbphi[NB ? C : 1], ssa[fam_sum3<FAM> ? C : 1];   // negative binomial: phi_c, sum of sp; student_t: sum z^2 / (nu + z^2)
+  double nbphi[NB ? C : 1], ssa[fam_sum3(FAM) ? C : 1];   // negative binomial: phi_c, sum of sp; student_t: sum z^2 / (nu + z^2)
   if constexpr (NB) {
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -192,7 +175,7 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
           } else if constexpr (ST) {
             de = student_resid_libm(eta, gp(sh.y)[row], Al[C + c], nu, nu1, inv_nu, lpa[c], ssa[c]);
           } else {
-            static_assert(fam_known<FAM>, "k_sweep: unknown family");
+            static_assert(fam_known(FAM), "k_sweep: unknown family");
             const double is = Al[C + c];
             const double z = (gp(sh.y)[row] - eta) * is;
             lpa[c] += z * z;          // linreg: sum of squares, finished in the reduce
@@ -253,7 +236,7 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
     for (int i = 0; i < NT; ++i) v += src[i];
     out[(size_t)c * A.PW + (is_lp ? d + 1 : 0)] = v;
   }
-  if constexpr (fam_sum3<FAM>) {   // the third scalar sum, column d + 2, through the same area
+  if constexpr (fam_sum3(FAM)) {   // the third scalar sum, column d + 2, through the same area
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < C; ++c) red[(size_t)c * NT + tid] = ssa[c];
@@ -280,8 +263,8 @@ __global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_
   constexpr int T = 64, NT = 256, JPT = 2;
   constexpr int CP = (T * C + NT - 1) / NT;       // residual pairs per thread
   constexpr int NVMAX = (T * 128 / 2 + NT - 1) / NT;
-  static_assert(fam_known<FAM>, "k_sweep2: unknown family");
-  using yv_t = typename std::conditional<fam_yint<FAM>, int32_t, double>::type;
+  static_assert(fam_known(FAM), "k_sweep2: unknown family");
+  using yv_t = typename std::conditional<fam_yint(FAM), int32_t, double>::type;
   const int shard = A.shard0 + blockIdx.x / A.G;
   const int chunk = blockIdx.x % A.G;
   if (A.req_step && A.req_step[shard] != A.step_id - 1) return;
@@ -291,7 +274,7 @@ __global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_
   const int64_t r0 = sh.n * chunk / A.G, r1 = sh.n * (chunk + 1) / A.G;
   const cptr_t<double> qs = cp(A.q) + chain_row(A, shard) * A.Dp;   // chain c: (alpha, beta, [u])
   const gptr_t<double> X = gp(sh.x);
-  const gptr_t<yv_t> Y = (gptr_t<yv_t>)(fam_yint<FAM> ? (const void*)sh.yi : (const void*)sh.y);
+  const gptr_t<yv_t> Y = (gptr_t<yv_t>)(fam_yint(FAM) ? (const void*)sh.yi : (const void*)sh.y);
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* Xs = lds;                    // T * LD
@@ -304,10 +287,10 @@ __global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     alpha[c] = qs[(size_t)c * A.Dp];
-    inv_s[c] = fam_inv_sigma<FAM> ? exp(-qs[(size_t)c * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)c * A.Dp + d + 1] : 0.0;
+    inv_s[c] = fam_inv_sigma(FAM) ? exp(-qs[(size_t)c * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)c * A.Dp + d + 1] : 0.0;
   }
   constexpr bool NB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
-  double nbphi[NB ? C : 1], ssa[fam_sum3<FAM> ? CP : 1];   // negative binomial: phi_c; the third sum per residual pair
+  double nbphi[NB ? C : 1], ssa[fam_sum3(FAM) ? CP : 1];   // negative binomial: phi_c; the third sum per residual pair
   if constexpr (NB) {
 #pragma unroll
     for (int c = 0; c < C; ++c) nbphi[c] = exp(inv_s[c]);
@@ -481,7 +464,7 @@ __global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_
     for (int k = 0; k < 64; ++k) v += src[k];
     out[(size_t)c * A.PW + (kind == 0 ? d + 1 : 0)] = v;
   }
-  if constexpr (fam_sum3<FAM>) {   // the third scalar sum, column d + 2, through the same area
+  if constexpr (fam_sum3(FAM)) {   // the third scalar sum, column d + 2, through the same area
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < CP; ++i) red[(size_t)i * NT + tid] = ssa[i];
@@ -576,8 +559,8 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
   const int64_t t0 = nt * chunk / A.G, t1 = nt * (chunk + 1) / A.G;
   const int64_t r0 = t0 * T, r1 = std::min<int64_t>(sh.n, t1 * T);
   const int ntiles = (int)(t1 - t0);
-  static_assert(fam_known<FAM>, "k_sweep3: unknown family");
-  constexpr int YB = fam_yint<FAM> ? 4 : 8;         // y bytes per row
+  static_assert(fam_known(FAM), "k_sweep3: unknown family");
+  constexpr int YB = fam_yint(FAM) ? 4 : 8;         // y bytes per row
   const int SB = 8 * 16 * K;                        // X bytes of one wave's 8-row sub-tile
   const int SS = sweep3_slot_bytes(K);              // slot: X [0, SB), y [SB, SB + 8*YB)
 
@@ -600,7 +583,7 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
   }
   const int rc = fi < C ? fi : 0;                        // residual chain of this lane
   const double alpha = qs[(size_t)rc * A.Dp];
-  const double inv_s = fam_inv_sigma<FAM> ? exp(-qs[(size_t)rc * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)rc * A.Dp + d + 1] : 0.0;
+  const double inv_s = fam_inv_sigma(FAM) ? exp(-qs[(size_t)rc * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)rc * A.Dp + d + 1] : 0.0;
   constexpr bool NEGB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
   double nbphi = 0.0, ssa = 0.0;                          // negative binomial: phi of chain rc, sum of sp (student_t: of z^2 / (nu + z^2))
   if constexpr (NEGB) nbphi = exp(inv_s);
@@ -612,7 +595,7 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
   // nx 1-KiB X pieces (the last one partial) + one size-4 piece for y; buffer descriptors cover
   // exactly the chunk, so a partial last tile reads zeros past its end instead of faulting.
   const __amdgpu_buffer_rsrc_t xr = uniform_rsrc(sh.x + r0 * d, (r1 - r0) * d * 8);
-  const void* ybase = fam_yint<FAM> ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
+  const void* ybase = fam_yint(FAM) ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
   const __amdgpu_buffer_rsrc_t yr = uniform_rsrc(ybase, (r1 - r0) * YB);
   const int nx = (SB + 1023) >> 10;
   const int last_lanes = (SB - ((nx - 1) << 10)) >> 4;
@@ -758,7 +741,7 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
       for (int g = 0; g < 8; ++g) v += red2[(size_t)(ww * 64 + g * 8 + c) * 2 + kind];
     out[(size_t)c * A.PW + (kind == 0 ? d + 1 : 0)] = v;
   }
-  if constexpr (fam_sum3<FAM>) {   // the third scalar sum, column d + 2, through the same area
+  if constexpr (fam_sum3(FAM)) {   // the third scalar sum, column d + 2, through the same area
     __syncthreads();
     red2[(size_t)tid * 2] = ssa;
     __syncthreads();
@@ -797,8 +780,8 @@ __host__ __device__ inline int g5_kp(int d) { return (d + G5_KC - 1) / G5_KC * G
 __device__ __forceinline__ int g5_chain_off(int r, int c) { return r * 512 + ((((c >> 1) ^ ((r & 1) << 3))) << 4) + ((c & 1) << 3); }
 
 // beta^T images for pass F: qT[shard][k][.] = beta_c[k] (0 for k >= d), swizzled as g5_chain_off.
-// (Not a template: defined once, in sweep.hip itself.)
-#ifndef STK_SWEEP_FAMILY_TU
+// (Not a template: the base object's.)
+#ifdef STK_SWEEP_BASE
 __global__ __launch_bounds__(256) void k_qt_swizzle(SweepArgs A, int d) {
   const int shard = A.shard0 + blockIdx.y;
   if (A.req_step && A.req_step[shard] != A.step_id - 1) return;
@@ -852,7 +835,7 @@ __device__ __forceinline__ void dma16_lds(__amdgpu_buffer_rsrc_t r, char* dst, i
 // not fit beside the 128 accumulator and parked-eta registers at two blocks per CU: it runs one.  So does
 // student_t's, a full-range log1p and a reciprocal per element: at two blocks it spilt 33 VGPRs.)
 template <int FAM, int NW = G5_FW, int RT = 2, int KCF = G5_FKC, int NS = G5_FS, int SPLIT = 0>
-__global__ __launch_bounds__(64 * NW, (FAM == STK_NEGBIN || FAM == STK_STUDENT) ? 1 : 8 / NW) void k_gemm_fwd(SweepArgs A) {
+__global__ __launch_bounds__(64 * NW, fam_sum3(FAM) ? 1 : 8 / NW) void k_gemm_fwd(SweepArgs A) {
   constexpr int NCT = 4, TR = 16 * RT * NW;
   constexpr int XB = TR * KCF * 8, BB = KCF * 512, STG = XB + BB;
   constexpr int PPR = KCF / 2;                          // 16-B pieces per X row in the stage (8)
@@ -883,15 +866,15 @@ __global__ __launch_bounds__(64 * NW, (FAM == STK_NEGBIN || FAM == STK_STUDENT) 
   extern __shared__ __attribute__((aligned(16))) double lds[];
   char* const stg = reinterpret_cast<char*>(lds);      // NS stages of STG bytes
   double* const sptab = reinterpret_cast<double*>(stg + NS * STG);
-  static_assert(fam_known<FAM>, "k_gemm_fwd: unknown family");
-  if constexpr (FAM == STK_LOGREG || FAM == STK_POISSON || FAM == STK_NEGBIN) exp_table_init(sptab);
+  static_assert(fam_known(FAM), "k_gemm_fwd: unknown family");
+  if constexpr (fam_exp_table(FAM)) exp_table_init(sptab);
   // per-lane chain constants: chain 16 c2 + lr
   const double* qb = A.q + chain_row(A, shard) * A.Dp;
   double alpha[NCT], inv_s[NCT];
 #pragma unroll
   for (int c2 = 0; c2 < NCT; ++c2) {
     alpha[c2] = qb[(size_t)(16 * c2 + lr) * A.Dp];
-    inv_s[c2] = fam_inv_sigma<FAM> ? exp(-qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1])
+    inv_s[c2] = fam_inv_sigma(FAM) ? exp(-qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1])
                 : (FAM == STK_NEGBIN) ? qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1] : 0.0;
   }
   constexpr bool NB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
@@ -1088,7 +1071,7 @@ __global__ __launch_bounds__(64 * NW, (FAM == STK_NEGBIN || FAM == STK_STUDENT) 
       for (int h = 0; h < 4; ++h) v += red[((ww * 64 + h * 16 + l) * NCT + c2) * 2 + kind];
     A.partial[(((size_t)shard * A.Gs + chunk) * G5_C + c) * A.PW + (kind == 0 ? d + 1 : 0)] = v;
   }
-  if constexpr (fam_sum3<FAM>) {   // the third scalar sum, column d + 2, through the same area
+  if constexpr (fam_sum3(FAM)) {   // the third scalar sum, column d + 2, through the same area
     __syncthreads();
 #pragma unroll
     for (int c2 = 0; c2 < NCT; ++c2) red[((w * 64 + lane) * NCT + c2) * 2] = sp[c2];
@@ -1208,6 +1191,11 @@ __global__ __launch_bounds__(64 * G5_BW, 2) void k_gemm_bwd(SweepArgs A, int njb
         if (j < d) out[(size_t)(16 * c2 + lr) * A.PW + 1 + j] = acc[ct][c2][i];
       }
 }
+#ifdef STK_SWEEP_BASE   // no family's: the base object's, stated here so that its kernels come out in the file's order
+template __global__ void k_gemm_bwd<64>(SweepArgs, int);
+template __global__ void k_gemm_bwd<128>(SweepArgs, int);
+template __global__ void k_gemm_bwd<256>(SweepArgs, int);
+#endif
 
 // Sum chunk partials in chunk order and finish the family's lp / gradient.
 // grid (nshards*C, ceil(PW/64)), 1024 threads: 16 waves split the chunks (each sums its
@@ -1262,7 +1250,7 @@ __global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce(SweepArgs A, double*
       prior_lp = -0.5 * (sh.pa * qc[0] * qc[0] + sh.pb * sb);
     }
   }
-  static_assert(fam_known<FAM>, "k_sweep_reduce: unknown family");
+  static_assert(fam_known(FAM), "k_sweep_reduce: unknown family");
   if constexpr (FAM == STK_STUDENT) {
     // student_t (PW = d + 3): column d + 1 is sum log1p(z^2 / nu), column d + 2 is sum z^2 / (nu + z^2); with
     // sigma = exp(u) and its Jacobian, lp = -(nu + 1)/2 S1 - N u + u and d lp / d u = (nu + 1) S2 - N + 1
@@ -1297,8 +1285,10 @@ __global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce(SweepArgs A, double*
 //   lp      = S_lik + A1 + priors + v                                   (Jacobian of phi = e^v)
 //   d lp/dv = A2 - d alpha_lik - phi S_sp + (a - 1) - b phi + 1
 // with phi ~ gamma(a, b) adding (a - 1) v - b phi to lp.  phi = 0 or inf: lp and d lp/dv are NaN.
-#if defined(STK_SWEEP_NEGBIN_TU) || !defined(STK_POISSON_OWN_TU)
 constexpr int RDN_W = 8;   // 512 threads: the table terms' log / log1p want more registers than 16 waves leave
+__global__ __launch_bounds__(64 * RDN_W) void k_sweep_reduce_nb(SweepArgs A, const NbShardDev* nbs, double* lp_out,
+                                                               double* g_out, int C);
+#if !defined(STK_SWEEP_TU) || STK_SWEEP_TU == 5   // not a template either: the negative binomial's object's
 __global__ __launch_bounds__(64 * RDN_W) void k_sweep_reduce_nb(SweepArgs A, const NbShardDev* nbs, double* lp_out,
                                                                double* g_out, int C) {
   const int gidl = blockIdx.x;
@@ -1399,14 +1389,10 @@ __global__ __launch_bounds__(64 * RDN_W) void k_sweep_reduce_nb(SweepArgs A, con
 #include "launchers.h"
 using namespace stk;
 
-// (The negative binomial's follow the same rule in sweep_nb.hip, with STK_SWEEP_NEGBIN_TU.)
-// In the library (the Makefile's -DSTK_POISSON_OWN_TU) the Poisson instantiations of every kernel
-// above live in their own translation unit, sweep_pois.hip (this file with STK_SWEEP_POISSON_TU: the
-// launch templates below and the three stk_launch_*_poisson entry points), so this file's code
-// object holds the logistic and linear kernels it always did.  Built on its own, without either
-// macro -- the stand-alone tools under tools/ include this file as one translation unit -- it
-// defines the three entry points itself and links as before.
-#ifndef STK_SWEEP_FAMILY_TU
+// The library builds this file once per STK_SWEEP_TU (sweep_common.h): the planner and the dispatch on the
+// runtime family are the base object's; the launcher templates between them are instantiated for the
+// families the object holds, and those instantiations are what puts a family's kernels into it.
+#ifdef STK_SWEEP_BASE
 // The single-launch chain counts a sweep covers at d covariates (the batch sizes of the sampler).
 bool stk_sweep_supported(int C, int d) {
   if (C == G5_C) return d >= 1 && d <= 4096;
@@ -1522,13 +1508,15 @@ SweepWs stk_sweep_ws(void* base, const SweepLaunch& at_nmax, int nshards) {
   return w;
 }
 
+int stk::sweep_pw(int family, int d) { return d + (fam_sum3(family) ? 3 : 2); }
+
 static SweepArgs sweep_args(int family, const SweepLaunch& p, int shard0, const SweepCall& c, int LD) {
   SweepArgs A{c.shards, c.q, c.partial, c.req_step, c.step_id, p.C, c.Dp, p.G, LD, sweep_pw(family, p.d), shard0, c.Gs, c.ran};
   A.Ct = c.Ct;
   A.c0 = c.c0;
   return A;
 }
-#endif  // STK_SWEEP_FAMILY_TU
+#endif  // STK_SWEEP_BASE
 
 template <int FAM, int C, int T, int JPT>
 static hipError_t pick_vec(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
@@ -1567,10 +1555,9 @@ static hipError_t pick_tile(const SweepLaunch& p, const SweepArgs& A, int nblock
   return hipErrorInvalidValue;
 }
 
+// The VALU sweeps (kinds 1 - 3).
 template <int FAM>
-static hipError_t pick_c(const SweepLaunch& p, const SweepArgs& A, int nblocks, hipStream_t st) {
-  if (p.kind == SWEEP_16) return stk_launch_sweep16(FAM, A, p.d, nblocks, p.lds, st);
-  if (p.kind == SWEEP_16W) return stk_launch_sweep16w(FAM, A, p.d, nblocks, p.lds, st);
+hipError_t stk_launch_sweep_valu(const SweepLaunch& p, const SweepArgs& A, int nblocks, hipStream_t st) {
   if (p.kind < SWEEP_V1 || p.kind > SWEEP_V3) return hipErrorInvalidValue;
   switch (p.C) {
     case 1: return pick_tile<FAM, 1>(p, A, nblocks, st);
@@ -1580,106 +1567,67 @@ static hipError_t pick_c(const SweepLaunch& p, const SweepArgs& A, int nblocks, 
   }
   return hipErrorInvalidValue;
 }
+STK_SWEEP_INSTANTIATE(stk_launch_sweep_valu, const SweepLaunch&, const SweepArgs&, int, hipStream_t)
 
 // Pass F of the 64-chain sweep; the split stage schedule needs a tile's NKC = ceil(d / 16) stages to
 // hold its 8 epilogue parts.
 template <int FAM>
-static hipError_t launch_gemm_fwd(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+hipError_t stk_launch_gemm_fwd(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
   const bool split = (d + G5_FKC - 1) / G5_FKC >= 8;
   auto kf = split ? k_gemm_fwd<FAM, G5_FW, 2, G5_FKC, G5_FS, 1> : k_gemm_fwd<FAM>;
   if (const hipError_t e = allow_big_lds((const void*)kf)) return e;
   hipLaunchKernelGGL(kf, dim3(nblocks), dim3(64 * G5_FW), lds, st, A);
   return hipGetLastError();
 }
+STK_SWEEP_INSTANTIATE(stk_launch_gemm_fwd, const SweepArgs&, int, int, size_t, hipStream_t)
 
+// The reduce over `nchains` (shard, chain) pairs: k_sweep_reduce, one block per 64 of the PW columns, or the
+// negative binomial's own kernel and grid.
 template <int FAM>
-static hipError_t launch_reduce(const SweepArgs& A, dim3 grid, double* lp_out, double* g_out, int C, hipStream_t st) {
-  hipLaunchKernelGGL(k_sweep_reduce<FAM>, grid, dim3(64 * RD_W), 0, st, A, lp_out, g_out, C);
+hipError_t stk_launch_reduce(const SweepArgs& A, const NbShardDev* nb, int nchains, int d, double* lp_out, double* g_out,
+                             int C, hipStream_t st) {
+  if constexpr (FAM == STK_NEGBIN) {
+    if (!nb) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sweep_reduce_nb, dim3(nchains, (d + 1 + 63) / 64 + 1), dim3(64 * RDN_W), 0, st, A, nb, lp_out, g_out, C);
+  } else {
+    hipLaunchKernelGGL(k_sweep_reduce<FAM>, dim3(nchains, (A.PW + 63) / 64), dim3(64 * RD_W), 0, st, A, lp_out, g_out, C);
+  }
   return hipGetLastError();
 }
+STK_SWEEP_INSTANTIATE(stk_launch_reduce, const SweepArgs&, const NbShardDev*, int, int, double*, double*, int, hipStream_t)
 
-#if defined(STK_SWEEP_POISSON_TU) || !defined(STK_POISSON_OWN_TU)
-hipError_t stk_launch_sweep_poisson(const SweepLaunch& p, const SweepArgs& A, int nblocks, hipStream_t st) {
-  return pick_c<STK_POISSON>(p, A, nblocks, st);
-}
-hipError_t stk_launch_gemm_fwd_poisson(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  return launch_gemm_fwd<STK_POISSON>(A, d, nblocks, lds, st);
-}
-hipError_t stk_launch_sweep_reduce_poisson(const SweepArgs& A, int nblocks_x, int nblocks_y, double* lp_out, double* g_out,
-                                           int C, hipStream_t st) {
-  return launch_reduce<STK_POISSON>(A, dim3(nblocks_x, nblocks_y), lp_out, g_out, C, st);
-}
-#endif
-#if defined(STK_SWEEP_NEGBIN_TU) || !defined(STK_POISSON_OWN_TU)
-hipError_t stk_launch_sweep_negbin(const SweepLaunch& p, const SweepArgs& A, int nblocks, hipStream_t st) {
-  return pick_c<STK_NEGBIN>(p, A, nblocks, st);
-}
-hipError_t stk_launch_gemm_fwd_negbin(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  return launch_gemm_fwd<STK_NEGBIN>(A, d, nblocks, lds, st);
-}
-hipError_t stk_launch_sweep_reduce_negbin(const SweepArgs& A, const NbShardDev* nb, int nchains, int d, double* lp_out,
-                                          double* g_out, int C, hipStream_t st) {
-  if (!nb) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_sweep_reduce_nb, dim3(nchains, (d + 1 + 63) / 64 + 1), dim3(64 * RDN_W), 0, st, A, nb, lp_out, g_out, C);
-  return hipGetLastError();
-}
-#endif
-#if defined(STK_SWEEP_STUDENT_TU) || !defined(STK_POISSON_OWN_TU)   // sweep_st.hip, by the same rule
-hipError_t stk_launch_sweep_student(const SweepLaunch& p, const SweepArgs& A, int nblocks, hipStream_t st) {
-  return pick_c<STK_STUDENT>(p, A, nblocks, st);
-}
-hipError_t stk_launch_gemm_fwd_student(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  return launch_gemm_fwd<STK_STUDENT>(A, d, nblocks, lds, st);
-}
-hipError_t stk_launch_sweep_reduce_student(const SweepArgs& A, int nblocks_x, int nblocks_y, double* lp_out, double* g_out,
-                                           int C, hipStream_t st) {
-  return launch_reduce<STK_STUDENT>(A, dim3(nblocks_x, nblocks_y), lp_out, g_out, C, st);
-}
-#endif
-#ifndef STK_SWEEP_FAMILY_TU
+#ifdef STK_SWEEP_BASE
 // Launch the plan's sweep over `nsh` shards starting at shard0 (all of the plan's n) for the batch
 // of p.C chains that starts at chain c.c0 of every shard's c.Ct.
 hipError_t stk_launch_sweep(int family, const SweepLaunch& p, int shard0, int nsh, const SweepCall& c, hipStream_t st) {
-  if (family != STK_LOGREG && family != STK_LINREG && family != STK_POISSON && family != STK_NEGBIN && family != STK_STUDENT)
-    return hipErrorInvalidValue;
-  SweepArgs A = sweep_args(family, p, shard0, c, stk_sweep_args_ld(p));
-  const int nblocks = nsh * p.G, d = p.d;
-  if (p.kind == SWEEP_GEMM64) {
+  return sweep_family(family, [&](auto fam) -> hipError_t {
+    constexpr int FAM = decltype(fam)::value;
+    SweepArgs A = sweep_args(FAM, p, shard0, c, stk_sweep_args_ld(p));
+    const int nblocks = nsh * p.G, d = p.d;
+    if (p.kind == SWEEP_16) return stk_launch_sweep16<FAM>(A, d, nblocks, p.lds, st);
+    if (p.kind == SWEEP_16W) return stk_launch_sweep16w<FAM>(A, d, nblocks, p.lds, st);
+    if (p.kind != SWEEP_GEMM64) return stk_launch_sweep_valu<FAM>(p, A, nblocks, st);
     if (!c.ws || !c.ws->qT || !c.ws->R || c.ws->Rrows < p.Rrows) return hipErrorInvalidValue;
     A.qT = c.ws->qT;
     A.R = c.ws->R;
     A.Rrows = c.ws->Rrows;
     const int bjb = g5_bjb(d), njb = (d + bjb - 1) / bjb;
     hipLaunchKernelGGL(k_qt_swizzle, dim3((g5_kp(d) * G5_C + 255) / 256, nsh), dim3(256), 0, st, A, d);
-    const hipError_t ef = family == STK_LOGREG   ? launch_gemm_fwd<STK_LOGREG>(A, d, nblocks, p.lds, st)
-                          : family == STK_LINREG ? launch_gemm_fwd<STK_LINREG>(A, d, nblocks, p.lds, st)
-                          : family == STK_NEGBIN ? stk_launch_gemm_fwd_negbin(A, d, nblocks, p.lds, st)
-                          : family == STK_STUDENT ? stk_launch_gemm_fwd_student(A, d, nblocks, p.lds, st)
-                                                 : stk_launch_gemm_fwd_poisson(A, d, nblocks, p.lds, st);
-    if (ef != hipSuccess) return ef;
+    if (const hipError_t e = stk_launch_gemm_fwd<FAM>(A, d, nblocks, p.lds, st)) return e;
     auto kb = bjb == 64 ? k_gemm_bwd<64> : bjb == 128 ? k_gemm_bwd<128> : k_gemm_bwd<256>;
     if (const hipError_t e = allow_big_lds((const void*)kb)) return e;
     hipLaunchKernelGGL(kb, dim3(nblocks * njb), dim3(64 * G5_BW), G5_BNS * g5_bstage_bytes(bjb), st, A, njb);
     return hipGetLastError();
-  }
-  if (family == STK_LOGREG) return pick_c<STK_LOGREG>(p, A, nblocks, st);
-  if (family == STK_LINREG) return pick_c<STK_LINREG>(p, A, nblocks, st);
-  if (family == STK_NEGBIN) return stk_launch_sweep_negbin(p, A, nblocks, st);
-  if (family == STK_STUDENT) return stk_launch_sweep_student(p, A, nblocks, st);
-  return stk_launch_sweep_poisson(p, A, nblocks, st);
+  });
 }
 
 hipError_t stk_launch_sweep_reduce(int family, const SweepLaunch& p, int shard0, int nsh, const SweepCall& c,
                                    double* lp_out, double* g_out, hipStream_t st) {
-  SweepArgs A = sweep_args(family, p, shard0, c, 0);
-  A.ran = nullptr;
-  dim3 grid(nsh * p.C, (p.d + 2 + 63) / 64);
-  if (family == STK_LOGREG) return launch_reduce<STK_LOGREG>(A, grid, lp_out, g_out, p.C, st);
-  if (family == STK_LINREG) return launch_reduce<STK_LINREG>(A, grid, lp_out, g_out, p.C, st);
-  if (family == STK_POISSON) return stk_launch_sweep_reduce_poisson(A, grid.x, grid.y, lp_out, g_out, p.C, st);
-  if (family == STK_NEGBIN) return stk_launch_sweep_reduce_negbin(A, c.nb, nsh * p.C, p.d, lp_out, g_out, p.C, st);
-  if (family == STK_STUDENT)   // PW = d + 3 columns
-    return stk_launch_sweep_reduce_student(A, grid.x, (p.d + 3 + 63) / 64, lp_out, g_out, p.C, st);
-  return hipErrorInvalidValue;
+  return sweep_family(family, [&](auto fam) {
+    constexpr int FAM = decltype(fam)::value;
+    SweepArgs A = sweep_args(FAM, p, shard0, c, 0);
+    A.ran = nullptr;
+    return stk_launch_reduce<FAM>(A, c.nb, nsh * p.C, p.d, lp_out, g_out, p.C, st);
+  });
 }
-#endif  // STK_SWEEP_FAMILY_TU
+#endif  // STK_SWEEP_BASE

@@ -30,15 +30,12 @@
 //             FMAs instead of 4 mostly-padding MFMAs).
 // Chunk partials are summed in chunk order by k_sweep_reduce (sweep.hip): the gradient is
 // bitwise independent of how many shards share a launch or which GPU runs a shard.
+//
+// The library compiles this file once per STK_SWEEP_TU (sweep_common.h): the base object and one object per
+// later family; a tool that includes it without the macro gets every family.
 #include "sweep_common.h"
 #include <math.h>
 #include <algorithm>
-
-// A family's own translation unit (sweep16_pois.hip, sweep16_nb.hip) holds that family's instantiations and
-// launcher only.
-#if defined(STK_SWEEP16_POISSON_TU) || defined(STK_SWEEP16_NEGBIN_TU) || defined(STK_SWEEP16_STUDENT_TU)
-#define STK_SWEEP16_FAMILY_TU 1
-#endif
 
 namespace stk {
 
@@ -67,7 +64,7 @@ __host__ __device__ constexpr S16Geom s16_geom(int KF) {
 // Student-t has the linear layout but a residual of the negative binomial's weight (a full-range log1p and a
 // reciprocal per element): it takes the negative binomial's rule.
 __host__ __device__ constexpr bool s16_pre(int FAM, int KF) {
-  return FAM == STK_LINREG || KF <= ((FAM == STK_NEGBIN || FAM == STK_STUDENT) ? 25 : 27);
+  return FAM == STK_LINREG || KF <= (fam_sum3(FAM) ? 25 : 27);
 }
 constexpr int S16_FLUSH = 64;                   // sub-tiles between log1p flushes (4 elements each)
 
@@ -75,9 +72,9 @@ template <int FAM, int KF, bool PRE = s16_pre(FAM, KF), int NACC = 2>
 __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   constexpr S16Geom g = s16_geom(KF);
   constexpr int C = SM_C, NW = SM_W, JTM = g.JTM;
-  constexpr bool LOGI = FAM == STK_LOGREG, NB = FAM == STK_NEGBIN, POIS = FAM == STK_POISSON || NB;   // POIS: whole int32 counts
+  constexpr bool LOGI = FAM == STK_LOGREG, NB = FAM == STK_NEGBIN, POIS = fam_yint(FAM) && !LOGI;   // POIS: whole int32 counts
   constexpr bool ST = FAM == STK_STUDENT;                // the linear layout (double y, 1 / sigma per chain), its own residual
-  static_assert(LOGI || POIS || ST || FAM == STK_LINREG, "k_sweep16: unknown family");
+  static_assert(fam_known(FAM), "k_sweep16: unknown family");
   const int shard = A.shard0 + blockIdx.x / A.G;
   const int chunk = blockIdx.x % A.G;
   if (A.req_step && A.req_step[shard] != A.step_id - 1) return;
@@ -92,14 +89,14 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   const int nrows = (int)(r1 - r0);
   const int nsub = (nrows + SM_R - 1) / SM_R;
   const int mine = nsub > w ? (nsub - w + NW - 1) / NW : 0;   // own sub-tiles u = w + NW k
-  constexpr int YB = (LOGI || POIS) ? 4 : 8;       // int32 y (logistic, poisson) or double y
+  constexpr int YB = fam_yint(FAM) ? 4 : 8;        // int32 y (logistic, poisson) or double y
   const int SBX = SM_R * d * 8;
   const int SS = sweepm_slot_bytes(d);
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
   char* const slot = reinterpret_cast<char*>(lds) + (size_t)w * SS;
   double* const tab = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + (size_t)NW * SS);
-  if constexpr (LOGI || POIS) exp_table_init(tab);
+  if constexpr (fam_exp_table(FAM)) exp_table_init(tab);
   const double* qs = A.q + chain_row(A, shard) * A.Dp;
   double bf[KF];                   // beta_{lr} at the column k-step s of lane group lh takes (forward)
 #pragma unroll
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   }
   const double alpha = qs[(size_t)lr * A.Dp];
   // linear: 1 / sigma; negative binomial: v = log phi itself, with phi beside it (a lane is one chain)
-  const double inv_s = (FAM == STK_LINREG || ST) ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
+  const double inv_s = fam_inv_sigma(FAM) ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
   double nbphi = 0.0;
   if constexpr (NB) nbphi = exp(inv_s);
   double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;              // student_t: wave-uniform, read once
@@ -345,7 +342,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
       for (int h = 0; h < 4; ++h) v += red2[(size_t)(ww * 64 + h * 16 + c) * 2 + kind];
     out[(size_t)c * A.PW + (kind == 0 ? d + 1 : 0)] = v;
   }
-  if constexpr (NB || ST) {   // the third scalar sum (sp holds sum sp(t); student_t: sum z^2 / (nu + z^2)), column d + 2, through the same area
+  if constexpr (fam_sum3(FAM)) {   // the third scalar sum (sp holds sum sp(t); student_t: sum z^2 / (nu + z^2)), column d + 2, through the same area
     __syncthreads();
     red2[(size_t)tid * 2] = sp;
     __syncthreads();
@@ -363,13 +360,15 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
 #include "launchers.h"
 using namespace stk;
 
-#ifndef STK_SWEEP16_FAMILY_TU
+#ifdef STK_SWEEP_BASE
+bool stk_sweep16_supported(int d) { return d >= 1 && d <= 128; }
+
 // LDS bytes of k_sweep16 at d (the main loop's slots + table + remainder scratch, or the block
 // reduction's area, whichever is larger).
 size_t stk_sweep16_lds_bytes(int family, int d) {
   const int KF = (d + 3) / 4;
   const S16Geom g = s16_geom(KF);
-  size_t main = (size_t)SM_W * sweepm_slot_bytes(d) + ((family == STK_LINREG || family == STK_STUDENT) ? 0 : EX_TAB * 8);   // logistic, poisson: the exp table
+  size_t main = (size_t)SM_W * sweepm_slot_bytes(d) + (fam_exp_table(family) ? EX_TAB * 8 : 0);
   const size_t red = ((size_t)SM_W * g.JT * 16 * 16 + (size_t)SM_W * 64 * 2 + (size_t)SM_W * 4 * 4 * 16) * 8;
   return std::max(main, red);
 }
@@ -383,8 +382,9 @@ static hipError_t go16(const SweepArgs& A, int nblocks, size_t lds, hipStream_t 
   return hipGetLastError();
 }
 
+// Instantiated in the object that holds the family (STK_SWEEP_TU, sweep_common.h).
 template <int FAM>
-static hipError_t launch16(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+hipError_t stk_launch_sweep16(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
   switch ((d + 3) / 4) {
 #define S16_CASE(K) case K: return go16<FAM, K>(A, nblocks, lds, st);
     S16_CASE(1) S16_CASE(2) S16_CASE(3) S16_CASE(4) S16_CASE(5) S16_CASE(6) S16_CASE(7) S16_CASE(8)
@@ -395,35 +395,4 @@ static hipError_t launch16(const SweepArgs& A, int d, int nblocks, size_t lds, h
   }
   return hipErrorInvalidValue;
 }
-
-// In the library (-DSTK_POISSON_OWN_TU) the Poisson instantiations of k_sweep16 live in their own
-// translation unit, sweep16_pois.hip (this file with STK_SWEEP16_POISSON_TU), so the logistic and
-// linear ones compile as before; built on its own (the tools under tools/) this file defines the
-// Poisson launcher itself.
-#if defined(STK_SWEEP16_POISSON_TU) || !defined(STK_POISSON_OWN_TU)
-hipError_t stk_launch_sweep16_poisson(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  return launch16<STK_POISSON>(A, d, nblocks, lds, st);
-}
-#endif
-#if defined(STK_SWEEP16_NEGBIN_TU) || !defined(STK_POISSON_OWN_TU)   // sweep16_nb.hip, by the same rule
-hipError_t stk_launch_sweep16_negbin(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  return launch16<STK_NEGBIN>(A, d, nblocks, lds, st);
-}
-#endif
-#if defined(STK_SWEEP16_STUDENT_TU) || !defined(STK_POISSON_OWN_TU)   // sweep16_st.hip, by the same rule
-hipError_t stk_launch_sweep16_student(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  return launch16<STK_STUDENT>(A, d, nblocks, lds, st);
-}
-#endif
-#ifndef STK_SWEEP16_FAMILY_TU
-bool stk_sweep16_supported(int d) { return d >= 1 && d <= 128; }
-
-hipError_t stk_launch_sweep16(int family, const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  if (family == STK_LOGREG) return launch16<STK_LOGREG>(A, d, nblocks, lds, st);
-  if (family == STK_LINREG) return launch16<STK_LINREG>(A, d, nblocks, lds, st);
-  if (family == STK_POISSON) return stk_launch_sweep16_poisson(A, d, nblocks, lds, st);
-  if (family == STK_NEGBIN) return stk_launch_sweep16_negbin(A, d, nblocks, lds, st);
-  if (family == STK_STUDENT) return stk_launch_sweep16_student(A, d, nblocks, lds, st);
-  return hipErrorInvalidValue;
-}
-#endif
+STK_SWEEP_INSTANTIATE(stk_launch_sweep16, const SweepArgs&, int, int, size_t, hipStream_t)

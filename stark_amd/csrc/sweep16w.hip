@@ -28,15 +28,12 @@
 // A wave owns its columns over all the chunk's rows, so the chunk partial [chain][d + 2] is written
 // straight from the accumulators: no block reduction.  Chunks depend on (n, d) only and every sum
 // has a fixed order: the result is bitwise independent of the grid a shard is launched in.
+//
+// The library compiles this file once per STK_SWEEP_TU (sweep_common.h): the base object and one object per
+// later family; a tool that includes it without the macro gets every family.
 #include "sweep_common.h"
 #include <math.h>
 #include <algorithm>
-
-// A family's own translation unit (sweep16w_pois.hip, sweep16w_nb.hip) holds that family's instantiations and
-// launcher only.
-#if defined(STK_SWEEP16W_POISSON_TU) || defined(STK_SWEEP16W_NEGBIN_TU) || defined(STK_SWEEP16W_STUDENT_TU)
-#define STK_SWEEP16W_FAMILY_TU 1
-#endif
 
 namespace stk {
 
@@ -64,10 +61,10 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   constexpr int RSB = sw_row_bytes(DW), SLOTB = sw_slot_bytes(DW);
   constexpr int PPR = DW / 2 + 1;                   // 16-B pieces per padded row
   constexpr int NI = (SM_R * PPR + 63) / 64;        // DMA instructions per slot; the last one has 16 lanes
-  constexpr bool LOGI = FAM == STK_LOGREG, NB = FAM == STK_NEGBIN, POIS = FAM == STK_POISSON || NB;   // POIS: whole int32 counts
+  constexpr bool LOGI = FAM == STK_LOGREG, NB = FAM == STK_NEGBIN, POIS = fam_yint(FAM) && !LOGI;   // POIS: whole int32 counts
   constexpr bool ST = FAM == STK_STUDENT;           // the linear layout (double y, 1 / sigma per chain), its own residual
-  static_assert(LOGI || POIS || ST || FAM == STK_LINREG, "k_sweep16w: unknown family");
-  constexpr int YB = (LOGI || POIS) ? 4 : 8;        // int32 y (logistic, poisson) or double y
+  static_assert(fam_known(FAM), "k_sweep16w: unknown family");
+  constexpr int YB = fam_yint(FAM) ? 4 : 8;         // int32 y (logistic, poisson) or double y
   static_assert(KF % 4 == 0 && DW <= 128 && (SM_R * PPR) % 64 == 16, "slab geometry");
   const int NW = A.LD;                              // waves per block = column slabs
   const int shard = A.shard0 + blockIdx.x / A.G;
@@ -91,7 +88,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   char* const ybuf = reinterpret_cast<char*>(lds) + (size_t)NW * SLOTB;
   double* const exch = reinterpret_cast<double*>(ybuf + SW_YB);   // [NW][4 registers][64 lanes]
   double* const tab = exch + (size_t)NW * 256;
-  if constexpr (LOGI || POIS) exp_table_init(tab);
+  if constexpr (fam_exp_table(FAM)) exp_table_init(tab);
   const double* qs = A.q + chain_row(A, shard) * A.Dp;
   double bf[KF];                   // beta_{lr} at column j0 + lh KF + s (k-step s of lane group lh)
 #pragma unroll
@@ -101,7 +98,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   }
   const double alpha = w == 0 ? qs[(size_t)lr * A.Dp] : 0.0;   // wave 0's partial starts at alpha
   // linear: 1 / sigma; negative binomial: v = log phi itself, with phi beside it (a lane is one chain)
-  const double inv_s = (FAM == STK_LINREG || ST) ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
+  const double inv_s = fam_inv_sigma(FAM) ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
   double nbphi = 0.0;
   if constexpr (NB) nbphi = exp(inv_s);
   double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;              // student_t: wave-uniform, read once
@@ -271,7 +268,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
       out[d + 1] = lpa;
       out[0] = ga;
     }
-    if constexpr (NB || ST) {   // the third scalar sum (sp holds sum sp(t); student_t: sum z^2 / (nu + z^2)), column d + 2, joined the same way
+    if constexpr (fam_sum3(FAM)) {   // the third scalar sum (sp holds sum sp(t); student_t: sum z^2 / (nu + z^2)), column d + 2, joined the same way
       sp += __shfl_xor(sp, 16);
       sp += __shfl_xor(sp, 32);
       if (lh == 0) out[d + 2] = sp;
@@ -284,7 +281,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
 #include "launchers.h"
 using namespace stk;
 
-#ifndef STK_SWEEP16W_FAMILY_TU
+#ifdef STK_SWEEP_BASE
 bool stk_sweep16w_supported(int d) { return d > 128 && d <= 128 * SW_MAXW; }
 int stk_sweep16w_waves(int d) { return sw_waves(d); }
 int stk_sweep16w_chunks(int64_t n) {                  // >= SW_TILES tiles of 64 rows per chunk
@@ -293,8 +290,7 @@ int stk_sweep16w_chunks(int64_t n) {                  // >= SW_TILES tiles of 64
 }
 size_t stk_sweep16w_lds_bytes(int family, int d) {
   const int nw = sw_waves(d);
-  return (size_t)nw * sw_slot_bytes(sw_slab(d)) + SW_YB + (size_t)nw * 256 * 8 +
-         ((family == STK_LINREG || family == STK_STUDENT) ? 0 : EX_TAB * 8);   // logistic, poisson: the exp table
+  return (size_t)nw * sw_slot_bytes(sw_slab(d)) + SW_YB + (size_t)nw * 256 * 8 + (fam_exp_table(family) ? EX_TAB * 8 : 0);
 }
 #endif
 
@@ -306,8 +302,11 @@ static hipError_t go16w(const SweepArgs& A, int nblocks, size_t lds, hipStream_t
   return hipGetLastError();
 }
 
+// Instantiated in the object that holds the family (STK_SWEEP_TU, sweep_common.h).
 template <int FAM>
-static hipError_t launch16w(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+hipError_t stk_launch_sweep16w(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
+  if (!stk_sweep16w_supported(d) || A.LD != sw_waves(d) || lds < stk_sweep16w_lds_bytes(FAM, d) || lds > BIG_LDS_BYTES)
+    return hipErrorInvalidValue;
   switch (sw_slab(d) / 4) {
     case 20: return go16w<FAM, 20>(A, nblocks, lds, st);
     case 24: return go16w<FAM, 24>(A, nblocks, lds, st);
@@ -316,35 +315,4 @@ static hipError_t launch16w(const SweepArgs& A, int d, int nblocks, size_t lds, 
   }
   return hipErrorInvalidValue;
 }
-
-// In the library (-DSTK_POISSON_OWN_TU) the Poisson instantiations of k_sweep16w live in their own
-// translation unit, sweep16w_pois.hip (this file with STK_SWEEP16W_POISSON_TU), so the logistic and
-// linear ones compile as before; built on its own (the tools under tools/) this file defines the
-// Poisson launcher itself.
-#if defined(STK_SWEEP16W_POISSON_TU) || !defined(STK_POISSON_OWN_TU)
-hipError_t stk_launch_sweep16w_poisson(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  return launch16w<STK_POISSON>(A, d, nblocks, lds, st);   // the caller (stk_launch_sweep16w) checked the shape
-}
-#endif
-#if defined(STK_SWEEP16W_NEGBIN_TU) || !defined(STK_POISSON_OWN_TU)   // sweep16w_nb.hip, by the same rule
-hipError_t stk_launch_sweep16w_negbin(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  return launch16w<STK_NEGBIN>(A, d, nblocks, lds, st);
-}
-#endif
-#if defined(STK_SWEEP16W_STUDENT_TU) || !defined(STK_POISSON_OWN_TU)   // sweep16w_st.hip, by the same rule
-hipError_t stk_launch_sweep16w_student(const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  return launch16w<STK_STUDENT>(A, d, nblocks, lds, st);
-}
-#endif
-#ifndef STK_SWEEP16W_FAMILY_TU
-hipError_t stk_launch_sweep16w(int family, const SweepArgs& A, int d, int nblocks, size_t lds, hipStream_t st) {
-  if (!stk_sweep16w_supported(d) || A.LD != sw_waves(d) || lds < stk_sweep16w_lds_bytes(family, d) || lds > BIG_LDS_BYTES)
-    return hipErrorInvalidValue;
-  if (family == STK_LOGREG) return launch16w<STK_LOGREG>(A, d, nblocks, lds, st);
-  if (family == STK_LINREG) return launch16w<STK_LINREG>(A, d, nblocks, lds, st);
-  if (family == STK_POISSON) return stk_launch_sweep16w_poisson(A, d, nblocks, lds, st);
-  if (family == STK_NEGBIN) return stk_launch_sweep16w_negbin(A, d, nblocks, lds, st);
-  if (family == STK_STUDENT) return stk_launch_sweep16w_student(A, d, nblocks, lds, st);
-  return hipErrorInvalidValue;
-}
-#endif
+STK_SWEEP_INSTANTIATE(stk_launch_sweep16w, const SweepArgs&, int, int, size_t, hipStream_t)

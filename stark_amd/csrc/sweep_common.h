@@ -7,7 +7,55 @@
 #include "negbin_math.h"
 #include "student_math.h"
 
+// Which families' instantiations of the sweep kernels a translation unit of sweep.hip, sweep16.hip or
+// sweep16w.hip holds.  Undefined: every family, instantiated implicitly where it is
+// used -- a stand-alone tool that includes the kernel files as one translation unit.  The library's
+// Makefile compiles each kernel file four times: -DSTK_SWEEP_TU=0 is the base object (what is not a
+// template, and the logistic and linear families), 4, 5 and 6 hold the Poisson, negative-binomial and
+// Student-t families alone, so that a new family leaves the others' code objects as they were.  The
+// preprocessor cannot read the STK_* enumerators, hence the numbers.
+#ifdef STK_SWEEP_TU
+static_assert(STK_POISSON == 4 && STK_NEGBIN == 5 && STK_STUDENT == 6, "the Makefile's -DSTK_SWEEP_TU ids are the family ids");
+static_assert(STK_SWEEP_TU == 0 || STK_SWEEP_TU == STK_POISSON || STK_SWEEP_TU == STK_NEGBIN || STK_SWEEP_TU == STK_STUDENT,
+              "STK_SWEEP_TU: 0 or a family with an object of its own");
+#endif
+#if !defined(STK_SWEEP_TU) || STK_SWEEP_TU == 0
+#define STK_SWEEP_BASE 1   // this translation unit defines what is not a template
+#endif
+// After the definition of a launcher template `template <int FAM> hipError_t F(...)` (declared in
+// launchers.h): F's instantiations in this translation unit, its parameter types as the arguments.  The
+// base object declares the other families' `extern`, so that its dispatch finds them at link time and
+// instantiates none of their kernels.
+#if !defined(STK_SWEEP_TU)
+#define STK_SWEEP_INSTANTIATE(F, ...)
+#elif STK_SWEEP_TU == 0
+#define STK_SWEEP_INSTANTIATE(F, ...)                          \
+  template hipError_t F<STK_LOGREG>(__VA_ARGS__);              \
+  template hipError_t F<STK_LINREG>(__VA_ARGS__);              \
+  extern template hipError_t F<STK_POISSON>(__VA_ARGS__);      \
+  extern template hipError_t F<STK_NEGBIN>(__VA_ARGS__);       \
+  extern template hipError_t F<STK_STUDENT>(__VA_ARGS__);
+#else
+#define STK_SWEEP_INSTANTIATE(F, ...) template hipError_t F<STK_SWEEP_TU>(__VA_ARGS__);
+#endif
+
 namespace stk {
+
+// A family is a residual, not a kernel: every sweep takes FAM and must know it.  What the kernels and
+// their launchers ask about a family, in one place:
+__host__ __device__ constexpr bool fam_known(int f) {
+  return f == STK_LINREG || f == STK_LOGREG || f == STK_POISSON || f == STK_NEGBIN || f == STK_STUDENT;
+}
+__host__ __device__ constexpr bool fam_yint(int f) { return f == STK_LOGREG || f == STK_POISSON || f == STK_NEGBIN; }   // y is the shard's int32 y_int
+// The scalar next to beta, q[d + 1], as the kernels carry it per chain in their inv_s slot: linear
+// 1 / sigma = exp(-u); negative binomial v = log phi itself, with phi = exp(v) kept beside it (once per
+// chain, not per element); student_t 1 / sigma as linear (its y is the shard's double y too; nu, nu + 1 and
+// 1 / nu are wave-uniform, read once from the shard's entry); the others have none.
+__host__ __device__ constexpr bool fam_inv_sigma(int f) { return f == STK_LINREG || f == STK_STUDENT; }
+// A third partial sum per chain, column d + 2: the negative binomial's unweighted sum of sp(t), student_t's
+// sum of z^2 / (nu + z^2).  Their residuals are also the heavy ones (a log1p and a reciprocal per element).
+__host__ __device__ constexpr bool fam_sum3(int f) { return f == STK_NEGBIN || f == STK_STUDENT; }
+__host__ __device__ constexpr bool fam_exp_table(int f) { return fam_yint(f); }   // the MFMA sweeps keep the exp table in LDS
 
 typedef double dbl2 __attribute__((ext_vector_type(2)));   // loads from any address space
 

@@ -9,7 +9,7 @@ read with llvm-readelf and the instructions with llvm-objdump.  A kernel present
 "same" when the four figures, the instruction count and a hash of the instruction text (mnemonics and
 operands, in order; addresses and encodings left out) all agree.  Needs no GPU.  The answer to "did
 a change that adds instantiations in translation units of their own leave the existing kernels
-alone" -- e.g. the Poisson family's sweep_pois.hip / sweep16_pois.hip / sweep16w_pois.hip.
+alone" -- e.g. the Poisson family's sweep_pois.o / sweep16_pois.o / sweep16w_pois.o (-DSTK_SWEEP_TU=4).
 """
 import argparse
 import hashlib

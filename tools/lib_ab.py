@@ -11,8 +11,8 @@ each workload reports whether the arms' results are bit-identical.
              sweep16lin  the same at configs[2]'s shape (linear, 8 x 1.25e6 rows, d = 50)
              fulldata  tools/bench_fulldata.py --steps 6 (configs[4] at 1e7 rows): pass F + B ms
 
-usage: tools/lib_ab.py build NAME [--rev REV] [--flags FILE=FLAGS ...]   (here; -> tools/_bin/ab_NAME; no
-       --flags: the tree's Makefile)
+usage: tools/lib_ab.py build NAME [--rev REV] [--flags FILE=FLAGS ...]   (here; -> tools/_bin/ab_NAME, by the
+       tree's or the revision's Makefile, FLAGS in place of its own for FILE)
        tools/lib_ab.py run --arms A,B[,C] --work schools|sweep16|fulldata [--rounds R]   (GPU box)"""
 import argparse
 import json
@@ -22,15 +22,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "tools", "_bin")
-BASE_FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fvisibility=hidden"]
-
-
-def makefile_srcs(csrc):
-    """The library's sources: the SRCS line of the Makefile beside them (the tree's or the revision's)."""
-    for ln in open(os.path.join(csrc, "Makefile")):
-        if ln.startswith("SRCS :="):
-            return ln.split(":=", 1)[1].split()
-    sys.exit(f"no SRCS line in {csrc}/Makefile")
 
 
 def build(name, rev=None, flags=()):
@@ -45,27 +36,16 @@ def build(name, rev=None, flags=()):
                              capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", src], input=tar, check=True)
         csrc = os.path.join(src, "stark_amd", "csrc")
-    extra = {}
-    for f in flags:
-        k, v = f.split("=", 1)
-        extra[k] = v.split()
-    if not extra:        # the tree's own Makefile (its per-file flags)
-        subprocess.run(["make", "-s", "-j8", "-C", csrc, f"OUT={out}"], check=True)
-        json.dump({"rev": rev or "working tree", "flags": "Makefile"}, open(os.path.join(out, "arm.json"), "w"))
-        print("built", os.path.join(out, "libstark_hip.so"), "with the Makefile")
-        return
-    procs, objs = [], []
-    for s in makefile_srcs(csrc):
-        o = os.path.join(out, s.replace(".hip", ".o"))
-        objs.append(o)
-        procs.append(subprocess.Popen(["/opt/rocm/bin/hipcc", *BASE_FLAGS, *extra.get(s, []), "-c",
-                                       os.path.join(csrc, s), "-o", o]))
-    if any(p.wait() for p in procs):
-        sys.exit("build failed")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-shared", "--offload-arch=gfx950", "-o",
-                    os.path.join(out, "libstark_hip.so"), *objs], check=True)
-    json.dump({"rev": rev or "working tree", "flags": extra}, open(os.path.join(out, "arm.json"), "w"))
-    print("built", os.path.join(out, "libstark_hip.so"), extra)
+    # the one build recipe is the Makefile's: FILE=FLAGS becomes its per-file FLAGS_FILE, for every object built
+    # from FILE; where the compiler fails with them make falls back to the default flags and says so, which an
+    # arm that asked for flags must not do
+    extra = dict(f.split("=", 1) for f in flags)
+    p = subprocess.run(["make", "-s", "-j8", "-C", csrc, f"OUT={out}", *[f"FLAGS_{k}={v}" for k, v in extra.items()]],
+                       stdout=subprocess.PIPE, text=True)
+    if p.returncode or (extra and "failed, default flags" in p.stdout):
+        sys.exit("build failed:\n" + "\n".join(ln for ln in p.stdout.splitlines() if "failed" in ln))
+    json.dump({"rev": rev or "working tree", "flags": extra or "Makefile"}, open(os.path.join(out, "arm.json"), "w"))
+    print("built", os.path.join(out, "libstark_hip.so"), extra or "with the Makefile")
 
 
 def one(arm, work):

@@ -3,6 +3,7 @@
 // drift hits every arm, plus parity of every arm against round 3's product kernel (k_sweepe,
 // residual v3) after the chunk reduction.
 // Build: hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/sweep16_ab.hip -o tools/_bin/sweep16_ab
+// (no -DSTK_SWEEP_TU: the kernel files instantiate every family where it is used)
 // Run:   tools/_bin/sweep16_ab [rows_per_shard] [shards] [rounds] [reps] [d] [family 3=logistic 2=linear]
 #include "../stark_amd/csrc/sweep.hip"
 #include "sweep_variants.hip"

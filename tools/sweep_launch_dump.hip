@@ -6,6 +6,7 @@
 // means to alter routing; any other change must reproduce it byte for byte:
 //   hipcc -O1 --offload-arch=gfx950 -std=c++17 tools/sweep_launch_dump.hip -o tools/_bin/sweep_launch_dump
 //   tools/_bin/sweep_launch_dump | cmp - tests/golden/sweep_launch.json
+// (No -DSTK_SWEEP_TU: the three kernel files are one translation unit here, every family instantiated where used.)
 #include "../stark_amd/csrc/sweep.hip"
 #include "../stark_amd/csrc/sweep16.hip"
 #include "../stark_amd/csrc/sweep16w.hip"

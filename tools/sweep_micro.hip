@@ -6,6 +6,7 @@
 //   sweep    the product kernel (stk_launch_sweep, variant per STARK_SWEEP=1|2|3 / shape), all
 //            shards in one launch.
 // Build: hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/sweep_micro.hip -o tools/_bin/sweep_micro
+// (no -DSTK_SWEEP_TU: sweep.hip instantiates every family where it is used)
 // Run:   tools/_bin/sweep_micro [rows_per_shard] [shards] [d] [reps]
 #include "../stark_amd/csrc/sweep.hip"
 #include "sweep_variants.hip"
