@@ -88,7 +88,7 @@ enum {
 };
 
 /* Model families. */
-enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEGBIN = 5, STK_STUDENT = 6 };
+enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEGBIN = 5, STK_STUDENT = 6, STK_GAMMA = 7 };
 /* STK_POISSON: y ~ poisson_log(alpha + x * beta), the unconstrained parameters (alpha, beta[1..d]) in
  * the logistic layout (D = d + 1, P = d + 2: alpha, beta, lp__).  With eta_i = alpha + x_i . beta and
  * mu_i = exp(eta_i), lp = sum_i (y_i eta_i - mu_i) (+ the normal(0, s) prior terms of
@@ -148,6 +148,32 @@ enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEG
  * name with STK_E_ARG, before any work: stk_model_create_synthetic, stk_sampler_set_allreduce and the analysis
  * sweeps (stk_log_density_hessian, stk_log_predictive, stk_loo, stk_log_density_draws,
  * stk_log_density_grad_boot, stk_posterior_predict). */
+/* STK_GAMMA: y ~ gamma(shape, shape ./ exp(alpha + x * beta)), the gamma GLM with the log link (mean exp(eta),
+ * variance mean^2 / shape), the unconstrained parameters (alpha, beta[1..d], u = log shape) in the linear layout
+ * with shape where sigma is (D = d + 2, P = d + 3: alpha, beta, shape = e^u, lp__) and the shard's double y, every
+ * value finite and > 0 (stk_model_create returns STK_E_ARG and names the first row that is not).  With a = e^u,
+ * n rows, eta_i = alpha + x_i . beta, ly_i = log y_i, L = sum_i ly_i and t_i = ly_i - eta_i, the `~` statement's
+ * density on the unconstrained scale is
+ *   lp             = n kappa(a) - L - a H + u       (+ the priors of stk_model_set_prior / stk_model_set_prior_shape)
+ *   kappa(a)       = a log a - a - lgamma(a)
+ *   H              = sum_i h(t_i),   h(t) = e^t - 1 - t >= 0
+ *   d lp / d eta_i = a (e^{t_i} - 1)                -> d alpha = sum_i, d beta = X^T (.)
+ *   d lp / d u     = a [n kappa'(a) - H] + 1,       kappa'(a) = log a - psi(a)
+ * (the last u and + 1: the Jacobian of shape = e^u).  This is Stan's gamma_lpdf(y | a, a e^-eta) term for term:
+ * shape is a parameter, so nothing is dropped, (a - 1) log y with its -log y part included.  It is written as a
+ * deviance because the textbook form n (a log a - lgamma a) + (a - 1) L - a sum_i (eta_i + y_i e^-eta_i) cancels
+ * a n against a L and loses lp's last digits on precise data (shape 1e4 and up).  The library therefore keeps, next
+ * to y as given (what stk_model_copy_data returns and the fingerprints cover), ly = log y as the array its sweeps
+ * read, and L summed once in a fixed order.  kappa and kappa' are never formed from lgamma(a) or digamma(a) (at
+ * a = 1e8 kappa is 8, left over from terms of 1.8e9): csrc/gamma_math.h sums their Stirling remainders, by a
+ * recurrence below a = 16; stk_gamma_shape_terms_host runs the same code on the host.
+ * Where e^t overflows a double lp is -inf or NaN, never +inf and never a finite number; a NaN eta or u stays NaN;
+ * a = 0 or inf (exp(u) under- or overflowed) gives NaN.
+ * The sampler (any chains, the three metrics, both U-turn criteria, saved states: the family and the shape prior
+ * are part of a saved state's geometry), the gradient hooks, stk_model_set_prior, data copy-out and the
+ * fingerprints treat the family as they treat STK_LINREG.  Refused by name with STK_E_ARG, before any work:
+ * stk_model_create_synthetic, stk_sampler_set_allreduce and the analysis sweeps (stk_log_density_hessian,
+ * stk_log_predictive, stk_loo, stk_log_density_draws, stk_log_density_grad_boot, stk_posterior_predict). */
 
 /* One data shard (= one Spark partition, stark/stark.py:35).
  *   schools: n_rows = J, y[J], sigma[J]                   (example/stark_ex.py:8-11)
@@ -158,7 +184,8 @@ enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEG
  *            handed over as doubles as well as ints are refused (STK_E_ARG), here and by
  *            stk_shard_fingerprint_host, instead of one of the two being ignored
  *   negbin : as poisson (x, y_int >= 0, y and sigma NULL)
- *   student: as linreg (x, y)                                                        */
+ *   student: as linreg (x, y)
+ *   gamma  : as linreg (x, y), every y finite and > 0                                */
 typedef struct {
   int64_t n_rows;
   int32_t n_cols;
@@ -271,6 +298,14 @@ STK_API int stk_model_set_prior(stk_model* m, double alpha_scale, double beta_sc
 /* STK_NEGBIN only: phi ~ gamma(shape, rate), which adds (shape - 1) v - rate e^v to lp (exponential(r)
  * is gamma(1, r)).  shape > 0, rate >= 0; (1, 0) is flat, the default.  Every shard, before sampling. */
 STK_API int stk_model_set_prior_phi(stk_model* m, double shape, double rate);
+/* STK_GAMMA only: shape ~ gamma(shape, rate), which adds (shape - 1) u - rate e^u to lp (exponential(r) is
+ * gamma(1, r)).  shape > 0, rate >= 0; (1, 0) is flat, the default.  Any other family is refused by name.
+ * Every shard, before sampling. */
+STK_API int stk_model_set_prior_shape(stk_model* m, double shape, double rate);
+/* The shape-only terms of STK_GAMMA at shape a, by the code the device runs: out2[0] = kappa(a) =
+ * a log a - a - lgamma(a), out2[1] = kappa'(a) = log a - psi(a) > 0.  a = 0, inf or NaN gives NaN for both.
+ * No device is touched. */
+STK_API int stk_gamma_shape_terms_host(double a, double* out2);
 /* STK_STUDENT only: the degrees of freedom nu of y ~ student_t(nu, ., sigma), finite and > 0 (else STK_E_ARG
  * with the value in the message; any other family is refused by name).  Required before any density,
  * transition or sampler call: there is no default.  Every shard, before sampling. */
@@ -304,9 +339,9 @@ STK_API int stk_model_device_bytes(const stk_model* m, int64_t* bytes);
  * reduction order gives the same bits.
  *
  *   shard fingerprint = fmix( words([family, n_rows, n_cols], 0, 0)     n_cols = 0 for schools; family is
- *                                                                        the STK_* value (poisson: 4, negbin: 5, student: 6)
+ *                                                                        the STK_* value (poisson: 4, negbin: 5, student: 6, gamma: 7)
  *                           + words(x: n_rows * n_cols doubles, row-major, 1, 0)   regressions
- *                           + words(y doubles, 2, 0)                    linreg, student, schools
+ *                           + words(y doubles, 2, 0)                    linreg, student, gamma, schools
  *                           + words(y_int int32, 3, 0)                  logreg, poisson, negbin
  *                           + words(sigma doubles, 4, 0) )              schools
  *

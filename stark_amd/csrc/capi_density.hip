@@ -54,7 +54,7 @@ int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int
 // Every batch's sweep over every shard group; then (plan_reduces) every batch's reduction.  `run`
 // holds the run's buffers; a batch's partial-sum region, stride and first chain are filled in here.
 static SweepCall batch_call(const stk_model* m, const ChainPlan& cp, const ChainBatch& b, SweepCall c) {
-  c.nb = m->nb_dev.as<NbShardDev>();   // NULL but for the negative binomial, whose reduce reads it
+  c.nb = m->nb_dev.as<NbShardDev>();   // NULL but for the negative binomial and the gamma family, whose reduces read it
   c.partial += b.part_off;
   c.Gs = b.Gs;
   c.Ct = cp.Ct;

@@ -95,6 +95,7 @@ struct stk_model {
   std::vector<DevBuf> bufs;
   DevBuf sh_dev;
   std::vector<NbShardDev> nb;   // STK_NEGBIN: per shard, the count table (in bufs) and the phi prior; derived data
+                                // (STK_GAMMA: per shard, L = sum log y (in bufs) and the shape prior)
   DevBuf nb_dev;                // its device copy, what the reduce reads
   double nu = 0.0;              // STK_STUDENT: the degrees of freedom (0: not set yet); every shard's ShardDev carries a copy
   int64_t bytes = 0;
@@ -170,7 +171,7 @@ bool is_device_ptr(const void* p, int device);
 // ---- capi_model.hip
 const char* family_name(int family);
 bool is_regression(int family);     // linear, logistic, poisson: every regression entry point
-bool is_sweep_family(int family);   // those, neg_binomial and student_t: the gradient sweeps, the sampler, the priors
+bool is_sweep_family(int family);   // those, neg_binomial, student_t and gamma: the gradient sweeps, the sampler, the priors
 int model_ready(const stk_model* m);   // STK_E_ARG for a student_t model whose nu has not been set (no hidden default)
 void model_release(stk_model* m);
 int model_fingerprint(stk_model* m, int shard, uint64_t* out);   // cached

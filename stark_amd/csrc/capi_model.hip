@@ -1,6 +1,7 @@
 // C ABI of libstark_hip.so: models -- creation from host rows or the generator, info, priors, data
 // copy-out -- and the data fingerprints.
 #include "capi_internal.h"
+#include "gamma_math.h"
 
 const char* family_name(int family) {
   switch (family) {
@@ -10,14 +11,17 @@ const char* family_name(int family) {
     case STK_POISSON: return "poisson";
     case STK_NEGBIN: return "neg_binomial";
     case STK_STUDENT: return "student_t";
+    case STK_GAMMA: return "gamma";
   }
   return "unknown";
 }
 
 // The families every regression entry point serves (the analysis sweeps among them)...
 bool is_regression(int family) { return family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON; }
-// ...and those the gradient sweeps, the sampler and the priors serve: the negative binomial and Student-t too.
-bool is_sweep_family(int family) { return is_regression(family) || family == STK_NEGBIN || family == STK_STUDENT; }
+// ...and those the gradient sweeps, the sampler and the priors serve: the negative binomial, Student-t and gamma too.
+bool is_sweep_family(int family) {
+  return is_regression(family) || family == STK_NEGBIN || family == STK_STUDENT || family == STK_GAMMA;
+}
 
 int model_ready(const stk_model* m) {
   ARG_CHECK(m->family != STK_STUDENT || m->nu > 0.0,
@@ -39,6 +43,7 @@ static int family_dims(int family, int64_t n, int d, int* D, int* P) {
     case STK_POISSON: *D = d + 1; *P = d + 2; return STK_OK;   // the logistic layout: alpha, beta, lp__
     case STK_NEGBIN: *D = d + 2; *P = d + 3; return STK_OK;    // the linear layout: alpha, beta, phi (v = log phi), lp__
     case STK_STUDENT: *D = d + 2; *P = d + 3; return STK_OK;   // the linear layout itself: alpha, beta, sigma (s = log sigma), lp__
+    case STK_GAMMA: *D = d + 2; *P = d + 3; return STK_OK;     // the linear layout: alpha, beta, shape (u = log shape), lp__
   }
   stk_set_error("unknown model family %d", family);
   return STK_E_ARG;
@@ -62,7 +67,7 @@ static int upload_shard_table(stk_model* m) {
     m->Dmax = std::max(m->Dmax, s.D);
     m->Pmax = std::max(m->Pmax, s.P);
   }
-  if (m->family == STK_NEGBIN) RC(upload_nb_table(m));
+  if (m->family == STK_NEGBIN || m->family == STK_GAMMA) RC(upload_nb_table(m));
   RC(m->sh_dev.ensure(sizeof(ShardDev) * m->sh.size()));
   STK_HIP_CHECK(hipMemcpyAsync(m->sh_dev.p, m->sh.data(), sizeof(ShardDev) * m->sh.size(), hipMemcpyHostToDevice,
                                m->ctx->stream));
@@ -70,7 +75,8 @@ static int upload_shard_table(stk_model* m) {
   return STK_OK;
 }
 
-// The model's [nshards] NbShardDev (count tables and phi priors) to the device; again after a prior changes.
+// The model's [nshards] NbShardDev (count tables and phi priors; gamma: sum log y and the shape prior) to the
+// device; again after a prior changes.
 static int upload_nb_table(stk_model* m) {
   RC(m->nb_dev.ensure(sizeof(NbShardDev) * m->nb.size()));
   STK_HIP_CHECK(hipMemcpyAsync(m->nb_dev.p, m->nb.data(), sizeof(NbShardDev) * m->nb.size(), hipMemcpyHostToDevice,
@@ -169,6 +175,40 @@ static int attach_nb_table(stk_model* m, const int32_t* yi_dev, int64_t n) {
   return STK_OK;
 }
 
+// Sum of x[0 .. n) by halves down to runs of 8: a fixed order, the same bits on every run, error O(log n) ulp.
+static double pairwise_sum(const double* x, int64_t n) {
+  if (n <= 8) {
+    double s = 0.0;
+    for (int64_t i = 0; i < n; ++i) s += x[i];
+    return s;
+  }
+  const int64_t h = n / 2;
+  return pairwise_sum(x, h) + pairwise_sum(x + h, n - h);
+}
+
+// A gamma shard's derived data from its device copy of y: every y finite and > 0 (the first bad row is named),
+// ly = log y as the array the sweeps read (*ly_dev; the shard keeps y itself for copy-out and the fingerprint)
+// and L = sum ly in the shard's NbShardDev entry.
+static int attach_gamma_data(stk_model* m, int s, const double* y_dev, int64_t n, const double** ly_dev) {
+  std::vector<double> y((size_t)n);
+  STK_HIP_CHECK(hipMemcpyAsync(y.data(), y_dev, sizeof(double) * n, hipMemcpyDeviceToHost, m->ctx->stream));
+  STK_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  for (int64_t i = 0; i < n; ++i) {
+    ARG_CHECK(std::isfinite(y[i]) && y[i] > 0.0, "shard %d: y[%lld] = %g; gamma needs y finite and > 0", s, (long long)i, y[i]);
+    y[i] = log(y[i]);
+  }
+  const double L = pairwise_sum(y.data(), n);
+  NbShardDev gm{};
+  int rc = upload(m, y.data(), (size_t)n, ly_dev);
+  if (rc == STK_OK) rc = upload(m, &L, 1, &gm.tab);
+  // y and L are locals: whatever the uploads' outcome, a copy that was started must have read them before they go
+  const hipError_t e = hipStreamSynchronize(m->ctx->stream);
+  RC(rc);
+  STK_HIP_CHECK(e);
+  m->nb.push_back(gm);
+  return STK_OK;
+}
+
 // Shard s of a model from the caller's rows: validated, copied to the device, appended to m->sh.
 static int upload_shard(stk_model* m, int s, const stk_shard& in) {
   const int family = m->family;
@@ -197,9 +237,11 @@ static int upload_shard(stk_model* m, int s, const stk_shard& in) {
       RC(check_y_int(m, s, sd.yi, in.n_rows, pois, family == STK_NEGBIN ? "neg_binomial_2_log needs y >= 0" : "poisson_log needs y >= 0"));
       if (family == STK_NEGBIN) RC(attach_nb_table(m, sd.yi, in.n_rows));
     } else {   // family_dims knows every family: a new one must say here which y it takes
-      ARG_CHECK(family == STK_LINREG || family == STK_STUDENT, "shard %d: model family %d has no data layout", s, family);
-      ARG_CHECK(in.y, "shard %d: %s needs y", s, family == STK_STUDENT ? "student_t" : "linreg");
+      ARG_CHECK(family == STK_LINREG || family == STK_STUDENT || family == STK_GAMMA, "shard %d: model family %d has no data layout", s,
+                family);
+      ARG_CHECK(in.y, "shard %d: %s needs y", s, family == STK_STUDENT ? "student_t" : family == STK_GAMMA ? "gamma" : "linreg");
       RC(upload(m, in.y, n, &sd.y));
+      if (family == STK_GAMMA) RC(attach_gamma_data(m, s, sd.y, in.n_rows, &sd.sigma));   // sigma carries ly = log y (common.h)
     }
   }
   m->sh.push_back(sd);
@@ -388,6 +430,26 @@ int stk_model_set_prior_phi(stk_model* m, double shape, double rate) {
   return upload_nb_table(m);
 }
 
+int stk_model_set_prior_shape(stk_model* m, double shape, double rate) {
+  ARG_CHECK(m, "stk_model_set_prior_shape: NULL model");
+  ARG_CHECK(m->family == STK_GAMMA, "stk_model_set_prior_shape: a prior on shape is for the gamma family, not for the %s family (%d)",
+            family_name(m->family), m->family);
+  ARG_CHECK(shape > 0.0 && std::isfinite(shape) && rate >= 0.0 && std::isfinite(rate),
+            "stk_model_set_prior_shape: shape ~ gamma(shape, rate) needs shape > 0 and rate >= 0 (1, 0: flat), got (%g, %g)", shape, rate);
+  for (auto& gm : m->nb) {
+    gm.pr_a1 = shape - 1.0;
+    gm.pr_b = rate;
+  }
+  STK_HIP_CHECK(hipSetDevice(m->ctx->device));
+  return upload_nb_table(m);
+}
+
+int stk_gamma_shape_terms_host(double a, double* out2) {
+  ARG_CHECK(out2, "stk_gamma_shape_terms_host: out2 is NULL");
+  gamma_shape_terms(a, out2);
+  return STK_OK;
+}
+
 int stk_model_set_student_nu(stk_model* m, double nu) {
   ARG_CHECK(m, "stk_model_set_student_nu: NULL model");
   ARG_CHECK(m->family == STK_STUDENT, "stk_model_set_student_nu: nu is for the student_t family, not for the %s family (%d)",
@@ -475,7 +537,7 @@ int stk_fingerprint_words(stk_ctx* ctx, const void* buf, int64_t count, int32_t 
 int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
   ARG_CHECK(sh && out, "stk_shard_fingerprint_host: bad arguments");
   ARG_CHECK(family == STK_SCHOOLS || family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN ||
-                family == STK_STUDENT,
+                family == STK_STUDENT || family == STK_GAMMA,
             "unknown model family %d", family);
   ARG_CHECK(sh->n_rows > 0, "stk_shard_fingerprint_host: n_rows must be positive");
   uint64_t acc = fp_shard_header(family, sh->n_rows, sh->n_cols);
@@ -492,7 +554,8 @@ int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
                 "stk_shard_fingerprint_host: %s takes its counts in y_int alone; y and sigma must be NULL", fam);
       acc += stk_fp_words_host(sh->y_int, sh->n_rows, 4, 3, 0);
     } else {
-      ARG_CHECK(sh->y, "stk_shard_fingerprint_host: %s needs y", family == STK_STUDENT ? "student_t" : "linreg");
+      ARG_CHECK(sh->y, "stk_shard_fingerprint_host: %s needs y",
+                family == STK_STUDENT ? "student_t" : family == STK_GAMMA ? "gamma" : "linreg");
       acc += stk_fp_words_host(sh->y, sh->n_rows, 8, 2, 0);
     }
   }

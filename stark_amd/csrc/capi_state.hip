@@ -27,7 +27,7 @@ int state_geometry(const stk_sampler* s, uint64_t* out) {
   Fnv f;
   f.add(m->family), f.add(m->nshards), f.add(m->d), f.add(m->Dmax), f.add(m->Pmax);
   for (const auto& sd : m->sh) f.add(sd.n), f.add(sd.D), f.add(sd.P), f.add(sd.pa), f.add(sd.pb);
-  for (const auto& nb : m->nb) f.add(nb.pr_a1), f.add(nb.pr_b);   // negative binomial: the phi prior (no other family has entries)
+  for (const auto& nb : m->nb) f.add(nb.pr_a1), f.add(nb.pr_b);   // negative binomial: the phi prior; gamma: the shape prior (no other family has entries)
   if (m->family == STK_STUDENT) f.add(m->nu);                       // student_t alone: a state saved at nu = 4 is not one for nu = 5
   f.add(A.nchains), f.add(A.C), f.add(A.Dp), f.add(A.max_depth), f.add(A.num_warmup), f.add(A.num_samples);
   f.add(A.adapt), f.add(A.var_on), f.add(A.skip_ss), f.add(A.iter_offset);

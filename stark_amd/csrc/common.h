@@ -46,7 +46,7 @@ struct ShardDev {
   const double* x;      // n x d row-major (regressions)
   const double* y;      // schools y / linreg y
   const int32_t* yi;    // logreg y
-  const double* sigma;  // schools sigma; student_t: the bits of nu (shard_nu below)
+  const double* sigma;  // schools sigma; student_t: the bits of nu (shard_nu below); gamma: ly = log y, the sweeps' stream
   int64_t n;            // rows (J for schools)
   int d;                // covariates
   int D;                // unconstrained dimension

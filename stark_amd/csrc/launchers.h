@@ -49,7 +49,8 @@ struct SweepCall {
   int Dp;
   int Gs;                 // partial-sum stride in chunks per shard: the largest G of the batch's groups
   int Ct, c0;             // chains per shard in q / lp / grad, first chain of this batch
-  const NbShardDev* nb = nullptr;   // STK_NEGBIN: the model's [nshards] count tables and phi priors (the reduce reads them)
+  const NbShardDev* nb = nullptr;   // STK_NEGBIN: the model's [nshards] count tables and phi priors (the reduce reads them);
+                                    // STK_GAMMA: the shards' L = sum log y and the shape prior, in the same entries
 };
 
 // Columns of a chunk's partial row per chain: d alpha, d beta[1..d], the lp sum -- and the family's third
@@ -57,7 +58,7 @@ struct SweepCall {
 int sweep_pw(int family, int d);
 
 // The one place a runtime family id becomes a template argument: f(std::integral_constant<int, FAM>) for
-// the five regression families, hipErrorInvalidValue for anything else.
+// the six regression families, hipErrorInvalidValue for anything else.
 template <class F>
 hipError_t sweep_family(int family, F&& f) {
   switch (family) {
@@ -66,6 +67,7 @@ hipError_t sweep_family(int family, F&& f) {
     case STK_POISSON: return f(std::integral_constant<int, STK_POISSON>());
     case STK_NEGBIN: return f(std::integral_constant<int, STK_NEGBIN>());
     case STK_STUDENT: return f(std::integral_constant<int, STK_STUDENT>());
+    case STK_GAMMA: return f(std::integral_constant<int, STK_GAMMA>());
   }
   return hipErrorInvalidValue;
 }
@@ -85,7 +87,7 @@ hipError_t stk_launch_sweep_reduce(int family, const stk::SweepLaunch& p, int sh
 
 // One launcher template per launch point, defined in its kernel file and instantiated in the object that
 // holds the family (STK_SWEEP_TU, sweep_common.h): k_sweep / k_sweep2 / k_sweep3, pass F of the 64-chain
-// sweep, and the reduce (only the negative binomial's reads nb).
+// sweep, and the reduce (only the negative binomial's and the gamma family's read nb).
 template <int FAM>
 hipError_t stk_launch_sweep_valu(const stk::SweepLaunch& p, const stk::SweepArgs& A, int nblocks, hipStream_t st);
 template <int FAM>

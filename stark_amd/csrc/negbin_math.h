@@ -34,6 +34,8 @@ namespace stk {
 constexpr int NB_CAP = 1024;     // tail counts are kept for j < NB_CAP
 
 // What a negative-binomial shard adds to its ShardDev: derived data, built once at model creation.
+// (The gamma family, STK_GAMMA, keeps its shard's one derived number in the same entry: tab points at a single
+// double, L = sum_i log y_i, ncap = nbig = 0, and pr_a1, pr_b are the shape's gamma prior.)
 struct NbShardDev {
   const double* tab;   // [ncap] T_j, then [nbig][2]: (value, multiplicity) of the distinct counts > NB_CAP
   int ncap;            // min(max y, NB_CAP)

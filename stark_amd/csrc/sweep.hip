@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
   if (tid < C) {
     const double* qc = A.q + chain_row(A, shard, tid) * A.Dp;
     Al[tid] = qc[0];
-    Al[C + tid] = fam_inv_sigma(FAM) ? exp(-qc[d + 1]) : (FAM == STK_NEGBIN) ? qc[d + 1] : 0.0;
+    Al[C + tid] = fam_chain_scalar<FAM>(qc[d + 1]);
   }
   constexpr bool NB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
   double nbphi[NB ? C : 1], ssa[fam_sum3(FAM) ? C : 1];   // negative binomial: phi_c, sum of sp; student_t: sum z^2 / (nu + z^2)
@@ -174,6 +174,8 @@ __global__ __launch_bounds__(256) void k_sweep(SweepArgs A) {
             de = negbin_resid_libm(eta, (double)gp(sh.yi)[row], Al[C + c], nbphi[c], lpa[c], ssa[c]);
           } else if constexpr (ST) {
             de = student_resid_libm(eta, gp(sh.y)[row], Al[C + c], nu, nu1, inv_nu, lpa[c], ssa[c]);
+          } else if constexpr (FAM == STK_GAMMA) {
+            de = gamma_resid_libm(eta, gp(sh.sigma)[row], Al[C + c], lpa[c]);
           } else {
             static_assert(fam_known(FAM), "k_sweep: unknown family");
             const double is = Al[C + c];
@@ -274,7 +276,7 @@ __global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_
   const int64_t r0 = sh.n * chunk / A.G, r1 = sh.n * (chunk + 1) / A.G;
   const cptr_t<double> qs = cp(A.q) + chain_row(A, shard) * A.Dp;   // chain c: (alpha, beta, [u])
   const gptr_t<double> X = gp(sh.x);
-  const gptr_t<yv_t> Y = (gptr_t<yv_t>)(fam_yint(FAM) ? (const void*)sh.yi : (const void*)sh.y);
+  const gptr_t<yv_t> Y = (gptr_t<yv_t>)(fam_yint(FAM) ? (const void*)sh.yi : (const void*)fam_ydouble<FAM>(sh));
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* Xs = lds;                    // T * LD
@@ -287,7 +289,7 @@ __global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     alpha[c] = qs[(size_t)c * A.Dp];
-    inv_s[c] = fam_inv_sigma(FAM) ? exp(-qs[(size_t)c * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)c * A.Dp + d + 1] : 0.0;
+    inv_s[c] = fam_chain_scalar<FAM>(qs[(size_t)c * A.Dp + d + 1]);
   }
   constexpr bool NB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
   double nbphi[NB ? C : 1], ssa[fam_sum3(FAM) ? CP : 1];   // negative binomial: phi_c; the third sum per residual pair
@@ -402,6 +404,8 @@ __global__ __launch_bounds__(256, (FAM == STK_NEGBIN && C == 8) ? 1 : 2) void k_
             de = negbin_resid_libm(eta, (double)ycur, is, ph, lpa[i], ssa[i]);
           } else if constexpr (ST) {
             de = student_resid_libm(eta, ycur, is, nu, nu1, inv_nu, lpa[i], ssa[i]);
+          } else if constexpr (FAM == STK_GAMMA) {
+            de = gamma_resid_libm(eta, ycur, is, lpa[i]);
           } else {
             const double z = (ycur - eta) * is;
             lpa[i] += z * z;
@@ -583,7 +587,7 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
   }
   const int rc = fi < C ? fi : 0;                        // residual chain of this lane
   const double alpha = qs[(size_t)rc * A.Dp];
-  const double inv_s = fam_inv_sigma(FAM) ? exp(-qs[(size_t)rc * A.Dp + d + 1]) : (FAM == STK_NEGBIN) ? qs[(size_t)rc * A.Dp + d + 1] : 0.0;
+  const double inv_s = fam_chain_scalar<FAM>(qs[(size_t)rc * A.Dp + d + 1]);
   constexpr bool NEGB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
   double nbphi = 0.0, ssa = 0.0;                          // negative binomial: phi of chain rc, sum of sp (student_t: of z^2 / (nu + z^2))
   if constexpr (NEGB) nbphi = exp(inv_s);
@@ -595,7 +599,7 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
   // nx 1-KiB X pieces (the last one partial) + one size-4 piece for y; buffer descriptors cover
   // exactly the chunk, so a partial last tile reads zeros past its end instead of faulting.
   const __amdgpu_buffer_rsrc_t xr = uniform_rsrc(sh.x + r0 * d, (r1 - r0) * d * 8);
-  const void* ybase = fam_yint(FAM) ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
+  const void* ybase = fam_yint(FAM) ? (const void*)(sh.yi + r0) : (const void*)(fam_ydouble<FAM>(sh) + r0);
   const __amdgpu_buffer_rsrc_t yr = uniform_rsrc(ybase, (r1 - r0) * YB);
   const int nx = (SB + 1023) >> 10;
   const int last_lanes = (SB - ((nx - 1) << 10)) >> 4;
@@ -678,6 +682,8 @@ __global__ __launch_bounds__(512) void k_sweep3(SweepArgs A, int NBrt) {
           de = negbin_resid_libm(eta, (double)*reinterpret_cast<const int32_t*>(ys + frow * 4), inv_s, nbphi, lpa, ssa);
         } else if constexpr (ST) {
           de = student_resid_libm(eta, *reinterpret_cast<const double*>(ys + frow * 8), inv_s, nu, nu1, inv_nu, lpa, ssa);
+        } else if constexpr (FAM == STK_GAMMA) {
+          de = gamma_resid_libm(eta, *reinterpret_cast<const double*>(ys + frow * 8), inv_s, lpa);
         } else {
           const double yv = *reinterpret_cast<const double*>(ys + frow * 8);
           const double z = (yv - eta) * inv_s;
@@ -874,8 +880,7 @@ __global__ __launch_bounds__(64 * NW, fam_sum3(FAM) ? 1 : 8 / NW) void k_gemm_fw
 #pragma unroll
   for (int c2 = 0; c2 < NCT; ++c2) {
     alpha[c2] = qb[(size_t)(16 * c2 + lr) * A.Dp];
-    inv_s[c2] = fam_inv_sigma(FAM) ? exp(-qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1])
-                : (FAM == STK_NEGBIN) ? qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1] : 0.0;
+    inv_s[c2] = fam_chain_scalar<FAM>(qb[(size_t)(16 * c2 + lr) * A.Dp + d + 1]);
   }
   constexpr bool NB = FAM == STK_NEGBIN, ST = FAM == STK_STUDENT;
   double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;            // student_t: wave-uniform, read once
@@ -909,7 +914,7 @@ __global__ __launch_bounds__(64 * NW, fam_sum3(FAM) ? 1 : 8 / NW) void k_gemm_fw
   // per chain tile: logistic lm = sum(t - |t|) - 2 sum(flushed log1p(sp)), sp = prod(1 + e) - 1
   // (residual v4, sweep_common.h); linear: lm = sum z^2; poisson: lm = sum (y eta - mu), the lp itself;
   // negative binomial: lm = sum (y eta - (y + phi) sp(t)) and sp = sum sp(t);
-  // student_t: lm = sum log1p(z^2 / nu) and sp = sum z^2 / (nu + z^2)
+  // student_t: lm = sum log1p(z^2 / nu) and sp = sum z^2 / (nu + z^2); gamma: lm = sum h(ly - eta)
   double lm[NCT], sp[NCT], gaa[NCT];
 #pragma unroll
   for (int c2 = 0; c2 < NCT; ++c2) lm[c2] = sp[c2] = gaa[c2] = 0.0;
@@ -949,6 +954,10 @@ __global__ __launch_bounds__(64 * NW, fam_sum3(FAM) ? 1 : 8 / NW) void k_gemm_fw
         dv = student_resid(eta, pyt[rt][i], inv_s[c2], nu, nu1, inv_nu, lm2, sp2);
         lm[c2] = valid ? lm2 : lm[c2];
         sp[c2] = valid ? sp2 : sp[c2];
+      } else if constexpr (FAM == STK_GAMMA) {
+        double lm2 = lm[c2];
+        dv = gamma_resid(eta, pyt[rt][i], inv_s[c2], sptab, lm2);
+        lm[c2] = valid ? lm2 : lm[c2];
       } else {
         const double z = (pyt[rt][i] - eta) * inv_s[c2];
         lm[c2] += valid ? z * z : 0.0;
@@ -991,7 +1000,7 @@ __global__ __launch_bounds__(64 * NW, fam_sum3(FAM) ? 1 : 8 / NW) void k_gemm_fw
           const int64_t grow = (int64_t)(st / NKC) * TR + 16 * RT * w + 16 * rt + lh + 4 * i;
           if constexpr (FAM == STK_LOGREG) ybit |= (grow < nrows ? (uint32_t)sh.yi[r0 + grow] & 1u : 0u) << (4 * rt + i);
           else if constexpr (FAM == STK_POISSON || NB) yc[rt][i] = grow < nrows ? sh.yi[r0 + grow] : 0;
-          else yt[rt][i] = grow < nrows ? sh.y[r0 + grow] : 0.0;
+          else yt[rt][i] = grow < nrows ? fam_ydouble<FAM>(sh)[r0 + grow] : 0.0;
         }
     }
     if (st + NS - 1 < nst) issue(st + NS - 1);
@@ -1203,6 +1212,33 @@ template __global__ void k_gemm_bwd<256>(SweepArgs, int);
 // order -- a fixed order that depends only on G.  (At one shard per GPU the 4-wave form was a
 // chain of 32 dependent load batches per wave: 19 us per step.)
 constexpr int RD_W = 16;
+// Wave w's share of column o of chain c's chunk partials: its contiguous range of the G chunks, summed in order,
+// 8 loads in flight.
+template <int W>
+__device__ __forceinline__ double reduce_chunk_range(const SweepArgs& A, int shard, int c, int C, int o, int w) {
+  const int per = (A.G + W - 1) / W;
+  const int k0 = w * per, k1 = min(A.G, k0 + per);
+  const double* src = A.partial + ((size_t)shard * A.Gs * C + c) * A.PW + o;
+  const size_t stride = (size_t)C * A.PW;
+  double v = 0.0;
+  int k = k0;
+  for (; k + 8 <= k1; k += 8) {
+    double a[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = src[(size_t)(k + i) * stride];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v += a[i];
+  }
+  for (; k < k1; ++k) v += src[(size_t)k * stride];
+  return v;
+}
+// The normal(0, s) priors' term of lp at the chain's point: -(pa alpha^2 + pb |beta|^2) / 2, 0 when both are flat.
+__device__ __forceinline__ double normal_prior_lp(const ShardDev& sh, const double* qc, int d) {
+  if (sh.pa == 0.0 && sh.pb == 0.0) return 0.0;
+  double sb = 0.0;
+  for (int j = 1; j <= d; ++j) sb = fma(qc[j], qc[j], sb);
+  return -0.5 * (sh.pa * qc[0] * qc[0] + sh.pb * sb);
+}
 template <int FAM>
 __global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce(SweepArgs A, double* lp_out, double* g_out, int C) {
   const int gidl = blockIdx.x;              // local chain index in this launch
@@ -1381,6 +1417,51 @@ __global__ __launch_bounds__(64 * RDN_W) void k_sweep_reduce_nb(SweepArgs A, con
   const double gv = ((a2 - t[0]) - phi * t[2]) + (nb.pr_a1 - nb.pr_b * phi) + 1.0;
   lp_out[gid] = ok ? lp : nan;
   g[d + 1] = ok ? gv : nan;
+}
+#endif
+
+// The gamma family's reduce: k_sweep_reduce's grid and chunk sums (reduce_chunk_range: the same order) and the normal
+// priors (PW = d + 2: the family has no third sum), then the family's finish from H = sum h(t), the lp column, alone.  With a = exp(u), N rows and the
+// shard's L = sum log y (gms[shard].tab[0], summed once at model creation),
+//   lp      = N kappa(a) - L - a H + u + (pr_a1 u - pr_b a)                     (Jacobian of shape = e^u)
+//   d lp/du = a (N kappa'(a) - H) + 1 + (pr_a1 - pr_b a)
+// with shape ~ gamma(s, r) adding (s - 1) u - r a.  kappa and kappa' (gamma_math.h) are computed here, once per
+// (shard, chain), by the one thread that owns the column.  a = 0, a = inf or a NaN u: both are NaN.
+__global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce_gm(SweepArgs A, const NbShardDev* gms, double* lp_out,
+                                                              double* g_out, int C);
+#if !defined(STK_SWEEP_TU) || STK_SWEEP_TU == 7   // the gamma family's object's
+__global__ __launch_bounds__(64 * RD_W) void k_sweep_reduce_gm(SweepArgs A, const NbShardDev* gms, double* lp_out,
+                                                              double* g_out, int C) {
+  const int gidl = blockIdx.x;
+  const int shard = A.shard0 + gidl / C, c = gidl % C;
+  if (A.req_step && A.req_step[shard] != A.step_id - 1) return;
+  const ShardDev sh = A.shards[shard];
+  const int d = sh.d;
+  const int o = blockIdx.y * 64 + (threadIdx.x & 63);
+  const int w = threadIdx.x >> 6;
+  __shared__ double part[RD_W][64];
+  part[w][threadIdx.x & 63] = o < A.PW ? reduce_chunk_range<RD_W>(A, shard, c, C, o, w) : 0.0;
+  __syncthreads();
+  if (w != 0 || o >= A.PW) return;
+  double t = part[0][threadIdx.x];
+#pragma unroll
+  for (int i = 1; i < RD_W; ++i) t += part[i][threadIdx.x];
+  const size_t gid = chain_row(A, shard, c);
+  double* g = g_out + gid * A.Dp;
+  const double* qc = A.q + gid * A.Dp;
+  if (o == 0) {
+    g[0] = t - sh.pa * qc[0];                          // flat: the precision is 0 (a non-finite q is NaN either way)
+  } else if (o <= d) {
+    g[o] = t - sh.pb * qc[o];
+  } else {                                             // o == d + 1: H
+    const double prior_lp = normal_prior_lp(sh, qc, d);
+    const NbShardDev gm = gms[shard];
+    const double u = qc[d + 1], a = exp(u), N = (double)sh.n;
+    double kt[2];
+    gamma_shape_terms(a, kt);
+    lp_out[gid] = ((((N * kt[0] - gm.tab[0]) - a * t) + prior_lp) + (gm.pr_a1 * u - gm.pr_b * a)) + u;
+    g[d + 1] = (a * (N * kt[1] - t) + (gm.pr_a1 - gm.pr_b * a)) + 1.0;
+  }
 }
 #endif
 
@@ -1582,13 +1663,16 @@ hipError_t stk_launch_gemm_fwd(const SweepArgs& A, int d, int nblocks, size_t ld
 STK_SWEEP_INSTANTIATE(stk_launch_gemm_fwd, const SweepArgs&, int, int, size_t, hipStream_t)
 
 // The reduce over `nchains` (shard, chain) pairs: k_sweep_reduce, one block per 64 of the PW columns, or the
-// negative binomial's own kernel and grid.
+// negative binomial's own kernel and grid, or the gamma family's own kernel on k_sweep_reduce's grid.
 template <int FAM>
 hipError_t stk_launch_reduce(const SweepArgs& A, const NbShardDev* nb, int nchains, int d, double* lp_out, double* g_out,
                              int C, hipStream_t st) {
   if constexpr (FAM == STK_NEGBIN) {
     if (!nb) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_sweep_reduce_nb, dim3(nchains, (d + 1 + 63) / 64 + 1), dim3(64 * RDN_W), 0, st, A, nb, lp_out, g_out, C);
+  } else if constexpr (FAM == STK_GAMMA) {   // nb: the shards' L = sum log y and the shape prior
+    if (!nb) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sweep_reduce_gm, dim3(nchains, (A.PW + 63) / 64), dim3(64 * RD_W), 0, st, A, nb, lp_out, g_out, C);
   } else {
     hipLaunchKernelGGL(k_sweep_reduce<FAM>, dim3(nchains, (A.PW + 63) / 64), dim3(64 * RD_W), 0, st, A, lp_out, g_out, C);
   }

@@ -63,6 +63,10 @@ __host__ __device__ constexpr S16Geom s16_geom(int KF) {
 // The negative binomial's residual is the heaviest (a log1p per element, phi beside v): KF <= 25.
 // Student-t has the linear layout but a residual of the negative binomial's weight (a full-range log1p and a
 // reciprocal per element): it takes the negative binomial's rule.
+// The gamma family takes Poisson's rule, where this one starts: its residual is Poisson's table exp with a
+// subtraction in place of the int-to-double conversion (lighter still), and though its y is a double, y lives in
+// registers only between the slot's release and the residual, four values per lane (KF = 27: 248 VGPRs, as
+// Poisson's, no scratch; past it the slot is released after the backward, as for Poisson).
 __host__ __device__ constexpr bool s16_pre(int FAM, int KF) {
   return FAM == STK_LINREG || KF <= (fam_sum3(FAM) ? 25 : 27);
 }
@@ -74,6 +78,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   constexpr int C = SM_C, NW = SM_W, JTM = g.JTM;
   constexpr bool LOGI = FAM == STK_LOGREG, NB = FAM == STK_NEGBIN, POIS = fam_yint(FAM) && !LOGI;   // POIS: whole int32 counts
   constexpr bool ST = FAM == STK_STUDENT;                // the linear layout (double y, 1 / sigma per chain), its own residual
+  constexpr bool GM = FAM == STK_GAMMA;                  // double ly = log y (fam_ydouble), the shape a per chain, the exp table
   static_assert(fam_known(FAM), "k_sweep16: unknown family");
   const int shard = A.shard0 + blockIdx.x / A.G;
   const int chunk = blockIdx.x % A.G;
@@ -106,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   }
   const double alpha = qs[(size_t)lr * A.Dp];
   // linear: 1 / sigma; negative binomial: v = log phi itself, with phi beside it (a lane is one chain)
-  const double inv_s = fam_inv_sigma(FAM) ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
+  const double inv_s = fam_chain_scalar<FAM>(qs[(size_t)lr * A.Dp + d + 1]);
   double nbphi = 0.0;
   if constexpr (NB) nbphi = exp(inv_s);
   double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;              // student_t: wave-uniform, read once
@@ -115,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
   __builtin_amdgcn_s_waitcnt(0xF70);
 
   const __amdgpu_buffer_rsrc_t xr = uniform_rsrc(sh.x + r0 * d, (int64_t)nrows * d * 8);
-  const void* ybase = (LOGI || POIS) ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
+  const void* ybase = (LOGI || POIS) ? (const void*)(sh.yi + r0) : (const void*)(fam_ydouble<FAM>(sh) + r0);
   const __amdgpu_buffer_rsrc_t yr = uniform_rsrc(ybase, (int64_t)nrows * YB);
   const int nx = (SBX + 1023) >> 10;
   const int last_lanes = (SBX - ((nx - 1) << 10)) >> 4;
@@ -221,6 +226,8 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
           __builtin_amdgcn_sched_barrier(0);   // one element's temporaries at a time: interleaved, the four spill
         } else if constexpr (ST) {
           de[i] = student_resid(eta4[i], yv[i], inv_s, nu, nu1, inv_nu, lm, sp);
+        } else if constexpr (GM) {
+          de[i] = gamma_resid(eta4[i], yv[i], inv_s, tab, lm);
         } else if constexpr (POIS) {
           de[i] = pois_resid(eta4[i], (int32_t)ym[i], tab, lm);
         } else {
@@ -242,6 +249,8 @@ __global__ __launch_bounds__(256, 2) void k_sweep16(SweepArgs A) {
           __builtin_amdgcn_sched_barrier(0);
         } else if constexpr (ST) {
           dv = student_resid(eta4[i], yv[i], inv_s, nu, nu1, inv_nu, lm2, sp2);
+        } else if constexpr (GM) {
+          dv = gamma_resid(eta4[i], yv[i], inv_s, tab, lm2);
         } else if constexpr (POIS) {
           dv = pois_resid(eta4[i], (int32_t)ym[i], tab, lm2);
         } else {

@@ -63,6 +63,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   constexpr int NI = (SM_R * PPR + 63) / 64;        // DMA instructions per slot; the last one has 16 lanes
   constexpr bool LOGI = FAM == STK_LOGREG, NB = FAM == STK_NEGBIN, POIS = fam_yint(FAM) && !LOGI;   // POIS: whole int32 counts
   constexpr bool ST = FAM == STK_STUDENT;           // the linear layout (double y, 1 / sigma per chain), its own residual
+  constexpr bool GM = FAM == STK_GAMMA;             // double ly = log y (fam_ydouble), the shape a per chain, the exp table
   static_assert(fam_known(FAM), "k_sweep16w: unknown family");
   constexpr int YB = fam_yint(FAM) ? 4 : 8;         // int32 y (logistic, poisson) or double y
   static_assert(KF % 4 == 0 && DW <= 128 && (SM_R * PPR) % 64 == 16, "slab geometry");
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   }
   const double alpha = w == 0 ? qs[(size_t)lr * A.Dp] : 0.0;   // wave 0's partial starts at alpha
   // linear: 1 / sigma; negative binomial: v = log phi itself, with phi beside it (a lane is one chain)
-  const double inv_s = fam_inv_sigma(FAM) ? exp(-qs[(size_t)lr * A.Dp + d + 1]) : NB ? qs[(size_t)lr * A.Dp + d + 1] : 0.0;
+  const double inv_s = fam_chain_scalar<FAM>(qs[(size_t)lr * A.Dp + d + 1]);
   double nbphi = 0.0;
   if constexpr (NB) nbphi = exp(inv_s);
   double nu = 0.0, nu1 = 0.0, inv_nu = 0.0;              // student_t: wave-uniform, read once
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
   __builtin_amdgcn_s_waitcnt(0xF70);
 
   const __amdgpu_buffer_rsrc_t xr = uniform_rsrc(sh.x + r0 * d, (int64_t)nrows * d * 8);
-  const void* ybase = (LOGI || POIS) ? (const void*)(sh.yi + r0) : (const void*)(sh.y + r0);
+  const void* ybase = (LOGI || POIS) ? (const void*)(sh.yi + r0) : (const void*)(fam_ydouble<FAM>(sh) + r0);
   const __amdgpu_buffer_rsrc_t yr = uniform_rsrc(ybase, (int64_t)nrows * YB);
   // piece p = 64 j + lane of the slot image is piece p % PPR of row p / PPR; the pad piece and the
   // pieces past column d - 1 repeat the row's last valid piece (finite data under a zero beta)
@@ -188,6 +189,8 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
           __builtin_amdgcn_sched_barrier(0);   // one element's temporaries at a time: interleaved, the four spill
         } else if constexpr (ST) {
           de[i] = student_resid(eta4[i], yv[i], inv_s, nu, nu1, inv_nu, lm, sp);
+        } else if constexpr (GM) {
+          de[i] = gamma_resid(eta4[i], yv[i], inv_s, tab, lm);
         } else if constexpr (POIS) {
           de[i] = pois_resid(eta4[i], (int32_t)ym[i], tab, lm);
         } else {
@@ -209,6 +212,8 @@ __global__ __launch_bounds__(64 * SW_MAXW) void k_sweep16w(SweepArgs A) {
           __builtin_amdgcn_sched_barrier(0);
         } else if constexpr (ST) {
           dv = student_resid(eta4[i], yv[i], inv_s, nu, nu1, inv_nu, lm2, sp2);
+        } else if constexpr (GM) {
+          dv = gamma_resid(eta4[i], yv[i], inv_s, tab, lm2);
         } else if constexpr (POIS) {
           dv = pois_resid(eta4[i], (int32_t)ym[i], tab, lm2);
         } else {

@@ -6,17 +6,19 @@
 #include "predictive_math.h"
 #include "negbin_math.h"
 #include "student_math.h"
+#include "gamma_math.h"
 
 // Which families' instantiations of the sweep kernels a translation unit of sweep.hip, sweep16.hip or
 // sweep16w.hip holds.  Undefined: every family, instantiated implicitly where it is
 // used -- a stand-alone tool that includes the kernel files as one translation unit.  The library's
-// Makefile compiles each kernel file four times: -DSTK_SWEEP_TU=0 is the base object (what is not a
-// template, and the logistic and linear families), 4, 5 and 6 hold the Poisson, negative-binomial and
-// Student-t families alone, so that a new family leaves the others' code objects as they were.  The
+// Makefile compiles each kernel file five times: -DSTK_SWEEP_TU=0 is the base object (what is not a
+// template, and the logistic and linear families), 4, 5, 6 and 7 hold the Poisson, negative-binomial,
+// Student-t and gamma families alone, so that a new family leaves the others' code objects as they were.  The
 // preprocessor cannot read the STK_* enumerators, hence the numbers.
 #ifdef STK_SWEEP_TU
-static_assert(STK_POISSON == 4 && STK_NEGBIN == 5 && STK_STUDENT == 6, "the Makefile's -DSTK_SWEEP_TU ids are the family ids");
-static_assert(STK_SWEEP_TU == 0 || STK_SWEEP_TU == STK_POISSON || STK_SWEEP_TU == STK_NEGBIN || STK_SWEEP_TU == STK_STUDENT,
+static_assert(STK_POISSON == 4 && STK_NEGBIN == 5 && STK_STUDENT == 6 && STK_GAMMA == 7, "the Makefile's -DSTK_SWEEP_TU ids are the family ids");
+static_assert(STK_SWEEP_TU == 0 || STK_SWEEP_TU == STK_POISSON || STK_SWEEP_TU == STK_NEGBIN || STK_SWEEP_TU == STK_STUDENT ||
+                  STK_SWEEP_TU == STK_GAMMA,
               "STK_SWEEP_TU: 0 or a family with an object of its own");
 #endif
 #if !defined(STK_SWEEP_TU) || STK_SWEEP_TU == 0
@@ -34,7 +36,8 @@ static_assert(STK_SWEEP_TU == 0 || STK_SWEEP_TU == STK_POISSON || STK_SWEEP_TU =
   template hipError_t F<STK_LINREG>(__VA_ARGS__);              \
   extern template hipError_t F<STK_POISSON>(__VA_ARGS__);      \
   extern template hipError_t F<STK_NEGBIN>(__VA_ARGS__);       \
-  extern template hipError_t F<STK_STUDENT>(__VA_ARGS__);
+  extern template hipError_t F<STK_STUDENT>(__VA_ARGS__);     \
+  extern template hipError_t F<STK_GAMMA>(__VA_ARGS__);
 #else
 #define STK_SWEEP_INSTANTIATE(F, ...) template hipError_t F<STK_SWEEP_TU>(__VA_ARGS__);
 #endif
@@ -44,18 +47,32 @@ namespace stk {
 // A family is a residual, not a kernel: every sweep takes FAM and must know it.  What the kernels and
 // their launchers ask about a family, in one place:
 __host__ __device__ constexpr bool fam_known(int f) {
-  return f == STK_LINREG || f == STK_LOGREG || f == STK_POISSON || f == STK_NEGBIN || f == STK_STUDENT;
+  return f == STK_LINREG || f == STK_LOGREG || f == STK_POISSON || f == STK_NEGBIN || f == STK_STUDENT || f == STK_GAMMA;
 }
 __host__ __device__ constexpr bool fam_yint(int f) { return f == STK_LOGREG || f == STK_POISSON || f == STK_NEGBIN; }   // y is the shard's int32 y_int
 // The scalar next to beta, q[d + 1], as the kernels carry it per chain in their inv_s slot: linear
 // 1 / sigma = exp(-u); negative binomial v = log phi itself, with phi = exp(v) kept beside it (once per
 // chain, not per element); student_t 1 / sigma as linear (its y is the shard's double y too; nu, nu + 1 and
-// 1 / nu are wave-uniform, read once from the shard's entry); the others have none.
+// 1 / nu are wave-uniform, read once from the shard's entry); gamma the shape a = exp(u) (fam_chain_scalar below);
+// the others have none.
 __host__ __device__ constexpr bool fam_inv_sigma(int f) { return f == STK_LINREG || f == STK_STUDENT; }
 // A third partial sum per chain, column d + 2: the negative binomial's unweighted sum of sp(t), student_t's
 // sum of z^2 / (nu + z^2).  Their residuals are also the heavy ones (a log1p and a reciprocal per element).
+// The gamma family has none: its reduce finishes lp and d lp / d u from H = sum h(t) alone, the lp column.
 __host__ __device__ constexpr bool fam_sum3(int f) { return f == STK_NEGBIN || f == STK_STUDENT; }
-__host__ __device__ constexpr bool fam_exp_table(int f) { return fam_yint(f); }   // the MFMA sweeps keep the exp table in LDS
+// The MFMA sweeps keep the exp table in LDS for the families whose residual takes an exp: those with an int32 y,
+// and the gamma family, the one family with the table and a double y.
+__host__ __device__ constexpr bool fam_exp_table(int f) { return fam_yint(f) || f == STK_GAMMA; }
+// The gamma family's per-row stream is not the shard's y but ly = log y, computed once at model creation
+// (capi_model.hip): ShardDev::sigma, which no other regression reads as an array, points at it.  Its per-chain
+// scalar is the shape a = exp(u) itself, in the inv_s slot.
+template <int FAM>
+__device__ __forceinline__ const double* fam_ydouble(const ShardDev& sh) { return FAM == STK_GAMMA ? sh.sigma : sh.y; }
+// The per-chain scalar of the inv_s slot from the chain's q[d + 1].
+template <int FAM>
+__device__ __forceinline__ double fam_chain_scalar(double q) {
+  return fam_inv_sigma(FAM) ? exp(-q) : FAM == STK_GAMMA ? exp(q) : FAM == STK_NEGBIN ? q : 0.0;
+}
 
 typedef double dbl2 __attribute__((ext_vector_type(2)));   // loads from any address space
 
@@ -311,6 +328,54 @@ __device__ __forceinline__ double student_resid_libm(double eta, double y, doubl
   const double r = 1.0 / (nu + z2);
   ss = fma(z2, r, ss);
   return (z * r) * (nu1 * inv_sigma);
+}
+
+// Gamma residual: Stan's gamma_lpdf(y | a, a exp(-eta)) in the deviance form of include/stark_hip.h (STK_GAMMA)
+// and its derivative for one (row, chain), t = ly - eta with ly = log y the row's stream, a the chain's shape:
+//   lm <- lm + h(t),  h(t) = e^t - 1 - t >= 0       lp = n kappa(a) - L - a H + u, finished in the reduce
+//   dv = a (e^t - 1)                                 (returned)
+// The textbook form n (a log a - lgamma a) + (a - 1) L - a sum (eta + y e^-eta) is not used: on precise data
+// (shape 1e4 and up) a n and a L cancel and lp misses 1e-10 in fp64 whatever the kernel does.  Here nothing of
+// the shape's size is subtracted: h >= 0 is summed as it is, and the reduce multiplies H by a once.
+// e^t - 1 by the table exp of pois_resid (same table, same reduction, v_ldexp_f64) on clamp800(t), with two changes
+// that the sum over the rows needs.  With T = T_{n mod 1024} 2^{n div 1024} and e^r = 1 + rr,
+//   e^t - 1 = (T - 1) + T rr      one fma; T - 1 is exact for t in [-0.69, 0.69], where the difference cancels
+//   rr = r + r^2 (1/2 + r (1/6 + r / 24))      Taylor to r^4: error r^5 / 120 < 4e-20
+// pois_resid's fitted cubic is within 9.4e-17 of e^r, but its error is even in r and has a mean of +4e-17 over the
+// interval: summed over n rows at a fit (every t near 0) that is n a 4e-17 in d lp / d alpha, 1.7e-9 at n = 4,097
+// and a = 1e4, more than the 1e-9 bar of a small gradient component there (1e-10 x 1e-3 x max |g|, max |g| about 1e4).
+// The quartic has no such mean: what is left is the rounding of the table entries and of the fma.
+// T overflows to +inf past t = 709.78 and e^t - 1 is then +inf or NaN (inf rr + inf with rr <= 0), and underflows
+// to 0 (e^t - 1 = -1).  t itself enters h unclamped: t < -800 gives h = -1 - t, which is h to the last bit; where
+// e^t overflows h is +inf or NaN and lp -inf or NaN, never a finite number and never +inf; a NaN eta (the clamp
+// turns it into a finite argument) stays NaN in lm through t.
+// No reciprocal, no log1p, no running product, no second sum: the lightest residual after Poisson's -- 21 vector
+// instructions per element over the linear kernel's by the ISA count of k_sweep16<FAM, 25>, against 14 for Poisson,
+// 64 for logistic, 67 for student_t and 74 for the negative binomial counted the same way.
+__device__ __forceinline__ double gamma_resid(double eta, double ly, double a, const double* tab, double& lm) {
+  constexpr double MAGIC = 6755399441055744.0;            // 1.5 * 2^52
+  constexpr double INV_L = 1477.3197218702985;            // 1024 / ln 2
+  constexpr double L = 0.0006769015435155716;             // ln 2 / 1024
+  const double t = ly - eta;
+  const double c = clamp800(t);
+  const double sn = fma(c, INV_L, MAGIC);
+  const int ni = (int)(uint32_t)__builtin_bit_cast(uint64_t, sn);
+  const double n = sn - MAGIC;
+  const double r = fma(-n, L, c);
+  const double rr = fma(r * r, fma(fma(1.0 / 24.0, r, 1.0 / 6.0), r, 0.5), r);
+  const double T = __builtin_amdgcn_ldexp(tab[ni & (EX_TAB - 1)], ni >> 10);
+  const double em1 = fma(T, rr, T - 1.0);
+  lm += em1 - t;
+  return a * em1;
+}
+
+// The same terms with libm's expm1, for the VALU sweeps (k_sweep, k_sweep2, k_sweep3: C <= 8), which keep no
+// exp table.
+__device__ __forceinline__ double gamma_resid_libm(double eta, double ly, double a, double& lm) {
+  const double t = ly - eta;
+  const double em1 = expm1(t);
+  lm += em1 - t;
+  return a * em1;
 }
 
 }  // namespace stk

@@ -14,11 +14,11 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_NEGBIN, STK_POISSON, STK_SCHOOLS, STK_STUDENT, Config, RunInfo, Shard,
+from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_NEGBIN, STK_POISSON, STK_SCHOOLS, STK_STUDENT, STK_GAMMA, Config, RunInfo, Shard,
                    StarkHipError, check)
 
 FAMILIES = {"schools": STK_SCHOOLS, "linear": STK_LINREG, "logistic": STK_LOGREG, "poisson": STK_POISSON,
-            "neg_binomial": STK_NEGBIN, "student_t": STK_STUDENT}
+            "neg_binomial": STK_NEGBIN, "student_t": STK_STUDENT, "gamma": STK_GAMMA}
 
 # Live library handles, closed in dependency order (samplers, models, contexts) before the
 # HIP runtime's own exit handlers run; after that every close() is a no-op.
@@ -389,7 +389,7 @@ class Model:
             check(lib.stk_model_copy_data(self._h, shard, None, y.ctypes.data, None))
             return {"y": y}
         yint = self.family in (STK_LOGREG, STK_POISSON, STK_NEGBIN)
-        d = D - (2 if self.family in (STK_LINREG, STK_NEGBIN, STK_STUDENT) else 1)
+        d = D - (2 if self.family in (STK_LINREG, STK_NEGBIN, STK_STUDENT, STK_GAMMA) else 1)
         x = np.empty((n, d))
         if yint:
             y = np.empty(n, np.int32)
@@ -576,15 +576,18 @@ class Model:
             out.append(np.ascontiguousarray(yr.T))
         return tuple(out)
 
-    def set_prior(self, alpha=None, beta=None, phi=None):
+    def set_prior(self, alpha=None, beta=None, phi=None, shape=None):
         """normal(0, s) priors on alpha and beta (regressions); None or 0: flat.  phi=(shape, rate): the negative
         binomial's phi ~ gamma(shape, rate) (None: flat; exponential(r) is (1, r)); the library refuses it for
-        every other family."""
+        every other family.  shape=(a, b): the gamma family's shape ~ gamma(a, b), likewise its alone."""
         check(_lib.load().stk_model_set_prior(self._h, float(alpha or 0.0), float(beta or 0.0)))
         self.prior = {"alpha": alpha, "beta": beta}
         if phi is not None:
             check(_lib.load().stk_model_set_prior_phi(self._h, float(phi[0]), float(phi[1])))
             self.prior["phi"] = (float(phi[0]), float(phi[1]))
+        if shape is not None:
+            check(_lib.load().stk_model_set_prior_shape(self._h, float(shape[0]), float(shape[1])))
+            self.prior["shape"] = (float(shape[0]), float(shape[1]))
         return self
 
     def sampler(self, **cfg) -> "Sampler":
@@ -1031,6 +1034,15 @@ def ppc(stats, obs) -> dict:
         out[k] = {"obs": float(To[k]), "rep": Tr[k], "p": float(np.count_nonzero(Tr[k] >= To[k])) / S}
     out["chi2"] = {"obs": ps[:, 6].copy(), "rep": ps[:, 5].copy(), "p": float(np.count_nonzero(ps[:, 5] >= ps[:, 6])) / S}
     return out
+
+
+def gamma_shape_terms(a: float) -> "tuple[float, float]":
+    """The gamma family's shape-only terms at shape a, computed on the host by the code the reduce kernel runs
+    (stk_gamma_shape_terms_host): (kappa(a), kappa'(a)) = (a log a - a - lgamma(a), log a - psi(a)).  NaN for
+    a = 0, inf or NaN.  Needs no device."""
+    out = np.zeros(2, np.float64)
+    check(_lib.load().stk_gamma_shape_terms_host(float(a), out.ctypes.data))
+    return float(out[0]), float(out[1])
 
 
 def negbin_phi_terms(y, phi: float) -> "tuple[float, float]":

@@ -61,17 +61,29 @@ _PRIOR_PHI = re.compile(r"phi~(?:gamma\(" + _NUM + "," + _NUM + r"\)|exponential
 _STUDENT = re.compile(r"y~student_t\((?:" + _NUM + r"|(nu)),(?:alpha\+x\*beta|x\*beta\+alpha),sigma\)$")
 
 
+# y ~ gamma(shape, shape ./ exp(alpha + x * beta)) or y ~ gamma(shape, shape * exp(-(alpha + x * beta))): the gamma
+# GLM with the log link, rate = shape / mean (_strip leaves the blank before `./` where the program has one)
+_ETA = r"(?:alpha\+x\*beta|x\*beta\+alpha)"
+_GAMMA = re.compile(r"y~gamma\(shape,shape(?: ?\./exp\(" + _ETA + r"\)|\*exp\(-\(" + _ETA + r"\)\))\)$")
+# shape ~ gamma(a, b) or shape ~ exponential(r) = gamma(1, r): the gamma family's only shape priors
+_PRIOR_SHAPE = re.compile(r"shape~(?:gamma\(" + _NUM + "," + _NUM + r"\)|exponential\(" + _NUM + r"\))$")
+
+
 def _split_priors(stmts):
     """Separate `alpha ~ normal(0, s)` / `beta ~ normal(0, s)` statements (s > 0) and `phi ~ gamma(a, b)` /
-    `phi ~ exponential(r)` (a, b, r > 0; stored as 'phi': (a, b)) from the rest."""
+    `phi ~ exponential(r)` (a, b, r > 0; stored as 'phi': (a, b)) from the rest; `shape ~ ...` likewise, as
+    'shape': (a, b)."""
     priors, rest = {}, []
     for st in stmts:
         m = _PRIOR.match(st)
         mp = _PRIOR_PHI.match(st)
+        msh = _PRIOR_SHAPE.match(st)
         if m and float(m.group(2)) > 0 and m.group(1) not in priors:
             priors[m.group(1)] = float(m.group(2))
         elif mp and "phi" not in priors and all(float(g) > 0 for g in mp.groups() if g is not None):
             priors["phi"] = (float(mp.group(1)), float(mp.group(2))) if mp.group(1) is not None else (1.0, float(mp.group(3)))
+        elif msh and "shape" not in priors and all(float(g) > 0 for g in msh.groups() if g is not None):
+            priors["shape"] = (float(msh.group(1)), float(msh.group(2))) if msh.group(1) is not None else (1.0, float(msh.group(3)))
         else:
             rest.append(st)
     return priors, rest
@@ -80,7 +92,8 @@ def _split_priors(stmts):
 def program_info(model_code: str):
     """(family, priors) of a supported Stan program; priors = {'alpha': s, 'beta': s} for the
     regressions' optional `alpha ~ normal(0, s)` / `beta ~ normal(0, s)` statements (absent: flat), and
-    'phi': (a, b) for the negative binomial's `phi ~ gamma(a, b)` / `phi ~ exponential(b)`, and 'nu': v for a
+    'phi': (a, b) for the negative binomial's `phi ~ gamma(a, b)` / `phi ~ exponential(b)`, 'shape': (a, b) for the
+    gamma family's `shape ~ gamma(a, b)` / `shape ~ exponential(b)`, and 'nu': v for a
     student_t statement whose nu is the literal v (absent when nu is the data variable: pack_data reads it)."""
     code = _strip(model_code)
     b = _blocks(code)
@@ -94,19 +107,23 @@ def program_info(model_code: str):
         fam = None
     if fam != "neg_binomial" and "phi" in priors:   # a phi prior belongs to the negative binomial alone
         fam = None
+    if fam != "gamma" and "shape" in priors:        # a shape prior belongs to the gamma family alone
+        fam = None
     if fam is None:
         raise NotImplementedError(
             "stark_amd runs a fixed set of model families on the GPU (8 schools, Bayesian linear, logistic, "
             "Poisson (poisson_log), negative-binomial (neg_binomial_2_log) and Student-t (student_t with nu a data "
             "variable or a literal, never a parameter) regression with flat or normal(0, s) "
             "priors on alpha and beta, and for the negative binomial a flat, gamma(a, b) or exponential(r) prior on "
-            "phi; see stark_amd/models/*.stan).  This Stan program is not one of them; pass "
-            "family='schools'|'linear'|'logistic'|'poisson'|'neg_binomial'|'student_t' if it is an equivalent program.")
+            "phi, and gamma regression with the log link (gamma(shape, shape ./ exp(alpha + x * beta))) with a flat, "
+            "gamma(a, b) or exponential(r) prior on shape; see stark_amd/models/*.stan).  This Stan program is not one "
+            "of them; pass "
+            "family='schools'|'linear'|'logistic'|'poisson'|'neg_binomial'|'student_t'|'gamma' if it is an equivalent program.")
     return fam, priors
 
 
 def recognise(model_code: str) -> str:
-    """Return 'schools', 'linear', 'logistic', 'poisson', 'neg_binomial' or 'student_t' for a supported Stan program."""
+    """Return 'schools', 'linear', 'logistic', 'poisson', 'neg_binomial', 'student_t' or 'gamma' for a supported Stan program."""
     return program_info(model_code)[0]
 
 
@@ -145,6 +162,12 @@ def _recognise_blocks(b: dict, stm: list):
             if (_decl(params, r"(^|;)real<lower=0>sigma(;|$)") and not _decl(params, r"(^|;)[^;]*[ >\]]nu(;|$)")
                     and not b.get("transformed parameters") and nu_ok):
                 return "student_t"
+        if len(stm) == 1 and _GAMMA.match(stm[0]):
+            # the rate is shape / exp(eta) itself (any other rate expression, an added offset, an identity or inverse
+            # link are other programs to this recogniser), shape the parameter real<lower=0> shape, y positive reals
+            if (_decl(params, r"(^|;)real<lower=0>shape(;|$)") and not _decl(params, r"sigma|phi") and not b.get("transformed parameters")
+                    and _decl(b.get("data", ""), r"(^|;)(vector<lower=0>\[N\]y|real<lower=0>y\[N\]|array\[N\]real<lower=0>y)(;|$)")):
+                return "gamma"
         if stm in (["y~normal(alpha+x*beta,sigma)"], ["y~normal(x*beta+alpha,sigma)"]):
             if _decl(params, r"real<lower=0>sigma"):
                 return "linear"
@@ -153,9 +176,10 @@ def _recognise_blocks(b: dict, stm: list):
 
 def load_program_info(file=None, model_code=None, family=None, priors=None, **_ignored):
     """Mirror of pystan.StanModel(file=..., model_code=...) argument handling -> (family, priors).
-    family= (and priors={'alpha': s, 'beta': s}, for 'neg_binomial' also 'phi': (shape, rate)) override recognition."""
+    family= (and priors={'alpha': s, 'beta': s}, for 'neg_binomial' also 'phi': (shape, rate), for 'gamma' also
+    'shape': (shape, rate)) override recognition."""
     if family is not None:
-        if family not in ("schools", "linear", "logistic", "poisson", "neg_binomial", "student_t"):
+        if family not in ("schools", "linear", "logistic", "poisson", "neg_binomial", "student_t", "gamma"):
             raise ValueError(f"unknown family {family!r}")
         return family, dict(priors or {})
     if model_code is None:
@@ -217,6 +241,11 @@ def pack_data(family: str, data: dict, nu=None) -> dict:
         if not (np.isfinite(nu) and nu > 0):
             raise ValueError(f"student_t data: nu must be finite and > 0 (real<lower=0> nu), got {nu!r}")
         return {"x": x, "y": y, "nu": nu}
+    if family == "gamma":
+        # vector<lower=0>[N] y: the density needs log y, so 0 is refused too, and so is anything not finite
+        if not np.all(np.isfinite(y) & (y > 0)):
+            bad = int(np.flatnonzero(~(np.isfinite(y) & (y > 0)))[0])
+            raise ValueError(f"gamma data: y must be finite and > 0, got y[{bad}] = {y[bad]!r}")
     return {"x": x, "y": y}
 
 
@@ -232,6 +261,8 @@ def column_names(family: str, data: dict) -> list:
         cols.append("sigma")
     if family == "neg_binomial":
         cols.append("phi")
+    if family == "gamma":
+        cols.append("shape")
     return cols + ["lp__"]
 
 

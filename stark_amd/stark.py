@@ -114,15 +114,17 @@ def _unconstrain(family, data, init_dict):
         v.append(np.log(float(init_dict.get("sigma", 1.0))))
     if family == "neg_binomial":
         v.append(np.log(float(init_dict.get("phi", 1.0))))
+    if family == "gamma":
+        v.append(np.log(float(init_dict.get("shape", 1.0))))
     return np.asarray(v)
 
 
 NO_ANALYSIS_FAMILY = "neg_binomial"   # samples and combines; the analysis sweeps do not cover it
-NO_ANALYSIS_FAMILIES = (NO_ANALYSIS_FAMILY, "student_t")   # Student-t likewise
+NO_ANALYSIS_FAMILIES = (NO_ANALYSIS_FAMILY, "student_t", "gamma")   # Student-t and gamma likewise
 
 
 def _refuse_analysis(family, what):
-    """ValueError, before any sampling, where `what` is asked of the negative binomial or of Student-t: the Hessian,
+    """ValueError, before any sampling, where `what` is asked of the negative binomial, of Student-t or of gamma: the Hessian,
     log-predictive, PSIS-LOO, per-draw log-density, bootstrap and posterior predictive sweeps cover linear, logistic
     and poisson."""
     if family in NO_ANALYSIS_FAMILIES:
@@ -140,13 +142,13 @@ def unconstrain_draws(family, samples, n_cols=None):
     (``Stark.waic`` passes it); None takes it from the row count.
     ValueError for 8 schools (no log-predictive sweep), for P != D + 1 -- the draws of a ``pars=``
     selection cannot be scored: every parameter is needed -- and for a sigma <= 0 (names the draw)."""
-    if family not in ("linear", "logistic", "poisson", "neg_binomial", "student_t"):
+    if family not in ("linear", "logistic", "poisson", "neg_binomial", "student_t", "gamma"):
         raise ValueError(f"draws of the {family} family cannot be scored: the log-predictive sweep covers the "
                          "regression families (linear, logistic, poisson), not 8 schools")
     m = np.asarray(samples, np.float64)
     if m.ndim != 2:
         raise ValueError(f"samples must be the P x S draw matrix, got shape {m.shape}")
-    scale = {"linear": "sigma", "neg_binomial": "phi", "student_t": "sigma"}.get(family)   # the positive parameter after beta, if any
+    scale = {"linear": "sigma", "neg_binomial": "phi", "student_t": "sigma", "gamma": "shape"}.get(family)   # the positive parameter after beta, if any
     extra = 2 if scale else 1                           # parameters besides beta
     d = int(n_cols) if n_cols is not None else m.shape[0] - 1 - extra
     D = d + extra

@@ -117,11 +117,11 @@ def main():
     res["summary"] = {"kernels_same": nsame, "kernels_changed": ndiff, "kernels_new": nnew, "kernels_gone": ngone}
     if a.brief:
         keys = ("vgpr", "sgpr", "scratch_bytes", "lds_static_bytes", "vgpr_spills", "sgpr_spills", "instructions")
-        res["brief"] = "same: a count; changed: 'parent>branch' of " + ", ".join(keys) + "; new: the kernel names"
+        res["brief"] = "same: a count; changed: 'parent>branch' of " + ", ".join(keys) + "; new: those figures per kernel"
         for r in res["objects"].values():
             r["same"] = len(r["same"])
             r["changed"] = {k: " ".join(f"{v['parent'][f]}>{v['branch'][f]}" for f in keys) for k, v in r["changed"].items()}
-            r["new"] = sorted(r["new"])
+            r["new"] = {k: " ".join(f"{f}={v[f]}" for f in keys) for k, v in sorted(r["new"].items())}
     text = json.dumps(res, indent=1, sort_keys=True)
     if a.out:
         with open(a.out, "w") as f:
