@@ -16,6 +16,11 @@
  *                               launches of a sampling run (parity hook)
  *   stk_chain_batches           the batches a regression shard's `chains` run as (host only)
  *   stk_sweep_launch_info       the kernel and launch shape one batch's sweep has at (rows, d, C) (host only)
+ *   stk_model_create_sparse /   the same six regression families on CSR shards, kept as padded (index, value) rows:
+ *   stk_model_sparse_info /     density hooks, sampler, fingerprints and checkpoints as on a dense model; the
+ *   stk_chain_batches_sparse /  sparse batch table and launch shape (host only); the host twin of the sparse
+ *   stk_sweep_launch_info_sparse / shard's fingerprint (no reference counterpart: the reference's rows are dense)
+ *   stk_shard_fingerprint_sparse_host
  *   stk_fingerprint_words /     a 64-bit fingerprint of a shard's rows, on the device or the host;
  *   stk_shard_fingerprint_host / saved sampler states are bound to it (no reference counterpart)
  *   stk_model_fingerprint
@@ -393,6 +398,54 @@ STK_API int stk_chain_batches(int32_t C, int32_t d, int32_t* sizes, int32_t cap)
  * long that one of its chunks does not fit a buffer descriptor) -- the shapes stk_sampler_create and
  * the stk_log_density_grad* hooks refuse with the same code before they launch anything. */
 STK_API int stk_sweep_launch_info(int64_t n_rows, int32_t d, int32_t C, int64_t out[6]);
+
+/* ---- sparse design matrices: a second storage for the six regression families ----
+ * One shard of a sparse model, in CSR: row r's entries are indices / values [indptr[r], indptr[r + 1]).
+ * y / y_int are those of stk_shard for the family (logreg, poisson, negbin: y_int; linreg, student, gamma: y).
+ * Checked before anything is launched (STK_E_ARG names the shard and the row): indptr[0] = 0 and indptr
+ * non-decreasing; every index in [0, n_cols); indices strictly increasing within a row (duplicates are the
+ * caller's to sum); every value finite.  An index outside [0, n_cols) would be an out-of-bounds access on the
+ * device, so the check is never skipped.  The arrays may be host or device memory (device arrays are copied
+ * back for the check).  The y checks are those of stk_model_create. */
+typedef struct {
+  int64_t n_rows;
+  int32_t n_cols;
+  const int64_t* indptr;    /* [n_rows + 1] */
+  const int32_t* indices;   /* [indptr[n_rows]] */
+  const double* values;     /* [indptr[n_rows]] */
+  const double* y;
+  const int32_t* y_int;
+} stk_shard_sparse;
+/* A model whose every shard is sparse (a model is all sparse or all dense).  On the device a shard is kept as
+ * padded rows (ELL): K = the shard's longest row, idx[n_rows][K] int32 and val[n_rows][K] double, a short row
+ * padded with (0, 0.0) -- 12 K bytes per row instead of 8 n_cols; K may be 0 and may reach n_cols; one long row
+ * inflates K for its whole shard.  The priors, stk_model_set_student_nu, the density hooks (stk_log_density_grad,
+ * _shards, _chains), the sampler (every chain count, the three metrics, both U-turn criteria, stk_transition*,
+ * stk_sample), fingerprints and checkpoints work as on a dense model; the sweeps are k_sweep_sp (kind 7).  The
+ * analysis sweeps (Hessian, log-predictive, PSIS-LOO, per-draw log density, bootstrap, posterior predictive) and
+ * full-data mode (stk_sampler_set_allreduce) refuse a sparse model with STK_E_ARG and a message that says so. */
+STK_API int stk_model_create_sparse(stk_ctx* ctx, int family, const stk_shard_sparse* shards, int nshards, stk_model** out);
+/* out[0] = K, out[1] = nnz (the entries handed over, explicit zeros among them), out[2] = device bytes of
+ * the padded rows, 12 K n_rows.  STK_E_ARG for a dense model.  stk_model_shard_arrays reports x = NULL. */
+STK_API int stk_model_sparse_info(const stk_model* m, int shard, int64_t out[3]);
+/* The chain batches of a SPARSE shard's C chains at d covariates: greedy, largest first, over {16, 8, 4, 2, 1}
+ * for d <= 512 and {8, 4, 2, 1} for 512 < d <= 1024 (beta and the gradient of 16 chains no longer fit a CU's
+ * LDS); there is no 64-chain sparse pass.  A pure host function of (C, d), the contract of stk_chain_batches. */
+STK_API int stk_chain_batches_sparse(int32_t C, int32_t d, int32_t* sizes, int32_t cap);
+/* The sparse sweep of one batch of C chains over n_rows x d with longest row K (host only).  out[0] kind (7);
+ * out[1] rows per tile; out[2] bytes of the entry stage in LDS; out[3] chunks per shard (a function of n_rows
+ * alone); out[4] dynamic LDS bytes per block; out[5] private gradient copies per block (4, 2 or 1); out[6] 1 when
+ * a tile's entries (12 K bytes per row) are staged in LDS, 0 when the kernel reads them from global memory --
+ * the same bits either way; out[7] bytes of the shard's padded rows, 12 K n_rows. */
+STK_API int stk_sweep_launch_info_sparse(int64_t n_rows, int32_t d, int32_t K, int32_t C, int64_t out[8]);
+/* The fingerprint of a sparse shard.  With the padded rows idx / val as the device keeps them,
+ *   fmix( words([family, n_rows, n_cols, K], 0, 0) + words(idx: n_rows K int32, 5, 0) + words(val: n_rows K
+ *         doubles, 6, 0) + words(y, 2, 0) or words(y_int, 3, 0) )
+ * with two tags of its own, T[5] = 0xBE5466CF34E90C6C and T[6] = 0xC0AC29B7C97C50DD, and a four-word header, so
+ * that a sparse shard and the dense shard of the same matrix never share one.  stk_model_fingerprint gives the
+ * same bits from the device arrays; a state saved against the dense model of the same matrix is refused as
+ * saved against other data.  Host only; validates the shard as stk_model_create_sparse does. */
+STK_API int stk_shard_fingerprint_sparse_host(int family, const stk_shard_sparse* shard, uint64_t* out);
 
 /* ---- analytic Hessian (regression families, 1 <= d <= 128): one weighted Gram matrix
  * X~^T diag(w) X~, X~ = [1 | X], accumulated on the fp64 MFMA in a single pass over the shard ----

@@ -36,6 +36,13 @@ class Shard(ctypes.Structure):
                 ("sigma", ctypes.c_void_p)]
 
 
+class ShardSparse(ctypes.Structure):
+    """stk_shard_sparse: one CSR shard (indptr int64 [n_rows + 1], indices int32, values double)."""
+    _fields_ = [("n_rows", ctypes.c_int64), ("n_cols", ctypes.c_int32),
+                ("indptr", ctypes.c_void_p), ("indices", ctypes.c_void_p), ("values", ctypes.c_void_p),
+                ("y", ctypes.c_void_p), ("y_int", ctypes.c_void_p)]
+
+
 class Config(ctypes.Structure):
     _fields_ = [("num_warmup", ctypes.c_int32), ("num_samples", ctypes.c_int32),
                 ("chains", ctypes.c_int32), ("max_depth", ctypes.c_int32),
@@ -99,6 +106,11 @@ SIGNATURES = [
     ("stk_log_density_grad_chains", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp]),
     ("stk_chain_batches", ctypes.c_int, [_i32, _i32, _vp, _i32]),
     ("stk_sweep_launch_info", ctypes.c_int, [_i64, _i32, _i32, _vp]),
+    ("stk_model_create_sparse", ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ShardSparse), ctypes.c_int, _pp]),
+    ("stk_model_sparse_info", ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    ("stk_chain_batches_sparse", ctypes.c_int, [_i32, _i32, _vp, _i32]),
+    ("stk_sweep_launch_info_sparse", ctypes.c_int, [_i64, _i32, _i32, _i32, _vp]),
+    ("stk_shard_fingerprint_sparse_host", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ShardSparse), ctypes.POINTER(_u64)]),
     ("stk_sampler_create", ctypes.c_int, [_vp, ctypes.POINTER(Config), _pp]),
     ("stk_sampler_run", ctypes.c_int, [_vp, _i32, _i64]),
     ("stk_sampler_info", ctypes.c_int, [_vp, ctypes.POINTER(RunInfo)]),

@@ -25,6 +25,20 @@ std::vector<int> chain_batches(int C, int d) {
   return b;
 }
 
+// A sparse shard's: the sizes k_sweep_sp covers at d (sweep_sparse.hip: 16 up to d = 512, no 64-chain pass).
+std::vector<int> chain_batches_sparse(int C, int d) {
+  std::vector<int> b;
+  for (const int sz : {16, 8, 4, 2, 1}) {
+    if (!stk_sweep_sparse_supported(sz, d)) continue;
+    for (; C >= sz; C -= sz) b.push_back(sz);
+  }
+  if (C != 0) b.clear();
+  return b;
+}
+std::vector<int> model_chain_batches(const stk_model* m, int C) {
+  return m->sparse ? chain_batches_sparse(C, m->d) : chain_batches(C, m->d);
+}
+
 // Refuses, before anything is launched, a shard that no sweep covers at its n, d and batch size.
 int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int count, ChainPlan* cp) {
   *cp = ChainPlan();
@@ -34,7 +48,7 @@ int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int
     b.c0 = cp->Ct;
     b.part_off = cp->partial_bytes / sizeof(double);
     for (int sh = first; sh < first + count;) {
-      SweepGroup gr{sh, 1, stk_sweep_plan(m->sh[sh].n, m->d, sz, 0)};
+      SweepGroup gr{sh, 1, m->sparse ? stk_sweep_plan_sparse(m->sh[sh].n, m->d, sz) : stk_sweep_plan(m->sh[sh].n, m->d, sz, 0)};
       ARG_CHECK(gr.launch.kind != SWEEP_NONE,
                 "shard %d: no sweep covers n = %lld rows of d = %d covariates at C = %d chains (a chunk of the shard "
                 "must fit a buffer descriptor: split the shard)", sh, (long long)m->sh[sh].n, m->d, sz);
@@ -55,6 +69,7 @@ int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int
 // holds the run's buffers; a batch's partial-sum region, stride and first chain are filled in here.
 static SweepCall batch_call(const stk_model* m, const ChainPlan& cp, const ChainBatch& b, SweepCall c) {
   c.nb = m->nb_dev.as<NbShardDev>();   // NULL but for the negative binomial and the gamma family, whose reduces read it
+  c.sp = m->sp_dev.as<SpShardDev>();   // NULL but for a sparse model
   c.partial += b.part_off;
   c.Gs = b.Gs;
   c.Ct = cp.Ct;
@@ -65,7 +80,9 @@ hipError_t plan_sweeps(const stk_model* m, const ChainPlan& cp, const SweepCall&
   for (const auto& b : cp.batches) {
     const SweepCall c = batch_call(m, cp, b, run);
     for (const auto& gr : b.groups)
-      if (const hipError_t e = stk_launch_sweep(m->family, gr.launch, gr.shard0, gr.nsh, c, st)) return e;
+      if (const hipError_t e = gr.launch.kind == SWEEP_SPARSE ? stk_launch_sweep_sparse(m->family, gr.launch, gr.shard0, gr.nsh, c, st)
+                                                              : stk_launch_sweep(m->family, gr.launch, gr.shard0, gr.nsh, c, st))
+        return e;
   }
   return hipSuccess;
 }
@@ -188,7 +205,9 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
     // the chain batch the sampler's sweep uses: 64 (two-pass fp64 MFMA GEMMs) from 64 points,
     // 16 (fp64 MFMA) from 16 when d <= 128, else 4 / 2 / 1; this shard alone, the last point
     // repeated to fill the last batch (the kernel reads rows shard * Cb + c of the point buffer)
-    const int Cb = C <= 1 ? 1 : (C <= 2 ? 2 : (C >= 64 ? 64 : (C < 16 || !hook_single_launch(16, s.d) ? 4 : 16)));
+    // (a sparse shard: 16 where the sparse sweep covers it at d, no 64)
+    const int Cb = m->sparse ? (C <= 1 ? 1 : C <= 2 ? 2 : (C < 16 || !stk_sweep_sparse_supported(16, s.d)) ? 4 : 16)
+                             : C <= 1 ? 1 : (C <= 2 ? 2 : (C >= 64 ? 64 : (C < 16 || !hook_single_launch(16, s.d) ? 4 : 16)));
     ChainPlan plan;
     RC(chain_plan(m, {Cb}, shard, 1, &plan));
     for (int c0 = 0; c0 < C; c0 += Cb)
@@ -220,7 +239,10 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
 int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_shards: bad arguments");
   ARG_CHECK(is_sweep_family(m->family), "stk_log_density_grad_shards: regression families only");
-  ARG_CHECK(hook_single_launch(C, m->d), "points per shard must be a single batch size here: 1, 2, 4, 8, 16 (d <= 128) or 64");
+  if (m->sparse)
+    ARG_CHECK(stk_sweep_sparse_supported(C, m->d), "points per shard must be a single batch size of a sparse model here: 1, 2, 4, 8 or 16 (d <= 512)");
+  else
+    ARG_CHECK(hook_single_launch(C, m->d), "points per shard must be a single batch size here: 1, 2, 4, 8, 16 (d <= 128) or 64");
   return hook_every_shard(m, {C}, q, lp, grad);
 }
 
@@ -229,8 +251,8 @@ int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double
 int stk_log_density_grad_chains(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_chains: bad arguments");
   ARG_CHECK(is_sweep_family(m->family), "stk_log_density_grad_chains: regression families only");
-  ARG_CHECK(!chain_batches(C, m->d).empty(), "no sweep covers %d covariates (1..1024)", m->d);
-  return hook_every_shard(m, chain_batches(C, m->d), q, lp, grad);
+  ARG_CHECK(!model_chain_batches(m, C).empty(), "no sweep covers %d covariates (1..1024)", m->d);
+  return hook_every_shard(m, model_chain_batches(m, C), q, lp, grad);
 }
 
 // The chain batches a regression shard's C chains run as at d covariates (host only: no device).
@@ -240,6 +262,26 @@ int stk_chain_batches(int32_t C, int32_t d, int32_t* sizes, int32_t cap) {
   ARG_CHECK(!b.empty(), "no sweep covers %d covariates (1..1024)", d);
   for (size_t i = 0; i < b.size() && (int32_t)i < cap; ++i) sizes[i] = b[i];
   return (int)b.size();
+}
+
+// A sparse shard's (host only: no device).
+int stk_chain_batches_sparse(int32_t C, int32_t d, int32_t* sizes, int32_t cap) {
+  ARG_CHECK(C >= 1 && d >= 1 && cap >= 0 && (sizes || cap == 0), "stk_chain_batches_sparse: need C >= 1, d >= 1, cap >= 0");
+  const std::vector<int> b = chain_batches_sparse(C, d);
+  ARG_CHECK(!b.empty(), "no sparse sweep covers %d covariates (1..1024)", d);
+  for (size_t i = 0; i < b.size() && (int32_t)i < cap; ++i) sizes[i] = b[i];
+  return (int)b.size();
+}
+
+// The sparse sweep one batch of C chains runs over a shard of n_rows x d whose longest row has K entries (host only).
+int stk_sweep_launch_info_sparse(int64_t n_rows, int32_t d, int32_t K, int32_t C, int64_t out[8]) {
+  ARG_CHECK(n_rows >= 1 && d >= 1 && out, "stk_sweep_launch_info_sparse: need n_rows >= 1, d >= 1 and out");
+  ARG_CHECK(K >= 0 && K <= d, "stk_sweep_launch_info_sparse: K = %d; a row of d = %d covariates has 0 .. d entries", K, d);
+  ARG_CHECK(stk_sweep_sparse_supported(C, d), "%d chains are not one batch of a sparse shard at %d covariates (stk_chain_batches_sparse)", C, d);
+  const SweepLaunch p = stk_sweep_plan_sparse(n_rows, d, C);
+  const int64_t v[8] = {p.kind, p.T, p.ld, p.G, (int64_t)p.lds, p.waves, (int64_t)p.T * K * 12 <= p.ld ? 1 : 0, 12 * (int64_t)K * n_rows};
+  memcpy(out, v, sizeof(v));
+  return STK_OK;
 }
 
 // The sweep one batch of C chains runs over a shard of n_rows x d (host only: no device).
@@ -271,6 +313,7 @@ int stk_hessian_launch_info(int64_t n_rows, int32_t d, int64_t out[5]) {
 // they are its bits; the Hessians of all the call's shards are one sweep launch and one reduce launch.
 int stk_log_density_hessian(stk_model* m, int shard, const double* q, double* lp, double* grad, double* hess) {
   ARG_CHECK(m && q && hess && shard >= -1 && shard < m->nshards, "stk_log_density_hessian: bad arguments");
+  REFUSE_SPARSE(m, "stk_log_density_hessian");
   ARG_CHECK(is_regression(m->family), "stk_log_density_hessian: no Hessian sweep for the %s family (regressions only)",
             family_name(m->family));
   ARG_CHECK(stk_hessian_supported(m->d), "stk_log_density_hessian: the Hessian sweep covers 1 <= d <= 128 covariates, not d = %d",
@@ -319,6 +362,7 @@ int stk_predictive_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out
 
 int stk_log_predictive(stk_model* m, int shard, const double* q, int32_t S, double* rows, double* totals) {
   ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_log_predictive: bad model or shard");
+  REFUSE_SPARSE(m, "stk_log_predictive");
   ARG_CHECK(is_regression(m->family), "stk_log_predictive: no log-predictive sweep for the %s family (regressions only)",
             family_name(m->family));
   ARG_CHECK(stk_predictive_supported(m->d),
@@ -349,6 +393,7 @@ int stk_loo_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]) {
 
 int stk_loo(stk_model* m, int shard, const double* q, int32_t S, double* rows, double* totals) {
   ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_loo: bad model or shard");
+  REFUSE_SPARSE(m, "stk_loo");
   ARG_CHECK(is_regression(m->family), "stk_loo: no PSIS-LOO sweep for the %s family (regressions only)", family_name(m->family));
   ARG_CHECK(stk_loo_supported(m->d), "stk_loo: the PSIS-LOO sweep covers 1 <= d <= 128 covariates, not d = %d (%s family)",
             m->d, family_name(m->family));
@@ -380,6 +425,7 @@ int stk_logdens_launch_info(int64_t n_rows, int32_t d, int32_t S, int64_t out[6]
 // log-predictive sweep's draw image), one sweep launch and one reduce launch for all of them.
 int stk_log_density_draws(stk_model* m, int shard, const double* q, int32_t S, double* lp) {
   ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_log_density_draws: bad model or shard");
+  REFUSE_SPARSE(m, "stk_log_density_draws");
   ARG_CHECK(is_regression(m->family), "stk_log_density_draws: no per-draw log-density sweep for the %s family (regressions only)",
             family_name(m->family));
   ARG_CHECK(stk_logdens_supported(m->d),
@@ -448,6 +494,7 @@ int stk_boot_weights_host(uint64_t seed, uint32_t stream, int64_t row0, int64_t 
 int stk_log_density_grad_boot(stk_model* m, int shard, const double* q, int32_t R, int32_t rep0, uint64_t seed,
                               const int32_t* streams, int32_t kind, double* lp, double* grad, double* wsum) {
   ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_log_density_grad_boot: bad model or shard");
+  REFUSE_SPARSE(m, "stk_log_density_grad_boot");
   ARG_CHECK(is_regression(m->family), "stk_log_density_grad_boot: no bootstrap sweep for the %s family (regressions only)",
             family_name(m->family));
   ARG_CHECK(stk_boot_supported(m->d),
@@ -576,6 +623,7 @@ int stk_yrep_host(int32_t family, uint64_t seed, uint32_t stream, int64_t row0, 
 int stk_posterior_predict(stk_model* m, int shard, const double* q, int32_t S, int32_t draw0, uint64_t seed,
                           const int32_t* streams, double* stats, double* obs, double* rows, double* yrep) {
   ARG_CHECK(m && shard >= -1 && shard < m->nshards, "stk_posterior_predict: bad model or shard");
+  REFUSE_SPARSE(m, "stk_posterior_predict");
   ARG_CHECK(is_regression(m->family), "stk_posterior_predict: no posterior predictive sweep for the %s family (regressions only)",
             family_name(m->family));
   ARG_CHECK(stk_ppc_supported(m->d),

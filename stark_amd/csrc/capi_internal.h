@@ -97,6 +97,10 @@ struct stk_model {
   std::vector<NbShardDev> nb;   // STK_NEGBIN: per shard, the count table (in bufs) and the phi prior; derived data
                                 // (STK_GAMMA: per shard, L = sum log y (in bufs) and the shape prior)
   DevBuf nb_dev;                // its device copy, what the reduce reads
+  bool sparse = false;          // every shard's design matrix is kept as padded rows (stk_model_create_sparse): sh[s].x is null
+  std::vector<SpShardDev> sp;   // its side table, per shard (idx and val live in bufs), and the entries handed over
+  std::vector<int64_t> sp_nnz;
+  DevBuf sp_dev;                // the side table's device copy, what k_sweep_sp reads
   double nu = 0.0;              // STK_STUDENT: the degrees of freedom (0: not set yet); every shard's ShardDev carries a copy
   int64_t bytes = 0;
   std::vector<uint64_t> fp;   // shard fingerprints, computed on first use (the data never changes)
@@ -181,6 +185,13 @@ ShardRange shard_range(const stk_model* m, int shard, int (*chunks)(int64_t n));
 
 // ---- capi_density.hip: the chain plan (its construction comment is at ChainPlan above)
 std::vector<int> chain_batches(int C, int d);
+std::vector<int> chain_batches_sparse(int C, int d);
+std::vector<int> model_chain_batches(const stk_model* m, int C);   // the model's storage decides which of the two
+// An entry point without a sparse form: STK_E_ARG, before anything is launched, with a message that names the
+// entry point and says that the model is sparse.
+#define REFUSE_SPARSE(m, what)                                                                                      \
+  ARG_CHECK(!(m)->sparse, "%s: the model is sparse (stk_model_create_sparse); the sparse storage serves the density " \
+                          "hooks and the sampler only: build a dense model for this", what)
 int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int count, ChainPlan* cp);
 hipError_t plan_sweeps(const stk_model* m, const ChainPlan& cp, const SweepCall& run, hipStream_t st);
 hipError_t plan_reduces(const stk_model* m, const ChainPlan& cp, const SweepCall& run, double* lp, double* g,

@@ -209,6 +209,31 @@ static int attach_gamma_data(stk_model* m, int s, const double* y_dev, int64_t n
   return STK_OK;
 }
 
+// A regression shard's y, dense or sparse: validated for the family, copied to the device, with the family's derived
+// data (the negative binomial's count table, the gamma family's log y).  `in` is read for n_rows, y, y_int and sigma.
+static int upload_regression_y(stk_model* m, int s, const stk_shard& in, ShardDev* out) {
+  const int family = m->family;
+  const size_t n = (size_t)in.n_rows;
+  ShardDev& sd = *out;
+  if (family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN) {
+    const bool pois = family != STK_LOGREG;   // a count family
+    const char* fam = family == STK_NEGBIN ? "neg_binomial" : pois ? "poisson" : "logreg";
+    ARG_CHECK(in.y_int, "shard %d: %s needs y_int", s, fam);
+    // counts handed over as doubles too: say so, do not pick one of the two
+    ARG_CHECK(!pois || (!in.y && !in.sigma), "shard %d: %s takes its counts in y_int alone; y and sigma must be NULL", s, fam);
+    RC(upload(m, in.y_int, n, &sd.yi));
+    RC(check_y_int(m, s, sd.yi, in.n_rows, pois, family == STK_NEGBIN ? "neg_binomial_2_log needs y >= 0" : "poisson_log needs y >= 0"));
+    if (family == STK_NEGBIN) RC(attach_nb_table(m, sd.yi, in.n_rows));
+  } else {   // family_dims knows every family: a new one must say here which y it takes
+    ARG_CHECK(family == STK_LINREG || family == STK_STUDENT || family == STK_GAMMA, "shard %d: model family %d has no data layout", s,
+              family);
+    ARG_CHECK(in.y, "shard %d: %s needs y", s, family == STK_STUDENT ? "student_t" : family == STK_GAMMA ? "gamma" : "linreg");
+    RC(upload(m, in.y, n, &sd.y));
+    if (family == STK_GAMMA) RC(attach_gamma_data(m, s, sd.y, in.n_rows, &sd.sigma));   // sigma carries ly = log y (common.h)
+  }
+  return STK_OK;
+}
+
 // Shard s of a model from the caller's rows: validated, copied to the device, appended to m->sh.
 static int upload_shard(stk_model* m, int s, const stk_shard& in) {
   const int family = m->family;
@@ -227,24 +252,133 @@ static int upload_shard(stk_model* m, int s, const stk_shard& in) {
     ARG_CHECK(in.x && in.n_cols > 0, "shard %d: regression needs x", s);
     ARG_CHECK(stk_sweep_supported(1, in.n_cols), "n_cols %d unsupported (1..1024)", in.n_cols);
     RC(upload(m, in.x, n * in.n_cols, &sd.x));
-    if (family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN) {
-      const bool pois = family != STK_LOGREG;   // a count family
-      const char* fam = family == STK_NEGBIN ? "neg_binomial" : pois ? "poisson" : "logreg";
-      ARG_CHECK(in.y_int, "shard %d: %s needs y_int", s, fam);
-      // counts handed over as doubles too: say so, do not pick one of the two
-      ARG_CHECK(!pois || (!in.y && !in.sigma), "shard %d: %s takes its counts in y_int alone; y and sigma must be NULL", s, fam);
-      RC(upload(m, in.y_int, n, &sd.yi));
-      RC(check_y_int(m, s, sd.yi, in.n_rows, pois, family == STK_NEGBIN ? "neg_binomial_2_log needs y >= 0" : "poisson_log needs y >= 0"));
-      if (family == STK_NEGBIN) RC(attach_nb_table(m, sd.yi, in.n_rows));
-    } else {   // family_dims knows every family: a new one must say here which y it takes
-      ARG_CHECK(family == STK_LINREG || family == STK_STUDENT || family == STK_GAMMA, "shard %d: model family %d has no data layout", s,
-                family);
-      ARG_CHECK(in.y, "shard %d: %s needs y", s, family == STK_STUDENT ? "student_t" : family == STK_GAMMA ? "gamma" : "linreg");
-      RC(upload(m, in.y, n, &sd.y));
-      if (family == STK_GAMMA) RC(attach_gamma_data(m, s, sd.y, in.n_rows, &sd.sigma));   // sigma carries ly = log y (common.h)
-    }
+    RC(upload_regression_y(m, s, in, &sd));
   }
   m->sh.push_back(sd);
+  return STK_OK;
+}
+
+// ---------------------------------------------------------------- sparse shards
+// A sparse shard's three CSR arrays as host memory: the caller's own, or copies of its device arrays.
+struct CsrHost {
+  std::vector<int64_t> ip;
+  std::vector<int32_t> ix;
+  std::vector<double> vv;
+  const int64_t* indptr = nullptr;
+  const int32_t* indices = nullptr;
+  const double* values = nullptr;
+};
+static int csr_host(int s, const stk_shard_sparse& in, int device, CsrHost* h) {
+  ARG_CHECK(in.n_rows > 0, "shard %d: n_rows must be positive", s);
+  ARG_CHECK(in.indptr, "shard %d: a sparse shard needs indptr", s);
+  h->indptr = in.indptr;
+  if (device >= 0 && is_device_ptr(in.indptr, device)) {
+    h->ip.resize((size_t)in.n_rows + 1);
+    STK_HIP_CHECK(hipMemcpy(h->ip.data(), in.indptr, sizeof(int64_t) * h->ip.size(), hipMemcpyDefault));
+    h->indptr = h->ip.data();
+  }
+  const int64_t nnz = h->indptr[in.n_rows];
+  ARG_CHECK(nnz >= 0, "shard %d: row %lld: indptr ends at %lld; it runs from 0 to the number of entries", s,
+            (long long)in.n_rows - 1, (long long)nnz);
+  ARG_CHECK(nnz == 0 || (in.indices && in.values), "shard %d: a sparse shard with entries needs indices and values", s);
+  h->indices = in.indices;
+  h->values = in.values;
+  if (nnz > 0 && device >= 0 && is_device_ptr(in.indices, device)) {
+    h->ix.resize((size_t)nnz);
+    STK_HIP_CHECK(hipMemcpy(h->ix.data(), in.indices, sizeof(int32_t) * h->ix.size(), hipMemcpyDefault));
+    h->indices = h->ix.data();
+  }
+  if (nnz > 0 && device >= 0 && is_device_ptr(in.values, device)) {
+    h->vv.resize((size_t)nnz);
+    STK_HIP_CHECK(hipMemcpy(h->vv.data(), in.values, sizeof(double) * h->vv.size(), hipMemcpyDefault));
+    h->values = h->vv.data();
+  }
+  return STK_OK;
+}
+
+// The checks of include/stark_hip.h (stk_shard_sparse), each naming the shard and the row, then the padded rows:
+// K = the longest row, idx / val [n_rows][K], a short row filled up with (0, 0.0).  Nothing reaches the device
+// before every index is known to lie in [0, d).
+static int csr_pad_rows(int s, const stk_shard_sparse& in, const CsrHost& h, std::vector<int32_t>* idx, std::vector<double>* val,
+                        int* K) {
+  const int d = in.n_cols;
+  const int64_t n = in.n_rows;
+  ARG_CHECK(h.indptr[0] == 0, "shard %d: row 0: indptr[0] = %lld; indptr runs from 0 to the number of entries", s,
+            (long long)h.indptr[0]);
+  int64_t kmax = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    const int64_t e0 = h.indptr[r], e1 = h.indptr[r + 1];
+    ARG_CHECK(e1 >= e0, "shard %d: row %lld: indptr decreases (%lld after %lld)", s, (long long)r, (long long)e1, (long long)e0);
+    ARG_CHECK(e1 <= h.indptr[n], "shard %d: row %lld: indptr %lld passes the number of entries %lld", s, (long long)r, (long long)e1,
+              (long long)h.indptr[n]);
+    for (int64_t e = e0; e < e1; ++e) {
+      const int32_t j = h.indices[e];
+      ARG_CHECK(j >= 0 && j < d, "shard %d: row %lld: index %d is outside [0, %d)", s, (long long)r, j, d);
+      ARG_CHECK(e == e0 || j > h.indices[e - 1],
+                "shard %d: row %lld: indices must be strictly increasing within a row (%d after %d): sort them and sum duplicates", s,
+                (long long)r, j, h.indices[e - 1]);
+      ARG_CHECK(std::isfinite(h.values[e]), "shard %d: row %lld: the value at column %d is not finite (%g)", s, (long long)r, j,
+                h.values[e]);
+    }
+    kmax = std::max(kmax, e1 - e0);
+  }
+  *K = (int)kmax;   // <= d: a row's indices are distinct and in range
+  idx->assign((size_t)n * kmax, 0);
+  val->assign((size_t)n * kmax, 0.0);
+  for (int64_t r = 0; r < n; ++r)
+    for (int64_t e = h.indptr[r]; e < h.indptr[r + 1]; ++e) {
+      (*idx)[(size_t)(r * kmax + (e - h.indptr[r]))] = h.indices[e];
+      (*val)[(size_t)(r * kmax + (e - h.indptr[r]))] = h.values[e];
+    }
+  return STK_OK;
+}
+
+static int sparse_shard_dims(int s, int family, const stk_shard_sparse& in, int d0) {
+  ARG_CHECK(is_sweep_family(family), "a sparse model is one of the six regression families, not the %s family (%d)", family_name(family),
+            family);
+  ARG_CHECK(in.n_cols > 0 && in.n_cols <= 1024, "shard %d: n_cols %d unsupported (1..1024)", s, in.n_cols);
+  ARG_CHECK(in.n_cols == d0, "shard %d: n_cols %d differs from shard 0 (%d)", s, in.n_cols, d0);
+  return STK_OK;
+}
+
+// Shard s of a sparse model: validated on the host, padded, copied to the device, appended to m->sh and m->sp.
+static int upload_shard_sparse(stk_model* m, int s, const stk_shard_sparse& in) {
+  RC(sparse_shard_dims(s, m->family, in, m->d));
+  CsrHost h;
+  RC(csr_host(s, in, m->ctx->device, &h));
+  std::vector<int32_t> idx;
+  std::vector<double> val;
+  SpShardDev sp{};
+  int K = 0;
+  RC(csr_pad_rows(s, in, h, &idx, &val, &K));
+  sp.K = K;
+  ShardDev sd{};
+  sd.n = in.n_rows;
+  sd.d = in.n_cols;
+  RC(family_dims(m->family, in.n_rows, sd.d, &sd.D, &sd.P));
+  if (idx.empty()) {   // K = 0: nothing to read, but a pointer to hand over
+    idx.push_back(0);
+    val.push_back(0.0);
+  }
+  const int64_t before = m->bytes;
+  int rc = upload(m, idx.data(), idx.size(), &sp.idx);
+  if (rc == STK_OK) rc = upload(m, val.data(), val.size(), &sp.val);
+  const hipError_t e = hipStreamSynchronize(m->ctx->stream);   // idx and val are locals: a started copy must have read them
+  RC(rc);
+  STK_HIP_CHECK(e);
+  m->bytes = before + 12 * (int64_t)K * in.n_rows;
+  const stk_shard ys{in.n_rows, in.n_cols, nullptr, in.y, in.y_int, nullptr};
+  RC(upload_regression_y(m, s, ys, &sd));
+  m->sh.push_back(sd);
+  m->sp.push_back(sp);
+  m->sp_nnz.push_back(h.indptr[in.n_rows]);
+  return STK_OK;
+}
+
+static int upload_sp_table(stk_model* m) {
+  RC(m->sp_dev.ensure(sizeof(SpShardDev) * m->sp.size()));
+  STK_HIP_CHECK(hipMemcpyAsync(m->sp_dev.p, m->sp.data(), sizeof(SpShardDev) * m->sp.size(), hipMemcpyHostToDevice, m->ctx->stream));
+  STK_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
   return STK_OK;
 }
 
@@ -295,6 +429,7 @@ void model_release(stk_model* m) {
   for (auto& b : m->bufs) b.release();
   m->sh_dev.release();
   m->nb_dev.release();
+  m->sp_dev.release();
   delete m;
   ctx_release(c);
 }
@@ -304,6 +439,12 @@ void model_release(stk_model* m) {
 static uint64_t fp_shard_header(int family, int64_t n_rows, int n_cols) {
   const uint64_t h[3] = {(uint64_t)family, (uint64_t)n_rows, (uint64_t)(family == STK_SCHOOLS ? 0 : n_cols)};
   return stk_fp_words_host(h, 3, 8, 0, 0);
+}
+
+// A sparse shard's header: four words, the longest row K among them.
+static uint64_t fp_sparse_header(int family, int64_t n_rows, int n_cols, int K) {
+  const uint64_t h[4] = {(uint64_t)family, (uint64_t)n_rows, (uint64_t)n_cols, (uint64_t)K};
+  return stk_fp_words_host(h, 4, 8, 0, 0);
 }
 
 // One kernel per data array of the shard, all adding into one zeroed device word; cached.
@@ -321,13 +462,19 @@ int model_fingerprint(stk_model* m, int shard, uint64_t* out) {
     unsigned long long* sum = ctx->scratch[SCR_FP_SUM].as<unsigned long long>();
     STK_HIP_CHECK(hipMemsetAsync(sum, 0, sizeof(*sum), st));
     if (s.x) STK_HIP_CHECK(stk_launch_fp_words(s.x, s.n * s.d, 8, 1, 0, sum, st));
+    if (m->sparse) {   // the padded rows, under tags of their own
+      const SpShardDev& sp = m->sp[shard];
+      STK_HIP_CHECK(stk_launch_fp_words(sp.idx, s.n * sp.K, 4, 5, 0, sum, st));
+      STK_HIP_CHECK(stk_launch_fp_words(sp.val, s.n * sp.K, 8, 6, 0, sum, st));
+    }
     if (s.y) STK_HIP_CHECK(stk_launch_fp_words(s.y, s.n, 8, 2, 0, sum, st));
     if (s.yi) STK_HIP_CHECK(stk_launch_fp_words(s.yi, s.n, 4, 3, 0, sum, st));
     if (m->family == STK_SCHOOLS) STK_HIP_CHECK(stk_launch_fp_words(s.sigma, s.n, 8, 4, 0, sum, st));   // the only family with a sigma array
     unsigned long long v = 0;
     STK_HIP_CHECK(hipMemcpyAsync(&v, sum, sizeof(v), hipMemcpyDeviceToHost, st));
     STK_HIP_CHECK(hipStreamSynchronize(st));
-    m->fp[shard] = stk_fp_fmix(fp_shard_header(m->family, s.n, s.d) + (uint64_t)v);
+    const uint64_t head = m->sparse ? fp_sparse_header(m->family, s.n, s.d, m->sp[shard].K) : fp_shard_header(m->family, s.n, s.d);
+    m->fp[shard] = stk_fp_fmix(head + (uint64_t)v);
     m->fp_ok[shard] = 1;
   }
   *out = m->fp[shard];
@@ -343,6 +490,50 @@ int stk_model_create(stk_ctx* ctx, int family, const stk_shard* shards, int nsha
   int rc = STK_OK;
   for (int s = 0; s < nshards && rc == STK_OK; ++s) rc = upload_shard(m, s, shards[s]);
   return model_finish(m, rc, out);
+}
+
+int stk_model_create_sparse(stk_ctx* ctx, int family, const stk_shard_sparse* shards, int nshards, stk_model** out) {
+  ARG_CHECK(ctx && shards && out && nshards > 0, "stk_model_create_sparse: bad arguments");
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  stk_model* m = model_new(ctx, family, nshards, shards[0].n_cols);
+  m->sparse = true;
+  int rc = STK_OK;
+  for (int s = 0; s < nshards && rc == STK_OK; ++s) rc = upload_shard_sparse(m, s, shards[s]);
+  if (rc == STK_OK) rc = upload_sp_table(m);
+  return model_finish(m, rc, out);
+}
+
+int stk_model_sparse_info(const stk_model* m, int shard, int64_t out[3]) {
+  ARG_CHECK(m && out && shard >= 0 && shard < m->nshards, "stk_model_sparse_info: bad arguments");
+  ARG_CHECK(m->sparse, "stk_model_sparse_info: the model is dense (stk_model_create)");
+  out[0] = m->sp[shard].K;
+  out[1] = m->sp_nnz[shard];
+  out[2] = 12 * (int64_t)m->sp[shard].K * m->sh[shard].n;
+  return STK_OK;
+}
+
+int stk_shard_fingerprint_sparse_host(int family, const stk_shard_sparse* sh, uint64_t* out) {
+  ARG_CHECK(sh && out, "stk_shard_fingerprint_sparse_host: bad arguments");
+  RC(sparse_shard_dims(0, family, *sh, sh->n_cols));
+  CsrHost h;
+  RC(csr_host(0, *sh, -1, &h));
+  std::vector<int32_t> idx;
+  std::vector<double> val;
+  int K = 0;
+  RC(csr_pad_rows(0, *sh, h, &idx, &val, &K));
+  uint64_t acc = fp_sparse_header(family, sh->n_rows, sh->n_cols, K);
+  acc += stk_fp_words_host(idx.data(), sh->n_rows * K, 4, 5, 0) + stk_fp_words_host(val.data(), sh->n_rows * K, 8, 6, 0);
+  if (family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN) {
+    ARG_CHECK(sh->y_int, "stk_shard_fingerprint_sparse_host: the %s family needs y_int", family_name(family));
+    ARG_CHECK(family == STK_LOGREG || !sh->y, "stk_shard_fingerprint_sparse_host: the %s family takes its counts in y_int alone; y must be NULL",
+              family_name(family));
+    acc += stk_fp_words_host(sh->y_int, sh->n_rows, 4, 3, 0);
+  } else {
+    ARG_CHECK(sh->y, "stk_shard_fingerprint_sparse_host: the %s family needs y", family_name(family));
+    acc += stk_fp_words_host(sh->y, sh->n_rows, 8, 2, 0);
+  }
+  *out = stk_fp_fmix(acc);
+  return STK_OK;
 }
 
 int stk_gen_beta(uint64_t seed, int32_t d, double* beta) {

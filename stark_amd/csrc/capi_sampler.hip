@@ -105,7 +105,7 @@ static int check_config(const stk_model* m, const stk_config* cfg, int nch) {
               "lower max_depth",
               m->Dmax - 2, cfg->max_depth, cfg->nuts_criterion, lds, BIG_LDS_BYTES);
   } else {
-    ARG_CHECK(!chain_batches(cfg->chains, m->d).empty(), "no sweep covers %d covariates (1..1024)", m->d);
+    ARG_CHECK(!model_chain_batches(m, cfg->chains).empty(), "no sweep covers %d covariates (1..1024)", m->d);
   }
   return STK_OK;
 }
@@ -341,7 +341,7 @@ int stk_sampler_create(stk_model* m, const stk_config* cfg, stk_sampler** out) {
   if (cfg->metric == 1 && cfg->inv_metric_dense)
     RC(dense_metric_host(cfg->inv_metric_dense, m->Dmax, (m->Dmax + 7) / 8 * 8, &minv_host, &chol_host));
   ChainPlan plan;   // regressions: the chain batches, each with its sweeps grouped by consecutive shards of equal n
-  if (m->family != STK_SCHOOLS) RC(chain_plan(m, chain_batches(cfg->chains, m->d), 0, m->nshards, &plan));
+  if (m->family != STK_SCHOOLS) RC(chain_plan(m, model_chain_batches(m, cfg->chains), 0, m->nshards, &plan));
   stk_sampler* s = new stk_sampler();
   s->m = m;
   m->refs++;
@@ -394,6 +394,7 @@ int stk_sampler_grad_block(stk_sampler* s, int64_t* count) {
 
 int stk_sampler_set_allreduce(stk_sampler* s, stk_allreduce_fn fn, void* user, double* dev_block) {
   ARG_CHECK(s, "stk_sampler_set_allreduce: NULL sampler");
+  REFUSE_SPARSE(s->m, "stk_sampler_set_allreduce (full-data mode)");
   ARG_CHECK(s->m->family == STK_LOGREG,
             "full-data mode is logistic-only (a purely additive log density: flat priors, no Jacobian term), not for "
             "the %s family (%d)", family_name(s->m->family), s->m->family);

@@ -88,8 +88,10 @@ __global__ __launch_bounds__(FP_BLOCK) void k_fp_words(const void* buf, int64_t 
   }
 }
 
-static const uint64_t kFpTag[5] = {0x243F6A8885A308D3ull, 0x13198A2E03707344ull, 0xA4093822299F31D0ull,
-                                   0x082EFA98EC4E6C89ull, 0x452821E638D01377ull};
+// (5, 6: a sparse shard's padded columns and values -- the library's own; stk_fingerprint_words takes 0..4)
+static const uint64_t kFpTag[7] = {0x243F6A8885A308D3ull, 0x13198A2E03707344ull, 0xA4093822299F31D0ull,
+                                   0x082EFA98EC4E6C89ull, 0x452821E638D01377ull, 0xBE5466CF34E90C6Cull,
+                                   0xC0AC29B7C97C50DDull};
 
 }  // namespace stk
 

@@ -19,6 +19,8 @@ enum SweepKind : int {
   SWEEP_16 = 4,       // k_sweep16     C = 16, d <= 128 (sweep16.hip)
   SWEEP_GEMM64 = 5,   // k_qt_swizzle + k_gemm_fwd + k_gemm_bwd, C = 64
   SWEEP_16W = 6,      // k_sweep16w    C = 16, 128 < d <= 1024 (sweep16w.hip)
+  SWEEP_SPARSE = 7,   // k_sweep_sp    sparse (padded-row) shards: C <= 16, any d <= 1024 (sweep_sparse.hip); never
+                      // chosen by stk_sweep_plan, whose numbers keep their dense meaning
 };
 
 // The kernel and launch shape of one sweep over a shard of n rows: a function of (n, d, C) only,
@@ -30,11 +32,22 @@ struct SweepLaunch {
   int T;              // rows per tile
   int G;              // chunks per shard
   size_t lds;         // dynamic LDS bytes per block (kind 5: pass F's; pass B sizes its own)
-  int ld;             // kinds 1, 2: row stride of the X tile in LDS, in doubles
+  int ld;             // kinds 1, 2: row stride of the X tile in LDS, in doubles; kind 7: bytes of the entry stage in LDS
   int ring;           // kind 3: ring slots per wave
-  int waves;          // kind 6: waves per block (= column slabs)
+  int waves;          // kind 6: waves per block (= column slabs); kind 7: private gradient copies per block
   int64_t Rrows;      // kind 5: rows of the residual matrix R per shard (n rounded up to 64)
   size_t ws_bytes;    // kind 5: workspace bytes one shard needs (beta^T image + R); else 0
+};
+
+// What a sparse shard adds to its ShardDev (whose x is null): the padded rows (ELL) of its design matrix.  Row r's
+// K slots are idx[r K .. r K + K) and val[r K ..): the row's entries by strictly increasing column, then (0, 0.0).
+// A side table of the model, handed to the launch as SweepCall::sp: ShardDev and SweepArgs stay as every dense kernel
+// was built with.
+struct SpShardDev {
+  const int32_t* idx;   // [n][K]
+  const double* val;    // [n][K]
+  int32_t K;            // the shard's longest row (0: an all-zero matrix)
+  int32_t pad_;
 };
 
 // What one launch adds to its plan: where the data is and which batch of the shard's chains this is.
@@ -51,6 +64,7 @@ struct SweepCall {
   int Ct, c0;             // chains per shard in q / lp / grad, first chain of this batch
   const NbShardDev* nb = nullptr;   // STK_NEGBIN: the model's [nshards] count tables and phi priors (the reduce reads them);
                                     // STK_GAMMA: the shards' L = sum log y and the shape prior, in the same entries
+  const SpShardDev* sp = nullptr;   // a sparse model's [nshards] padded rows (kind 7 reads them); else NULL
 };
 
 // Columns of a chunk's partial row per chain: d alpha, d beta[1..d], the lp sum -- and the family's third
@@ -95,6 +109,16 @@ hipError_t stk_launch_gemm_fwd(const stk::SweepArgs& A, int d, int nblocks, size
 template <int FAM>
 hipError_t stk_launch_reduce(const stk::SweepArgs& A, const stk::NbShardDev* nb, int nchains, int d, double* lp_out,
                              double* g_out, int C, hipStream_t st);
+
+// ---- sweep_sparse.hip (sparse shards: C in {1, 2, 4, 8, 16}, 16 up to d = 512; any d <= 1024): the batch sizes it
+// covers, its plan (a function of (n, d, C) alone: the chunks of n alone), its launch
+bool stk_sweep_sparse_supported(int C, int d);
+stk::SweepLaunch stk_sweep_plan_sparse(int64_t n, int d, int C);
+hipError_t stk_launch_sweep_sparse(int family, const stk::SweepLaunch& p, int shard0, int nsh, const stk::SweepCall& c,
+                                   hipStream_t st);
+template <int FAM>
+hipError_t stk_launch_sweep_sp(const stk::SweepLaunch& p, const stk::SweepArgs& A, const stk::SpShardDev* sp, int nblocks,
+                               hipStream_t st);
 
 // ---- sweep16.hip: shapes k_sweep16 covers, its LDS bytes, its launch
 bool stk_sweep16_supported(int d);

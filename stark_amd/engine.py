@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_NEGBIN, STK_POISSON, STK_SCHOOLS, STK_STUDENT, STK_GAMMA, Config, RunInfo, Shard,
-                   StarkHipError, check)
+                   ShardSparse, StarkHipError, check)
 
 FAMILIES = {"schools": STK_SCHOOLS, "linear": STK_LINREG, "logistic": STK_LOGREG, "poisson": STK_POISSON,
             "neg_binomial": STK_NEGBIN, "student_t": STK_STUDENT, "gamma": STK_GAMMA}
@@ -177,15 +177,86 @@ def make_config(num_warmup=1000, num_samples=1000, chains=1, max_depth=10, adapt
     return c
 
 
-def chain_batches(chains: int, n_cols: int) -> list[int]:
+def chain_batches(chains: int, n_cols: int, sparse: bool = False) -> list[int]:
     """The contiguous chain batches that ``chains`` chains per shard of a regression with ``n_cols``
     covariates run as (stk_chain_batches): greedy, largest first, over the single-launch sizes
-    {64, 16, 8, 4, 2, 1} a sweep covers at that width.  Host only: needs no device."""
+    {64, 16, 8, 4, 2, 1} a sweep covers at that width.  ``sparse=True``: those of a sparse shard
+    (stk_chain_batches_sparse), over {16, 8, 4, 2, 1} up to 512 covariates and {8, 4, 2, 1} past
+    them.  Host only: needs no device."""
     sizes = np.zeros(max(int(chains), 1), np.int32)
-    n = _lib.load().stk_chain_batches(int(chains), int(n_cols), sizes.ctypes.data, sizes.size)
+    fn = _lib.load().stk_chain_batches_sparse if sparse else _lib.load().stk_chain_batches
+    n = fn(int(chains), int(n_cols), sizes.ctypes.data, sizes.size)
     if n < 0:
         check(n)
     return [int(v) for v in sizes[:n]]
+
+
+def sparse_launch(n_rows: int, n_cols: int, K: int, chains: int) -> dict:
+    """The sparse sweep that one batch of ``chains`` chains runs over a shard of ``n_rows`` x ``n_cols``
+    whose longest row has ``K`` entries (stk_sweep_launch_info_sparse): ``kind`` (7), rows per tile ``T``,
+    ``stage_bytes`` of the entry stage in LDS, chunks per shard ``G`` (a function of ``n_rows`` alone),
+    ``lds_bytes``, the private gradient ``copies`` per block, ``staged`` (1: a tile's entries fit the
+    stage) and ``ell_bytes``, the shard's padded rows (12 K n_rows).  Host only: needs no device."""
+    out = np.zeros(8, np.int64)
+    check(_lib.load().stk_sweep_launch_info_sparse(int(n_rows), int(n_cols), int(K), int(chains), out.ctypes.data))
+    return dict(zip(("kind", "T", "stage_bytes", "G", "lds_bytes", "copies", "staged", "ell_bytes"), (int(v) for v in out)))
+
+
+def is_sparse_shard(sh) -> bool:
+    """Whether a shard dict holds a sparse design matrix: ``"x_csr"``, or a scipy.sparse ``"x"``."""
+    return "x_csr" in sh or (hasattr(sh.get("x"), "tocsr") and not isinstance(sh.get("x"), np.ndarray))
+
+
+def canonical_csr(sh):
+    """A sparse shard's design matrix as the canonical CSR triple the library takes: ``(indptr int64,
+    indices int32, values float64, d)`` with the indices of every row sorted and duplicates summed;
+    explicit zeros are kept.  ``sh["x"]``: a scipy.sparse matrix of any format; or ``sh["x_csr"]``: a raw
+    ``(indptr, indices, values)`` triple with ``sh["d"]`` columns (needs no scipy).  Out-of-range or
+    negative indices are left as they are: the library names their shard and row."""
+    if "x_csr" in sh:
+        indptr, indices, values = sh["x_csr"]
+        d = int(sh["d"])
+        indptr = np.ascontiguousarray(indptr, np.int64)
+        indices = np.asarray(indices)
+        if indices.size and (indices.min() < np.iinfo(np.int32).min or indices.max() > np.iinfo(np.int32).max):
+            raise ValueError("x_csr: a column index does not fit int32")
+        indices = np.ascontiguousarray(indices, np.int32)
+        values = np.ascontiguousarray(values, np.float64)
+        if indptr.ndim != 1 or indptr.size < 2 or indices.shape != values.shape or indices.ndim != 1:
+            raise ValueError("x_csr: need indptr [n + 1] and equal-length indices and values")
+    else:
+        m = sh["x"].tocsr()
+        d = int(m.shape[1])
+        indptr = np.ascontiguousarray(m.indptr, np.int64)
+        indices = np.ascontiguousarray(m.indices, np.int32)
+        values = np.ascontiguousarray(m.data, np.float64)
+    n = indptr.size - 1
+    if indptr[0] != 0 or np.any(np.diff(indptr) < 0) or indptr[-1] != indices.size:
+        return indptr, indices, values, d   # not a CSR row structure: the library says which row
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    order = np.lexsort((indices, rows))      # stable: equal (row, column) keep their order, so the sums are reproducible
+    rows, cols, vals = rows[order], indices[order], values[order]
+    first = np.ones(rows.size, bool)
+    first[1:] = (rows[1:] != rows[:-1]) | (cols[1:] != cols[:-1])
+    start = np.flatnonzero(first)
+    vals = np.add.reduceat(vals, start) if start.size else vals
+    rows, cols = rows[first], cols[first]
+    out_ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(rows, minlength=n), out=out_ptr[1:])
+    return out_ptr, np.ascontiguousarray(cols, np.int32), np.ascontiguousarray(vals, np.float64), d
+
+
+def _host_shard_sparse(family, sh):
+    """One sparse shard dict as a ``stk_shard_sparse`` of host pointers, plus the arrays that keep them alive."""
+    if family == STK_SCHOOLS:
+        raise ValueError("a sparse design matrix is for the regression families, not for schools")
+    indptr, indices, values, d = canonical_csr(sh)
+    n = indptr.size - 1
+    y, is_int = _regression_y(family, sh["y"], n)      # the y rules of the dense path, by its own code
+    shard = ShardSparse(n, d, indptr.ctypes.data, indices.ctypes.data if indices.size else None,
+                        values.ctypes.data if values.size else None, None if is_int else y.ctypes.data,
+                        y.ctypes.data if is_int else None)
+    return shard, [indptr, indices, values, y]
 
 
 def sweep_launch(n_rows: int, n_cols: int, chains: int) -> dict:
@@ -197,6 +268,26 @@ def sweep_launch(n_rows: int, n_cols: int, chains: int) -> dict:
     out = np.zeros(6, np.int64)
     check(_lib.load().stk_sweep_launch_info(int(n_rows), int(n_cols), int(chains), out.ctypes.data))
     return dict(zip(("kind", "T", "LD", "G", "lds_bytes", "ws_bytes_per_shard"), (int(v) for v in out)))
+
+
+def _regression_y(family, y, n_rows):
+    """A regression shard's y as the array the library takes, checked for the family, and whether it is the int32
+    ``y_int`` (logistic, poisson, neg_binomial) or the float64 ``y``.  Dense and sparse shards share it."""
+    if family == STK_LOGREG:
+        y = np.ascontiguousarray(y, np.int32)
+        if np.any((y != 0) & (y != 1)):
+            raise ValueError("bernoulli_logit: y must be 0 or 1")
+    elif family in (STK_POISSON, STK_NEGBIN):
+        y = np.asarray(y)
+        if y.dtype.kind not in "iuf" or not np.all(y == np.round(y)) or np.any(y < 0) or np.any(y > np.iinfo(np.int32).max):
+            raise ValueError(("poisson_log" if family == STK_POISSON else "neg_binomial_2_log") +
+                             ": y must hold integers in 0 .. 2^31 - 1")
+        y = np.ascontiguousarray(y, np.int32)
+    else:
+        y = np.ascontiguousarray(y, np.float64)
+    if y.shape[0] != n_rows:
+        raise ValueError("x and y row counts differ")
+    return y, family in (STK_LOGREG, STK_POISSON, STK_NEGBIN)
 
 
 def _host_shard(family, sh):
@@ -211,23 +302,8 @@ def _host_shard(family, sh):
     x = np.ascontiguousarray(sh["x"], np.float64)
     if x.ndim != 2:
         raise ValueError("regression shard: x must be N x K")
-    if family == STK_LOGREG:
-        y = np.ascontiguousarray(sh["y"], np.int32)
-        if np.any((y != 0) & (y != 1)):
-            raise ValueError("bernoulli_logit: y must be 0 or 1")
-        shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, None, y.ctypes.data, None)
-    elif family in (STK_POISSON, STK_NEGBIN):
-        y = np.asarray(sh["y"])
-        if y.dtype.kind not in "iuf" or not np.all(y == np.round(y)) or np.any(y < 0) or np.any(y > np.iinfo(np.int32).max):
-            raise ValueError(("poisson_log" if family == STK_POISSON else "neg_binomial_2_log") +
-                             ": y must hold integers in 0 .. 2^31 - 1")
-        y = np.ascontiguousarray(y, np.int32)
-        shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, None, y.ctypes.data, None)
-    else:
-        y = np.ascontiguousarray(sh["y"], np.float64)
-        shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, y.ctypes.data, None, None)
-    if y.shape[0] != x.shape[0]:
-        raise ValueError("x and y row counts differ")
+    y, is_int = _regression_y(family, sh["y"], x.shape[0])
+    shard = Shard(x.shape[0], x.shape[1], x.ctypes.data, None if is_int else y.ctypes.data, y.ctypes.data if is_int else None, None)
     return shard, [x, y]
 
 
@@ -273,8 +349,12 @@ def shard_fingerprint(family, shard) -> np.uint64:
     fam = FAMILIES.get(family, family)
     if fam not in FAMILY_NAMES:
         raise ValueError(f"unknown model family {family!r}")
-    sh, _held = _host_shard(fam, shard)
     out = ctypes.c_uint64()
+    if is_sparse_shard(shard):   # the sparse twin (stk_shard_fingerprint_sparse_host): never the dense shard's value
+        sh, _held = _host_shard_sparse(fam, shard)
+        check(_lib.load().stk_shard_fingerprint_sparse_host(fam, ctypes.byref(sh), ctypes.byref(out)))
+        return np.uint64(out.value)
+    sh, _held = _host_shard(fam, shard)
     check(_lib.load().stk_shard_fingerprint_host(fam, ctypes.byref(sh), ctypes.byref(out)))
     return np.uint64(out.value)
 
@@ -295,6 +375,7 @@ class Model:
         elif nu is not None:
             raise ValueError(f"nu= is for the student_t family, not for the {FAMILY_NAMES.get(self.family, self.family)} family")
         self.nu = None if nu is None else float(nu)
+        self.sparse = False   # True: the design matrices are kept as padded rows (a scipy.sparse "x" or "x_csr")
         if _handle is not None:
             self._h = _handle
         else:
@@ -314,6 +395,18 @@ class Model:
 
     def _create(self, shards):
         keep = []
+        nsp = sum(1 for sh in shards if is_sparse_shard(sh))
+        if nsp:   # a sparse model (stk_model_create_sparse); dense shards take the path below, as ever
+            if nsp != len(shards):
+                raise ValueError("a model is all sparse or all dense: some shards hold a sparse x and some a dense one")
+            sarr = (ShardSparse * len(shards))()
+            for i, sh in enumerate(shards):
+                sarr[i], held = _host_shard_sparse(self.family, sh)
+                keep += held
+            h = ctypes.c_void_p()
+            check(_lib.load().stk_model_create_sparse(self.ctx._h, self.family, sarr, len(shards), ctypes.byref(h)))
+            self.sparse = True
+            return h
         arr = (Shard * len(shards))()
         for i, sh in enumerate(shards):
             arr[i], held = _host_shard(self.family, sh)
@@ -345,6 +438,13 @@ class Model:
         b = np.empty(n_cols, np.float64)
         check(_lib.load().stk_gen_beta(int(data_seed), int(n_cols), b.ctypes.data))
         return b
+
+    def sparse_info(self, shard: int) -> dict:
+        """A sparse model's shard (stk_model_sparse_info): ``K`` (its longest row, the padded width), ``nnz``
+        (the entries handed over) and ``bytes``, the device bytes of its padded rows, 12 K n_rows."""
+        out = np.zeros(3, np.int64)
+        check(_lib.load().stk_model_sparse_info(self._h, int(shard), out.ctypes.data))
+        return {"K": int(out[0]), "nnz": int(out[1]), "bytes": int(out[2])}
 
     def device_bytes(self) -> int:
         v = ctypes.c_int64()
@@ -390,14 +490,14 @@ class Model:
             return {"y": y}
         yint = self.family in (STK_LOGREG, STK_POISSON, STK_NEGBIN)
         d = D - (2 if self.family in (STK_LINREG, STK_NEGBIN, STK_STUDENT, STK_GAMMA) else 1)
-        x = np.empty((n, d))
+        x = np.empty((n, 0 if self.sparse else d))   # a sparse model keeps no dense x: y alone comes back
         if yint:
             y = np.empty(n, np.int32)
             check(lib.stk_model_copy_data(self._h, shard, x.ctypes.data, None, y.ctypes.data))
         else:
             y = np.empty(n)
             check(lib.stk_model_copy_data(self._h, shard, x.ctypes.data, y.ctypes.data, None))
-        return {"x": x, "y": y}
+        return {"y": y} if self.sparse else {"x": x, "y": y}
 
     def log_density_grad(self, shard: int, q):
         """lp and grad lp (Stan log_prob, propto, jacobian) at C points (C x D)."""

@@ -209,7 +209,14 @@ def pack_data(family: str, data: dict, nu=None) -> dict:
             raise ValueError("schools data: sigma must be positive (real<lower=0> sigma[J])")
         return {"y": y, "sigma": s}
     N, K = int(data["N"]), int(data["K"])
-    x = np.asarray(data["x"], np.float64).reshape(N, K)
+    if hasattr(data["x"], "tocsr") and not isinstance(data["x"], np.ndarray):
+        # a scipy.sparse design matrix goes through as it is (engine.Model keeps it as padded rows); N and K are
+        # checked against its shape, y below as for dense rows
+        x = data["x"]
+        if tuple(x.shape) != (N, K):
+            raise ValueError(f"sparse x has shape {tuple(x.shape)}, the data say N = {N}, K = {K}")
+    else:
+        x = np.asarray(data["x"], np.float64).reshape(N, K)
     if family == "logistic":
         y = np.asarray(data["y"]).reshape(-1)
         if y.shape[0] != N:

@@ -134,6 +134,16 @@ def _refuse_analysis(family, what):
                          "combiner='semiparametric'")
 
 
+def _refuse_sparse(datas, what):
+    """ValueError, before a model is built, where `what` is asked of partitions whose design matrix is sparse
+    (a scipy.sparse data["x"]): the sparse storage serves the sampler and the combiners only."""
+    for d in datas:
+        if engine.is_sparse_shard({"x": d.get("x")}):
+            raise ValueError(f"{what} is not available on sparse data: the analysis sweeps (Hessian, log-predictive, "
+                             "PSIS-LOO, per-draw log density, bootstrap, posterior predictive) read dense rows; sparse "
+                             "partitions sample and combine (concensusWeight with weights='sample', distribute)")
+
+
 def unconstrain_draws(family, samples, n_cols=None):
     """The P x S constrained matrix ``concensusWeight`` returns (rows alpha, beta[1..d], [sigma], lp__)
     as the [S][D] unconstrained draws ``engine.Model.log_predictive`` scores: lp__ is dropped and
@@ -312,6 +322,8 @@ class Stark:
         """The GPU run behind _sample_partitions: every extract() row of every partition.
         laplace: the shards' Laplace covariances are fitted before the model is closed
         (self._laplace_cov, one per data dict)."""
+        if laplace:
+            _refuse_sparse(datas, "weights='laplace'")
         priors = dict(getattr(self, "priors", None) or {})
         model_kw = {}
         if self.family == "student_t":
@@ -361,6 +373,7 @@ class Stark:
         rows as there), S = ceil((iter - warmup) / thin) * chains; weights[i] the Laplace precision of the
         selected rows other than lp__ (want_weights, from the SAME fit) or None; diagnostics[i] the 1 x 2
         array [khat, ess].  permuted is accepted and ignored: the draws are exchangeable."""
+        _refuse_sparse(datas, "method='laplace'")
         rows = [frontend.select_pars(self.family, d, pars, include) for d in datas]   # validates first
         cfg = sampling_config(self.family, datas, **kwargs)
         S = -(-cfg["num_samples"] // cfg["thin"]) * cfg["chains"]
@@ -604,6 +617,7 @@ class Stark:
         rank, ws = dist.world()
         mine = dist.local_partitions(len(parts), rank, ws)
         datas = [self.prepare_data_callback(list(parts[p])) for p in mine]
+        _refuse_sparse(datas, "waic")
         q = unconstrain_draws(self.family, samples, n_cols=int(datas[0]["K"]) if datas else None)
         local = {}
         if datas:
@@ -646,6 +660,7 @@ class Stark:
         rank, ws = dist.world()
         mine = dist.local_partitions(len(parts), rank, ws)
         datas = [self.prepare_data_callback(list(parts[p])) for p in mine]
+        _refuse_sparse(datas, "loo")
         q = unconstrain_draws(self.family, samples, n_cols=int(datas[0]["K"]) if datas else None)
         local = {}
         if datas:
@@ -680,6 +695,7 @@ class Stark:
         rank, ws = dist.world()
         mine = dist.local_partitions(len(parts), rank, ws)
         datas = [self.prepare_data_callback(list(parts[p])) for p in mine]
+        _refuse_sparse(datas, "ppc")
         for p, d in zip(mine, datas):
             if int(d["K"]) > self.PPC_MAX_COLS:
                 raise ValueError(f"ppc covers at most {self.PPC_MAX_COLS} covariates; partition {p} has K = "
@@ -732,6 +748,7 @@ class Stark:
         rank, ws = dist.world()
         mine = dist.local_partitions(len(parts), rank, ws)
         datas = [self.prepare_data_callback(list(parts[p])) for p in mine]
+        _refuse_sparse(datas, "bootstrap")
         for p, d in zip(mine, datas):
             if int(d["K"]) > self.BOOT_MAX_COLS:
                 raise ValueError(f"bootstrap covers at most {self.BOOT_MAX_COLS} covariates; partition {p} has K = "
