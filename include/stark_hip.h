@@ -93,7 +93,8 @@ enum {
 };
 
 /* Model families. */
-enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEGBIN = 5, STK_STUDENT = 6, STK_GAMMA = 7 };
+enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEGBIN = 5, STK_STUDENT = 6, STK_GAMMA = 7,
+       STK_CATEGORICAL = 8 };
 /* STK_POISSON: y ~ poisson_log(alpha + x * beta), the unconstrained parameters (alpha, beta[1..d]) in
  * the logistic layout (D = d + 1, P = d + 2: alpha, beta, lp__).  With eta_i = alpha + x_i . beta and
  * mu_i = exp(eta_i), lp = sum_i (y_i eta_i - mu_i) (+ the normal(0, s) prior terms of
@@ -179,6 +180,28 @@ enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEG
  * fingerprints treat the family as they treat STK_LINREG.  Refused by name with STK_E_ARG, before any work:
  * stk_model_create_synthetic, stk_sampler_set_allreduce and the analysis sweeps (stk_log_density_hessian,
  * stk_log_predictive, stk_loo, stk_log_density_draws, stk_log_density_grad_boot, stk_posterior_predict). */
+/* STK_CATEGORICAL: y[n] ~ categorical_logit(append_row(alpha + x[n] * beta, 0)), softmax regression with K = ncat >= 2
+ * classes (stk_model_set_categories; never a default), G = K - 1 free classes and class K the reference (eta = 0).
+ * The unconstrained point is Stan's own order with nothing constrained: q = [alpha_1 .. alpha_G, beta_1[0 .. d), ...,
+ * beta_G[0 .. d)] -- class g's coefficients are the g-th block of d, the column-major vector of models/categorical.stan
+ * -- so D = G (d + 1) and P = D + 1 (alpha[1..G], beta[1..G d], lp__).  The shard is x and y_int in [1, K] as given.
+ * With eta_ig = alpha_g + x_i . beta_g, m_i = max(0, max_g eta_ig) and s_i = e^{-m_i} + sum_g e^{eta_ig - m_i},
+ *   lp               = sum_i (eta_{i, y_i} - m_i - log s_i)        eta_{i, K} = 0   (+ the priors of stk_model_set_prior)
+ *   d lp / d eta_ig  = 1[y_i = g] - e^{eta_ig - m_i} / s_i          -> d alpha_g = sum_i, d beta_g = X^T (.)
+ * (`~`: nothing to drop).  stk_model_set_prior's normal(0, s) priors apply to every alpha_g and to every beta entry.
+ * The maximum is subtracted so that coefficients of any size that keep eta finite give a finite lp; a NaN eta stays
+ * NaN in lp and the gradient; where an eta is +-inf lp is -inf or NaN, never +inf and never a finite number.
+ * Envelope: G <= 16 and G ceil(d / 16) <= 16 (K = 2 to d = 256, K = 3 to d = 128, K = 5 to d = 64, K = 9 to d = 32,
+ * K = 17 to d = 16), the accumulator tiles of k_sweep_cat (csrc/sweep_cat.hip).  Outside it stk_model_set_categories
+ * returns STK_E_ARG with a message that names K and d, before anything is launched; so do the hooks and
+ * stk_sampler_create for a model that never had its categories set.
+ * Chains run in launches of up to 16: C chains are C / 16 launches of 16 and one of C mod 16
+ * (stk_chain_batches_categorical); a chain's lp and gradient are the same bits in whichever batch and column.
+ * The sampler (any chains, the three metrics, both U-turn criteria, saved states: K is part of a saved state's
+ * geometry), the gradient hooks, stk_model_set_prior, data copy-out and the fingerprints (y as given) work for the
+ * family.  Refused by name with STK_E_ARG, before any work: stk_model_create_sparse, stk_model_create_synthetic,
+ * stk_sampler_set_allreduce, the analysis sweeps (stk_log_density_hessian, stk_log_predictive, stk_loo,
+ * stk_log_density_draws, stk_log_density_grad_boot, stk_posterior_predict) and stk_yrep_host. */
 
 /* One data shard (= one Spark partition, stark/stark.py:35).
  *   schools: n_rows = J, y[J], sigma[J]                   (example/stark_ex.py:8-11)
@@ -190,7 +213,9 @@ enum { STK_SCHOOLS = 1, STK_LINREG = 2, STK_LOGREG = 3, STK_POISSON = 4, STK_NEG
  *            stk_shard_fingerprint_host, instead of one of the two being ignored
  *   negbin : as poisson (x, y_int >= 0, y and sigma NULL)
  *   student: as linreg (x, y)
- *   gamma  : as linreg (x, y), every y finite and > 0                                */
+ *   gamma  : as linreg (x, y), every y finite and > 0
+ *   categorical: x, y_int[n_rows] in [1, K] (checked on the device copy by stk_model_set_categories, which
+ *            names the first row outside); y and sigma must be NULL                  */
 typedef struct {
   int64_t n_rows;
   int32_t n_cols;
@@ -315,6 +340,17 @@ STK_API int stk_gamma_shape_terms_host(double a, double* out2);
  * with the value in the message; any other family is refused by name).  Required before any density,
  * transition or sampler call: there is no default.  Every shard, before sampling. */
 STK_API int stk_model_set_student_nu(stk_model* m, double nu);
+/* STK_CATEGORICAL only: the classes K = ncat >= 2 of y ~ categorical_logit (any other family is refused by name).
+ * Called once, before any density, transition or sampler call: there is no default, and a second call is refused.
+ * It sets D = (K - 1)(d + 1) and P = D + 1 of every shard, refuses a (K, d) outside the envelope
+ * ((K - 1) <= 16, (K - 1) ceil(d / 16) <= 16, (K - 1)(d + 1) <= 1024) with a message that names K and d, and checks
+ * every shard's y_int on the device: the first value outside [1, K] is refused with its shard and row named, and the
+ * model stays without categories. */
+STK_API int stk_model_set_categories(stk_model* m, int32_t ncat);
+/* Whether k_sweep_cat covers K = ncat classes at d covariates (1 / 0), and the launches C chains of such a shard
+ * run as: C / 16 of 16 chains, then one of C mod 16 (the contract of stk_chain_batches).  Host only: no device. */
+STK_API int stk_categorical_supported(int32_t ncat, int32_t d);
+STK_API int stk_chain_batches_categorical(int32_t C, int32_t d, int32_t ncat, int32_t* sizes, int32_t cap);
 /* The two phi-only sums of STK_NEGBIN over n counts y_int >= 0 at phi > 0, computed on the host by the
  * code the device runs (its table builder and term functions): out[0] = sum_i sum_{j < y_i} log1p(j / phi),
  * out[1] = sum_i [psi(y_i + phi) - psi(phi)].  No device is touched. */

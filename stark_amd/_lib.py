@@ -16,6 +16,7 @@ STK_OK = 0
 ERRORS = {-1: "STK_E_ARG", -2: "STK_E_HIP", -3: "STK_E_NOMEM", -4: "STK_E_STATE",
           -5: "STK_E_NUMERIC", -6: "STK_E_NAN", -7: "STK_E_LINALG"}
 STK_SCHOOLS, STK_LINREG, STK_LOGREG, STK_POISSON, STK_NEGBIN, STK_STUDENT, STK_GAMMA = 1, 2, 3, 4, 5, 6, 7
+STK_CATEGORICAL = 8
 N_STATS = 6
 STAT_NAMES = ("accept_stat__", "stepsize__", "treedepth__", "n_leapfrog__", "divergent__", "energy__")
 
@@ -89,6 +90,9 @@ SIGNATURES = [
     ("stk_model_set_prior", ctypes.c_int, [_vp, _dbl, _dbl]),
     ("stk_model_set_prior_phi", ctypes.c_int, [_vp, _dbl, _dbl]),
     ("stk_model_set_student_nu", ctypes.c_int, [_vp, _dbl]),
+    ("stk_model_set_categories", ctypes.c_int, [_vp, _i32]),
+    ("stk_categorical_supported", ctypes.c_int, [_i32, _i32]),
+    ("stk_chain_batches_categorical", ctypes.c_int, [_i32, _i32, _i32, _vp, _i32]),
     ("stk_model_set_prior_shape", ctypes.c_int, [_vp, _dbl, _dbl]),
     ("stk_gamma_shape_terms_host", ctypes.c_int, [_dbl, _vp]),
     ("stk_negbin_phi_terms_host", ctypes.c_int, [_vp, _i64, _dbl, _vp]),

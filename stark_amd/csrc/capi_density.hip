@@ -35,8 +35,21 @@ std::vector<int> chain_batches_sparse(int C, int d) {
   if (C != 0) b.clear();
   return b;
 }
+// A categorical shard's: C / 16 launches of 16 chains and one of the C mod 16 left over (k_sweep_cat takes any count up
+// to 16: the unused columns carry zero coefficients).  A pure function of (C, K, d); empty outside the envelope.
+std::vector<int> chain_batches_cat(int C, int ncat, int d) {
+  std::vector<int> b;
+  if (C < 1 || !stk_sweep_cat_supported(ncat - 1, d)) return b;
+  for (; C >= CAT_MAX_CHAINS; C -= CAT_MAX_CHAINS) b.push_back(CAT_MAX_CHAINS);
+  if (C > 0) b.push_back(C);
+  return b;
+}
 std::vector<int> model_chain_batches(const stk_model* m, int C) {
+  if (m->family == STK_CATEGORICAL) return chain_batches_cat(C, m->ncat, m->d);
   return m->sparse ? chain_batches_sparse(C, m->d) : chain_batches(C, m->d);
+}
+int model_sweep_pw(const stk_model* m) {
+  return m->family == STK_CATEGORICAL ? stk_sweep_cat_pw(m->ncat, m->d) : sweep_pw(m->family, m->d);
 }
 
 // Refuses, before anything is launched, a shard that no sweep covers at its n, d and batch size.
@@ -48,7 +61,9 @@ int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int
     b.c0 = cp->Ct;
     b.part_off = cp->partial_bytes / sizeof(double);
     for (int sh = first; sh < first + count;) {
-      SweepGroup gr{sh, 1, m->sparse ? stk_sweep_plan_sparse(m->sh[sh].n, m->d, sz) : stk_sweep_plan(m->sh[sh].n, m->d, sz, 0)};
+      SweepGroup gr{sh, 1, m->family == STK_CATEGORICAL ? stk_sweep_plan_cat(m->sh[sh].n, m->d, sz, m->ncat)
+                           : m->sparse                   ? stk_sweep_plan_sparse(m->sh[sh].n, m->d, sz)
+                                                         : stk_sweep_plan(m->sh[sh].n, m->d, sz, 0)};
       ARG_CHECK(gr.launch.kind != SWEEP_NONE,
                 "shard %d: no sweep covers n = %lld rows of d = %d covariates at C = %d chains (a chunk of the shard "
                 "must fit a buffer descriptor: split the shard)", sh, (long long)m->sh[sh].n, m->d, sz);
@@ -58,7 +73,7 @@ int chain_plan(const stk_model* m, const std::vector<int>& sizes, int first, int
       b.groups.push_back(gr);
       sh += gr.nsh;
     }
-    cp->partial_bytes += sizeof(double) * (size_t)m->nshards * b.Gs * sz * sweep_pw(m->family, m->d);
+    cp->partial_bytes += sizeof(double) * (size_t)m->nshards * b.Gs * sz * model_sweep_pw(m);
     cp->Ct += sz;
     cp->batches.push_back(std::move(b));
   }
@@ -80,8 +95,9 @@ hipError_t plan_sweeps(const stk_model* m, const ChainPlan& cp, const SweepCall&
   for (const auto& b : cp.batches) {
     const SweepCall c = batch_call(m, cp, b, run);
     for (const auto& gr : b.groups)
-      if (const hipError_t e = gr.launch.kind == SWEEP_SPARSE ? stk_launch_sweep_sparse(m->family, gr.launch, gr.shard0, gr.nsh, c, st)
-                                                              : stk_launch_sweep(m->family, gr.launch, gr.shard0, gr.nsh, c, st))
+      if (const hipError_t e = gr.launch.kind == SWEEP_CAT      ? stk_launch_sweep_cat(gr.launch, gr.shard0, gr.nsh, c, st)
+                               : gr.launch.kind == SWEEP_SPARSE ? stk_launch_sweep_sparse(m->family, gr.launch, gr.shard0, gr.nsh, c, st)
+                                                                : stk_launch_sweep(m->family, gr.launch, gr.shard0, gr.nsh, c, st))
         return e;
   }
   return hipSuccess;
@@ -91,7 +107,9 @@ hipError_t plan_reduces(const stk_model* m, const ChainPlan& cp, const SweepCall
   for (const auto& b : cp.batches) {
     const SweepCall c = batch_call(m, cp, b, run);
     for (const auto& gr : b.groups)
-      if (const hipError_t e = stk_launch_sweep_reduce(m->family, gr.launch, gr.shard0, gr.nsh, c, lp, g, st)) return e;
+      if (const hipError_t e = gr.launch.kind == SWEEP_CAT ? stk_launch_sweep_reduce_cat(gr.launch, gr.shard0, gr.nsh, c, lp, g, st)
+                                                           : stk_launch_sweep_reduce(m->family, gr.launch, gr.shard0, gr.nsh, c, lp, g, st))
+        return e;
   }
   return hipSuccess;
 }
@@ -206,8 +224,10 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
     // 16 (fp64 MFMA) from 16 when d <= 128, else 4 / 2 / 1; this shard alone, the last point
     // repeated to fill the last batch (the kernel reads rows shard * Cb + c of the point buffer)
     // (a sparse shard: 16 where the sparse sweep covers it at d, no 64)
-    const int Cb = m->sparse ? (C <= 1 ? 1 : C <= 2 ? 2 : (C < 16 || !stk_sweep_sparse_supported(16, s.d)) ? 4 : 16)
-                             : C <= 1 ? 1 : (C <= 2 ? 2 : (C >= 64 ? 64 : (C < 16 || !hook_single_launch(16, s.d) ? 4 : 16)));
+    // (a categorical shard: one launch of up to 16 points, whatever their count)
+    const int Cb = m->family == STK_CATEGORICAL ? std::min<int>(C, CAT_MAX_CHAINS)
+                   : m->sparse ? (C <= 1 ? 1 : C <= 2 ? 2 : (C < 16 || !stk_sweep_sparse_supported(16, s.d)) ? 4 : 16)
+                               : C <= 1 ? 1 : (C <= 2 ? 2 : (C >= 64 ? 64 : (C < 16 || !hook_single_launch(16, s.d) ? 4 : 16)));
     ChainPlan plan;
     RC(chain_plan(m, {Cb}, shard, 1, &plan));
     for (int c0 = 0; c0 < C; c0 += Cb)
@@ -238,8 +258,10 @@ int stk_log_density_grad(stk_model* m, int shard, const double* q, int32_t C, do
 // group's own G.
 int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_shards: bad arguments");
-  ARG_CHECK(is_sweep_family(m->family), "stk_log_density_grad_shards: regression families only");
-  if (m->sparse)
+  ARG_CHECK(is_density_family(m->family), "stk_log_density_grad_shards: regression families only");
+  if (m->family == STK_CATEGORICAL)
+    ARG_CHECK(C <= CAT_MAX_CHAINS, "points per shard must be one launch of a categorical model here: 1 .. 16, not %d", C);
+  else if (m->sparse)
     ARG_CHECK(stk_sweep_sparse_supported(C, m->d), "points per shard must be a single batch size of a sparse model here: 1, 2, 4, 8 or 16 (d <= 512)");
   else
     ARG_CHECK(hook_single_launch(C, m->d), "points per shard must be a single batch size here: 1, 2, 4, 8, 16 (d <= 128) or 64");
@@ -250,7 +272,8 @@ int stk_log_density_grad_shards(stk_model* m, const double* q, int32_t C, double
 // run at chains = C.
 int stk_log_density_grad_chains(stk_model* m, const double* q, int32_t C, double* lp, double* grad) {
   ARG_CHECK(m && q && lp && C > 0, "stk_log_density_grad_chains: bad arguments");
-  ARG_CHECK(is_sweep_family(m->family), "stk_log_density_grad_chains: regression families only");
+  ARG_CHECK(is_density_family(m->family), "stk_log_density_grad_chains: regression families only");
+  RC(model_ready(m));
   ARG_CHECK(!model_chain_batches(m, C).empty(), "no sweep covers %d covariates (1..1024)", m->d);
   return hook_every_shard(m, model_chain_batches(m, C), q, lp, grad);
 }
@@ -262,6 +285,21 @@ int stk_chain_batches(int32_t C, int32_t d, int32_t* sizes, int32_t cap) {
   ARG_CHECK(!b.empty(), "no sweep covers %d covariates (1..1024)", d);
   for (size_t i = 0; i < b.size() && (int32_t)i < cap; ++i) sizes[i] = b[i];
   return (int)b.size();
+}
+
+// A categorical shard's at K = ncat classes (host only: no device).
+int stk_chain_batches_categorical(int32_t C, int32_t d, int32_t ncat, int32_t* sizes, int32_t cap) {
+  ARG_CHECK(C >= 1 && d >= 1 && ncat >= 2 && cap >= 0 && (sizes || cap == 0),
+            "stk_chain_batches_categorical: need C >= 1, d >= 1, ncat >= 2, cap >= 0");
+  const std::vector<int> b = chain_batches_cat(C, ncat, d);
+  ARG_CHECK(!b.empty(), "the categorical sweep does not cover K = %d classes at d = %d covariates: it needs K - 1 <= 16 and "
+                        "(K - 1) ceil(d / 16) <= 16", ncat, d);
+  for (size_t i = 0; i < b.size() && (int32_t)i < cap; ++i) sizes[i] = b[i];
+  return (int)b.size();
+}
+
+int stk_categorical_supported(int32_t ncat, int32_t d) {
+  return ncat >= 2 && d >= 1 && stk_sweep_cat_supported(ncat - 1, d) && (ncat - 1) * (d + 1) <= 1024 ? 1 : 0;
 }
 
 // A sparse shard's (host only: no device).

@@ -102,6 +102,7 @@ struct stk_model {
   std::vector<int64_t> sp_nnz;
   DevBuf sp_dev;                // the side table's device copy, what k_sweep_sp reads
   double nu = 0.0;              // STK_STUDENT: the degrees of freedom (0: not set yet); every shard's ShardDev carries a copy
+  int ncat = 0;                 // STK_CATEGORICAL: the classes K (0: not set yet; stk_model_set_categories); likewise
   int64_t bytes = 0;
   std::vector<uint64_t> fp;   // shard fingerprints, computed on first use (the data never changes)
   std::vector<char> fp_ok;
@@ -176,7 +177,8 @@ bool is_device_ptr(const void* p, int device);
 const char* family_name(int family);
 bool is_regression(int family);     // linear, logistic, poisson: every regression entry point
 bool is_sweep_family(int family);   // those, neg_binomial, student_t and gamma: the gradient sweeps, the sampler, the priors
-int model_ready(const stk_model* m);   // STK_E_ARG for a student_t model whose nu has not been set (no hidden default)
+bool is_density_family(int family); // those and categorical, whose sweep is its own (sweep_cat.hip): the hooks, the sampler, the priors
+int model_ready(const stk_model* m);   // STK_E_ARG for a student_t model whose nu, or a categorical one whose K, has not been set (no hidden default)
 void model_release(stk_model* m);
 int model_fingerprint(stk_model* m, int shard, uint64_t* out);   // cached
 // shard == -1 means every shard: the first shard, how many, and the largest per-shard chunk count.
@@ -186,7 +188,9 @@ ShardRange shard_range(const stk_model* m, int shard, int (*chunks)(int64_t n));
 // ---- capi_density.hip: the chain plan (its construction comment is at ChainPlan above)
 std::vector<int> chain_batches(int C, int d);
 std::vector<int> chain_batches_sparse(int C, int d);
-std::vector<int> model_chain_batches(const stk_model* m, int C);   // the model's storage decides which of the two
+std::vector<int> chain_batches_cat(int C, int ncat, int d);
+std::vector<int> model_chain_batches(const stk_model* m, int C);   // the model's family and storage decide which of the three
+int model_sweep_pw(const stk_model* m);                            // columns of a chunk's partial row per chain
 // An entry point without a sparse form: STK_E_ARG, before anything is launched, with a message that names the
 // entry point and says that the model is sparse.
 #define REFUSE_SPARSE(m, what)                                                                                      \

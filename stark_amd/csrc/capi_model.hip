@@ -12,6 +12,7 @@ const char* family_name(int family) {
     case STK_NEGBIN: return "neg_binomial";
     case STK_STUDENT: return "student_t";
     case STK_GAMMA: return "gamma";
+    case STK_CATEGORICAL: return "categorical";
   }
   return "unknown";
 }
@@ -23,9 +24,14 @@ bool is_sweep_family(int family) {
   return is_regression(family) || family == STK_NEGBIN || family == STK_STUDENT || family == STK_GAMMA;
 }
 
+// ...and categorical, which has a sweep of its own (sweep_cat.hip) and none of the sparse or analysis forms.
+bool is_density_family(int family) { return is_sweep_family(family) || family == STK_CATEGORICAL; }
+
 int model_ready(const stk_model* m) {
   ARG_CHECK(m->family != STK_STUDENT || m->nu > 0.0,
             "the student_t model's nu has not been set: call stk_model_set_student_nu first (there is no default)");
+  ARG_CHECK(m->family != STK_CATEGORICAL || m->ncat >= 2,
+            "the categorical model's classes have not been set: call stk_model_set_categories first (there is no default)");
   return STK_OK;
 }
 
@@ -44,6 +50,7 @@ static int family_dims(int family, int64_t n, int d, int* D, int* P) {
     case STK_NEGBIN: *D = d + 2; *P = d + 3; return STK_OK;    // the linear layout: alpha, beta, phi (v = log phi), lp__
     case STK_STUDENT: *D = d + 2; *P = d + 3; return STK_OK;   // the linear layout itself: alpha, beta, sigma (s = log sigma), lp__
     case STK_GAMMA: *D = d + 2; *P = d + 3; return STK_OK;     // the linear layout: alpha, beta, shape (u = log shape), lp__
+    case STK_CATEGORICAL: *D = 0; *P = 0; return STK_OK;       // (K - 1)(d + 1) and + 1, once stk_model_set_categories has said K
   }
   stk_set_error("unknown model family %d", family);
   return STK_E_ARG;
@@ -215,7 +222,11 @@ static int upload_regression_y(stk_model* m, int s, const stk_shard& in, ShardDe
   const int family = m->family;
   const size_t n = (size_t)in.n_rows;
   ShardDev& sd = *out;
-  if (family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN) {
+  if (family == STK_CATEGORICAL) {   // y_int in [1, K] as given; checked once K is known (stk_model_set_categories)
+    ARG_CHECK(in.y_int, "shard %d: categorical needs y_int", s);
+    ARG_CHECK(!in.y && !in.sigma, "shard %d: categorical takes its classes in y_int alone; y and sigma must be NULL", s);
+    RC(upload(m, in.y_int, n, &sd.yi));
+  } else if (family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN) {
     const bool pois = family != STK_LOGREG;   // a count family
     const char* fam = family == STK_NEGBIN ? "neg_binomial" : pois ? "poisson" : "logreg";
     ARG_CHECK(in.y_int, "shard %d: %s needs y_int", s, fam);
@@ -595,7 +606,7 @@ int stk_model_copy_data(stk_model* m, int shard, double* x, double* y, int32_t* 
 
 int stk_model_set_prior(stk_model* m, double alpha_scale, double beta_scale) {
   ARG_CHECK(m, "stk_model_set_prior: NULL model");
-  ARG_CHECK(is_sweep_family(m->family), "priors apply to the regression families");
+  ARG_CHECK(is_density_family(m->family), "priors apply to the regression families");
   ARG_CHECK(alpha_scale >= 0.0 && beta_scale >= 0.0, "prior scales must be >= 0 (0 or inf: flat)");
   auto prec = [](double sc) { return (sc == 0.0 || std::isinf(sc)) ? 0.0 : 1.0 / (sc * sc); };
   for (auto& sd : m->sh) {
@@ -649,6 +660,49 @@ int stk_model_set_student_nu(stk_model* m, double nu) {
   m->nu = nu;
   for (auto& sd : m->sh) shard_set_nu(sd, nu);
   STK_HIP_CHECK(hipSetDevice(m->ctx->device));
+  return upload_shard_table(m);
+}
+
+int stk_model_set_categories(stk_model* m, int32_t ncat) {
+  ARG_CHECK(m, "stk_model_set_categories: NULL model");
+  ARG_CHECK(m->family == STK_CATEGORICAL, "stk_model_set_categories: classes are for the categorical family, not for the %s family (%d)",
+            family_name(m->family), m->family);
+  ARG_CHECK(m->ncat == 0, "stk_model_set_categories: the model's classes are set already (K = %d): they are set once", m->ncat);
+  ARG_CHECK(ncat >= 2, "stk_model_set_categories: K = %d classes; categorical_logit needs K >= 2 (d = %d)", ncat, m->d);
+  const int G = ncat - 1, d = m->d;
+  ARG_CHECK(stk_sweep_cat_supported(G, d) && (int64_t)G * (d + 1) <= 1024,
+            "stk_model_set_categories: K = %d classes at d = %d covariates are outside the categorical sweep's envelope: it needs "
+            "K - 1 <= 16, (K - 1) ceil(d / 16) <= 16 and (K - 1)(d + 1) <= 1024", ncat, d);
+  stk_ctx* ctx = m->ctx;
+  STK_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf flag;
+  RC(flag.ensure(sizeof(int64_t)));
+  for (int s = 0; s < m->nshards; ++s) {   // the kernel never sees a class outside [1, K]
+    const ShardDev& sd = m->sh[s];
+    int64_t bad = -1;
+    int32_t v = 0;
+    hipError_t e = stk_launch_check_ycat(sd.yi, sd.n, ncat, flag.as<int64_t>(), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, flag.p, sizeof(int64_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && bad >= 0 && bad < sd.n) e = hipMemcpy(&v, sd.yi + bad, sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+      flag.release();
+      stk_set_error("shard %d: y_int check failed: %s", s, hipGetErrorString(e));
+      return STK_E_HIP;
+    }
+    if (bad >= 0 && bad < sd.n) {
+      flag.release();
+      stk_set_error("shard %d: y_int[%lld] = %d; categorical_logit with K = %d classes needs 1 .. %d", s, (long long)bad, v, ncat, ncat);
+      return STK_E_ARG;
+    }
+  }
+  flag.release();
+  m->ncat = ncat;
+  for (auto& sd : m->sh) {
+    sd.D = G * (d + 1);
+    sd.P = sd.D + 1;
+  }
   return upload_shard_table(m);
 }
 
@@ -728,7 +782,7 @@ int stk_fingerprint_words(stk_ctx* ctx, const void* buf, int64_t count, int32_t 
 int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
   ARG_CHECK(sh && out, "stk_shard_fingerprint_host: bad arguments");
   ARG_CHECK(family == STK_SCHOOLS || family == STK_LINREG || family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN ||
-                family == STK_STUDENT || family == STK_GAMMA,
+                family == STK_STUDENT || family == STK_GAMMA || family == STK_CATEGORICAL,
             "unknown model family %d", family);
   ARG_CHECK(sh->n_rows > 0, "stk_shard_fingerprint_host: n_rows must be positive");
   uint64_t acc = fp_shard_header(family, sh->n_rows, sh->n_cols);
@@ -738,8 +792,8 @@ int stk_shard_fingerprint_host(int family, const stk_shard* sh, uint64_t* out) {
   } else {
     ARG_CHECK(sh->x && sh->n_cols > 0, "stk_shard_fingerprint_host: regression needs x");
     acc += stk_fp_words_host(sh->x, sh->n_rows * sh->n_cols, 8, 1, 0);
-    if (family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN) {
-      const char* fam = family == STK_NEGBIN ? "neg_binomial" : family == STK_POISSON ? "poisson" : "logreg";
+    if (family == STK_LOGREG || family == STK_POISSON || family == STK_NEGBIN || family == STK_CATEGORICAL) {
+      const char* fam = family == STK_CATEGORICAL ? "categorical" : family == STK_NEGBIN ? "neg_binomial" : family == STK_POISSON ? "poisson" : "logreg";
       ARG_CHECK(sh->y_int, "stk_shard_fingerprint_host: %s needs y_int", fam);
       ARG_CHECK(family == STK_LOGREG || (!sh->y && !sh->sigma),
                 "stk_shard_fingerprint_host: %s takes its counts in y_int alone; y and sigma must be NULL", fam);

@@ -88,7 +88,7 @@ static int check_config(const stk_model* m, const stk_config* cfg, int nch) {
             "chains_per_wave must be 0, 1, 2 or 4");
   ARG_CHECK(cfg->metric >= 0 && cfg->metric <= 2, "metric must be 0 (diag_e), 1 (dense_e) or 2 (unit_e)");
   ARG_CHECK(cfg->metric != 1 || m->family != STK_SCHOOLS,
-            "metric dense_e is for the regression families (linear, logistic, poisson, neg_binomial, student_t, gamma): the fused 8-schools kernel "
+            "metric dense_e is for the regression families (linear, logistic, poisson, neg_binomial, student_t, gamma, categorical): the fused 8-schools kernel "
             "has no dense form; use diag_e or unit_e");
   ARG_CHECK(nch > 0, "dimension %d too large (max 1024)", m->Dmax);
   if (m->family == STK_SCHOOLS) {
@@ -105,6 +105,7 @@ static int check_config(const stk_model* m, const stk_config* cfg, int nch) {
               "lower max_depth",
               m->Dmax - 2, cfg->max_depth, cfg->nuts_criterion, lds, BIG_LDS_BYTES);
   } else {
+    RC(model_ready(m));
     ARG_CHECK(!model_chain_batches(m, cfg->chains).empty(), "no sweep covers %d covariates (1..1024)", m->d);
   }
   return STK_OK;
@@ -119,7 +120,10 @@ static void fill_args(const stk_model* m, const stk_config* cfg, NutsArgs* args)
   // The NUTS kernels read the family only for the draw layout (schools; or the last unconstrained
   // coordinate written as its exp): the negative binomial's phi = e^v sits where the linear sigma does, and
   // student_t's sigma = e^s is the linear sigma; so does the gamma family's shape = e^u.
-  A.family = (m->family == STK_NEGBIN || m->family == STK_STUDENT || m->family == STK_GAMMA) ? STK_LINREG : m->family;
+  // categorical writes q as it is, lp__ last: the logistic layout at D = (K - 1)(d + 1).
+  A.family = (m->family == STK_NEGBIN || m->family == STK_STUDENT || m->family == STK_GAMMA) ? STK_LINREG
+             : m->family == STK_CATEGORICAL                                                  ? STK_LOGREG
+                                                                                             : m->family;
   A.max_depth = cfg->max_depth;
   A.num_warmup = cfg->num_warmup;
   A.num_samples = cfg->num_samples;

@@ -29,6 +29,7 @@ int state_geometry(const stk_sampler* s, uint64_t* out) {
   for (const auto& sd : m->sh) f.add(sd.n), f.add(sd.D), f.add(sd.P), f.add(sd.pa), f.add(sd.pb);
   for (const auto& nb : m->nb) f.add(nb.pr_a1), f.add(nb.pr_b);   // negative binomial: the phi prior; gamma: the shape prior (no other family has entries)
   if (m->family == STK_STUDENT) f.add(m->nu);                       // student_t alone: a state saved at nu = 4 is not one for nu = 5
+  if (m->family == STK_CATEGORICAL) f.add(m->ncat);                 // categorical alone: (K = 3, d = 5) and (K = 4, d = 3) share D = 12
   f.add(A.nchains), f.add(A.C), f.add(A.Dp), f.add(A.max_depth), f.add(A.num_warmup), f.add(A.num_samples);
   f.add(A.adapt), f.add(A.var_on), f.add(A.skip_ss), f.add(A.iter_offset);
   f.add(A.init_buffer), f.add(A.term_buffer), f.add(A.base_window);

@@ -10,6 +10,8 @@ namespace stk {
 
 struct SweepArgs;   // sweep_common.h (device side)
 
+constexpr int CAT_MAX_CHAINS = 16;   // chains of one k_sweep_cat launch: the MFMA's 16 columns (sweep_cat.hip)
+
 // Which regression sweep runs; the numbers are those of tests/golden/sweep_launch.json.
 enum SweepKind : int {
   SWEEP_NONE = 0,     // no sweep: the chunk bytes do not fit a buffer descriptor, or (C, d) has no kernel
@@ -21,6 +23,8 @@ enum SweepKind : int {
   SWEEP_16W = 6,      // k_sweep16w    C = 16, 128 < d <= 1024 (sweep16w.hip)
   SWEEP_SPARSE = 7,   // k_sweep_sp    sparse (padded-row) shards: C <= 16, any d <= 1024 (sweep_sparse.hip); never
                       // chosen by stk_sweep_plan, whose numbers keep their dense meaning
+  SWEEP_CAT = 8,      // k_sweep_cat   STK_CATEGORICAL: C <= 16 chains, K - 1 classes' tiles (sweep_cat.hip); never chosen by
+                      // stk_sweep_plan either
 };
 
 // The kernel and launch shape of one sweep over a shard of n rows: a function of (n, d, C) only,
@@ -32,7 +36,8 @@ struct SweepLaunch {
   int T;              // rows per tile
   int G;              // chunks per shard
   size_t lds;         // dynamic LDS bytes per block (kind 5: pass F's; pass B sizes its own)
-  int ld;             // kinds 1, 2: row stride of the X tile in LDS, in doubles; kind 7: bytes of the entry stage in LDS
+  int ld;             // kinds 1, 2: row stride of the X tile in LDS, in doubles; kind 7: bytes of the entry stage in LDS;
+                      // kind 8: the classes K
   int ring;           // kind 3: ring slots per wave
   int waves;          // kind 6: waves per block (= column slabs); kind 7: private gradient copies per block
   int64_t Rrows;      // kind 5: rows of the residual matrix R per shard (n rounded up to 64)
@@ -119,6 +124,16 @@ hipError_t stk_launch_sweep_sparse(int family, const stk::SweepLaunch& p, int sh
 template <int FAM>
 hipError_t stk_launch_sweep_sp(const stk::SweepLaunch& p, const stk::SweepArgs& A, const stk::SpShardDev* sp, int nblocks,
                                hipStream_t st);
+
+// ---- sweep_cat.hip (STK_CATEGORICAL): the envelope in (G = K - 1, d), the plan of one launch of C <= 16 chains (chunks
+// of (n, d) alone), the partial row's width G (d + 1) + 1, the sweep, its reduce, and the device check of y in [1, K]
+bool stk_sweep_cat_supported(int G, int d);
+stk::SweepLaunch stk_sweep_plan_cat(int64_t n, int d, int C, int ncat);
+int stk_sweep_cat_pw(int ncat, int d);
+hipError_t stk_launch_sweep_cat(const stk::SweepLaunch& p, int shard0, int nsh, const stk::SweepCall& c, hipStream_t st);
+hipError_t stk_launch_sweep_reduce_cat(const stk::SweepLaunch& p, int shard0, int nsh, const stk::SweepCall& c, double* lp_out,
+                                       double* g_out, hipStream_t st);
+hipError_t stk_launch_check_ycat(const int32_t* y, int64_t n, int K, int64_t* first, hipStream_t st);
 
 // ---- sweep16.hip: shapes k_sweep16 covers, its LDS bytes, its launch
 bool stk_sweep16_supported(int d);

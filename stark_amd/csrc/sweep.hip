@@ -1212,26 +1212,7 @@ template __global__ void k_gemm_bwd<256>(SweepArgs, int);
 // order -- a fixed order that depends only on G.  (At one shard per GPU the 4-wave form was a
 // chain of 32 dependent load batches per wave: 19 us per step.)
 constexpr int RD_W = 16;
-// Wave w's share of column o of chain c's chunk partials: its contiguous range of the G chunks, summed in order,
-// 8 loads in flight.
-template <int W>
-__device__ __forceinline__ double reduce_chunk_range(const SweepArgs& A, int shard, int c, int C, int o, int w) {
-  const int per = (A.G + W - 1) / W;
-  const int k0 = w * per, k1 = min(A.G, k0 + per);
-  const double* src = A.partial + ((size_t)shard * A.Gs * C + c) * A.PW + o;
-  const size_t stride = (size_t)C * A.PW;
-  double v = 0.0;
-  int k = k0;
-  for (; k + 8 <= k1; k += 8) {
-    double a[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a[i] = src[(size_t)(k + i) * stride];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v += a[i];
-  }
-  for (; k < k1; ++k) v += src[(size_t)k * stride];
-  return v;
-}
+// reduce_chunk_range (a wave's share of a column's chunk partials, summed in chunk order): sweep_common.h
 // The normal(0, s) priors' term of lp at the chain's point: -(pa alpha^2 + pb |beta|^2) / 2, 0 when both are flat.
 __device__ __forceinline__ double normal_prior_lp(const ShardDev& sh, const double* qc, int d) {
   if (sh.pa == 0.0 && sh.pb == 0.0) return 0.0;

@@ -378,4 +378,26 @@ __device__ __forceinline__ double gamma_resid_libm(double eta, double ly, double
   return a * em1;
 }
 
+// The reduces' chunk order, shared by sweep.hip's and sweep_cat.hip's.
+// Wave w's share of column o of chain c's chunk partials: its contiguous range of the G chunks, summed in order,
+// 8 loads in flight.
+template <int W>
+__device__ __forceinline__ double reduce_chunk_range(const SweepArgs& A, int shard, int c, int C, int o, int w) {
+  const int per = (A.G + W - 1) / W;
+  const int k0 = w * per, k1 = min(A.G, k0 + per);
+  const double* src = A.partial + ((size_t)shard * A.Gs * C + c) * A.PW + o;
+  const size_t stride = (size_t)C * A.PW;
+  double v = 0.0;
+  int k = k0;
+  for (; k + 8 <= k1; k += 8) {
+    double a[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = src[(size_t)(k + i) * stride];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v += a[i];
+  }
+  for (; k < k1; ++k) v += src[(size_t)k * stride];
+  return v;
+}
+
 }  // namespace stk

@@ -14,11 +14,21 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_NEGBIN, STK_POISSON, STK_SCHOOLS, STK_STUDENT, STK_GAMMA, Config, RunInfo, Shard,
+from ._lib import (N_STATS, STAT_NAMES, STK_LINREG, STK_LOGREG, STK_NEGBIN, STK_POISSON, STK_SCHOOLS, STK_STUDENT, STK_GAMMA, STK_CATEGORICAL, Config, RunInfo, Shard,
                    ShardSparse, StarkHipError, check)
 
 FAMILIES = {"schools": STK_SCHOOLS, "linear": STK_LINREG, "logistic": STK_LOGREG, "poisson": STK_POISSON,
             "neg_binomial": STK_NEGBIN, "student_t": STK_STUDENT, "gamma": STK_GAMMA}
+# The families with a coefficient MATRIX (several linear predictors per row, a sweep of their own), kept beside the
+# table of the one-predictor families above; family_id() and FAMILY_NAMES know both.  FAMILIES itself stays at its
+# seven entries: tests/test_host_gamma.py::test_engine_tables_and_driver_refusals asserts its values are 1 .. 7, and
+# existing tests are not edited.  The next matrix family goes into MATRIX_FAMILIES.
+MATRIX_FAMILIES = {"categorical": STK_CATEGORICAL}
+
+
+def family_id(family):
+    """A family name (or id) as the library's id; an unknown name comes back as it is."""
+    return FAMILIES.get(family, MATRIX_FAMILIES.get(family, family))
 
 # Live library handles, closed in dependency order (samplers, models, contexts) before the
 # HIP runtime's own exit handlers run; after that every close() is a no-op.
@@ -36,7 +46,7 @@ def _shutdown():
             except Exception:
                 pass
     _finalized = True
-FAMILY_NAMES = {v: k for k, v in FAMILIES.items()}
+FAMILY_NAMES = {v: k for k, v in {**FAMILIES, **MATRIX_FAMILIES}.items()}
 METRICS = {"diag_e": 0, "dense_e": 1, "unit_e": 2}
 
 
@@ -177,13 +187,22 @@ def make_config(num_warmup=1000, num_samples=1000, chains=1, max_depth=10, adapt
     return c
 
 
-def chain_batches(chains: int, n_cols: int, sparse: bool = False) -> list[int]:
+def chain_batches(chains: int, n_cols: int, sparse: bool = False, ncat: int | None = None) -> list[int]:
     """The contiguous chain batches that ``chains`` chains per shard of a regression with ``n_cols``
     covariates run as (stk_chain_batches): greedy, largest first, over the single-launch sizes
     {64, 16, 8, 4, 2, 1} a sweep covers at that width.  ``sparse=True``: those of a sparse shard
     (stk_chain_batches_sparse), over {16, 8, 4, 2, 1} up to 512 covariates and {8, 4, 2, 1} past
-    them.  Host only: needs no device."""
+    them.  ``ncat=K``: those of a categorical shard with K classes (stk_chain_batches_categorical):
+    ``chains // 16`` launches of 16 and one of the ``chains % 16`` left over; STK_E_ARG outside the
+    family's envelope.  Host only: needs no device."""
     sizes = np.zeros(max(int(chains), 1), np.int32)
+    if ncat is not None:
+        if sparse:
+            raise ValueError("the categorical family has no sparse form")
+        n = _lib.load().stk_chain_batches_categorical(int(chains), int(n_cols), int(ncat), sizes.ctypes.data, sizes.size)
+        if n < 0:
+            check(n)
+        return [int(v) for v in sizes[:n]]
     fn = _lib.load().stk_chain_batches_sparse if sparse else _lib.load().stk_chain_batches
     n = fn(int(chains), int(n_cols), sizes.ctypes.data, sizes.size)
     if n < 0:
@@ -277,6 +296,11 @@ def _regression_y(family, y, n_rows):
         y = np.ascontiguousarray(y, np.int32)
         if np.any((y != 0) & (y != 1)):
             raise ValueError("bernoulli_logit: y must be 0 or 1")
+    elif family == STK_CATEGORICAL:   # classes 1 .. K as given; the library checks them against K on the device
+        y = np.asarray(y)
+        if y.dtype.kind not in "iuf" or not np.all(y == np.round(y)) or np.any(np.abs(y) > np.iinfo(np.int32).max):
+            raise ValueError("categorical_logit: y must hold integers (the classes 1 .. ncat)")
+        y = np.ascontiguousarray(y, np.int32)
     elif family in (STK_POISSON, STK_NEGBIN):
         y = np.asarray(y)
         if y.dtype.kind not in "iuf" or not np.all(y == np.round(y)) or np.any(y < 0) or np.any(y > np.iinfo(np.int32).max):
@@ -287,7 +311,7 @@ def _regression_y(family, y, n_rows):
         y = np.ascontiguousarray(y, np.float64)
     if y.shape[0] != n_rows:
         raise ValueError("x and y row counts differ")
-    return y, family in (STK_LOGREG, STK_POISSON, STK_NEGBIN)
+    return y, family in (STK_LOGREG, STK_POISSON, STK_NEGBIN, STK_CATEGORICAL)
 
 
 def _host_shard(family, sh):
@@ -346,7 +370,7 @@ def shard_fingerprint(family, shard) -> np.uint64:
     """The data fingerprint of one shard of host rows -- the dict ``Model`` takes -- computed on the
     host (stk_shard_fingerprint_host): equal to ``Model.fingerprint(s)`` of a model holding these
     rows as shard s, so rows can be checked before an upload, or on another rank."""
-    fam = FAMILIES.get(family, family)
+    fam = family_id(family)
     if fam not in FAMILY_NAMES:
         raise ValueError(f"unknown model family {family!r}")
     out = ctypes.c_uint64()
@@ -362,11 +386,28 @@ def shard_fingerprint(family, shard) -> np.uint64:
 class Model:
     """Shards of one model family resident on one device (``stk_model``)."""
 
-    def __init__(self, ctx: Context, family, shards=None, _handle=None, nu=None):
+    def __init__(self, ctx: Context, family, shards=None, _handle=None, nu=None, ncat=None):
         """nu: the degrees of freedom of the "student_t" family, finite and > 0 -- required there (the library has
-        no default), refused for every other family."""
+        no default), refused for every other family.  ncat: the classes K >= 2 of the "categorical" family, from
+        ncat= or, without it, from the shards' "ncat" entries (what frontend.pack_data leaves there), which must
+        agree; required there, refused for every other family."""
         self.ctx = ctx
-        self.family = FAMILIES.get(family, family)
+        self.family = family_id(family)
+        if self.family == STK_CATEGORICAL:
+            ks = sorted({int(sh["ncat"]) for sh in (shards or []) if "ncat" in sh})
+            if ncat is None:
+                if len(ks) != 1:
+                    raise ValueError("the categorical family needs ncat= (the classes, >= 2) or one \"ncat\" in every shard: "
+                                     f"got {ks}")
+                ncat = ks[0]
+            elif ks and ks != [ncat]:
+                raise ValueError(f"categorical: ncat = {ncat!r} but the shards' \"ncat\" entries are {ks}: one model has one ncat")
+            if int(ncat) != ncat or int(ncat) < 2:
+                raise ValueError(f"categorical: ncat must be an integer >= 2, got {ncat!r}")
+            ncat = int(ncat)
+        elif ncat is not None:
+            raise ValueError(f"ncat= is for the categorical family, not for the {FAMILY_NAMES.get(self.family, self.family)} family")
+        self.ncat = ncat
         if self.family == STK_STUDENT:
             if nu is None:
                 raise ValueError("the student_t family needs nu= (the degrees of freedom, > 0): there is no default")
@@ -384,6 +425,8 @@ class Model:
         lib = _lib.load()
         if self.nu is not None:
             check(lib.stk_model_set_student_nu(self._h, self.nu))
+        if self.ncat is not None:
+            check(lib.stk_model_set_categories(self._h, self.ncat))
         self.nshards = len(shards) if shards is not None else self._nshards
         self.D, self.P, self.n_rows = [], [], []
         for s in range(self.nshards):
@@ -420,7 +463,7 @@ class Model:
                   row_offset: int = 0, alpha: float = 0.0, beta=None, noise_sigma: float = 1.0):
         """Shards generated in HBM by the Philox generator: linear and logistic only
         (the library refuses "poisson": the generator draws no counts)."""
-        fam = FAMILIES.get(family, family)
+        fam = family_id(family)
         b = None
         if beta is not None:
             b = np.ascontiguousarray(beta, np.float64)
@@ -488,8 +531,10 @@ class Model:
             y = np.empty(n)
             check(lib.stk_model_copy_data(self._h, shard, None, y.ctypes.data, None))
             return {"y": y}
-        yint = self.family in (STK_LOGREG, STK_POISSON, STK_NEGBIN)
+        yint = self.family in (STK_LOGREG, STK_POISSON, STK_NEGBIN, STK_CATEGORICAL)
         d = D - (2 if self.family in (STK_LINREG, STK_NEGBIN, STK_STUDENT, STK_GAMMA) else 1)
+        if self.family == STK_CATEGORICAL:
+            d = D // (self.ncat - 1) - 1
         x = np.empty((n, 0 if self.sparse else d))   # a sparse model keeps no dense x: y alone comes back
         if yint:
             y = np.empty(n, np.int32)
@@ -1013,7 +1058,7 @@ def fitted_mean(ctx, family, x, q):
     """The posterior mean of E[y | x] for new rows ``x`` [n, d] over the draws ``q`` [S, D]: ``mu`` of
     ``Model.log_predictive`` on a model of these rows with zero ``y`` (logistic: the probability;
     poisson: the rate; linear: the linear predictor)."""
-    fam = FAMILIES.get(family, family)
+    fam = family_id(family)
     if fam not in (STK_LINREG, STK_LOGREG, STK_POISSON):
         raise ValueError("fitted_mean needs a regression family (linear, logistic, poisson)")
     x = np.ascontiguousarray(x, np.float64)
@@ -1072,7 +1117,7 @@ def yrep_host(family, seed: int, stream: int, row0: int, draw0: int, eta, u=None
     same header; needs no device.  margin=True also returns, per element, the smallest relative gap of any
     comparison that decided the value: below 1e-10 the element may differ for an eta that differs in its last
     bits.  stream: the shard's global index."""
-    fam = FAMILIES.get(family, family)
+    fam = family_id(family)
     eta = np.ascontiguousarray(np.atleast_2d(eta), np.float64)
     uv = None if u is None else np.ascontiguousarray(np.atleast_1d(u), np.float64)
     if uv is not None and uv.shape != (eta.shape[1],):

@@ -69,6 +69,39 @@ _GAMMA = re.compile(r"y~gamma\(shape,shape(?: ?\./exp\(" + _ETA + r"\)|\*exp\(-\
 _PRIOR_SHAPE = re.compile(r"shape~(?:gamma\(" + _NUM + "," + _NUM + r"\)|exponential\(" + _NUM + r"\))$")
 
 
+# Softmax regression (models/categorical.stan): K = ncat classes, class ncat the reference, beta a column-major vector.
+#   matrix[N, ncat - 1] eta = rep_matrix(alpha', N) + x * to_matrix(beta, K, ncat - 1);      (either order of the sum)
+#   for (n in 1:N) y[n] ~ categorical_logit(append_row(eta[n]', 0));                          (with or without braces)
+_CAT_XB = r"x\*to_matrix\(beta,K,ncat-1\)"
+_CAT_A = r"rep_matrix\(alpha',N\)"
+_CAT_ETA = re.compile(r"matrix\[N,ncat-1\]eta=(?:" + _CAT_A + r"\+" + _CAT_XB + "|" + _CAT_XB + r"\+" + _CAT_A + ")$")
+_CAT_LIK = re.compile(r"for\(n in 1:N\)(\{?)y\[n\]~categorical_logit\(append_row\(eta\[n\]',0\)\)$")
+_CAT_PARAMS = re.compile(r"vector\[ncat-1\]alpha;vector\[K\*\(ncat-1\)\]beta;?$")
+
+
+def _recognise_categorical(b: dict, stm: list):
+    """'categorical' for the committed program's blocks.  A `matrix` beta, a missing append_row(., 0), a
+    categorical(softmax(.)), an added offset and a transformed parameters block are other programs to this recogniser."""
+    lik = [_CAT_LIK.match(t) for t in stm]
+    braced = [m for m in lik if m and m.group(1)]
+    # one eta statement, one loop; a braced loop body leaves its closing brace behind as the last statement
+    rest = [t for t, m in zip(stm, lik) if not m]
+    if braced:
+        if not rest or rest[-1] != "}":
+            return None
+        rest = rest[:-1]
+    if sum(1 for m in lik if m) != 1 or len(rest) != 1 or not _CAT_ETA.match(rest[0]):
+        return None
+    data = b.get("data", "")
+    if (_CAT_PARAMS.match(b.get("parameters", "")) and not b.get("transformed parameters")
+            and _decl(data, r"(^|;)int<lower=[01]>N(;|$)") and _decl(data, r"(^|;)int<lower=[01]>K(;|$)")
+            and _decl(data, r"(^|;)matrix\[N,K\]x(;|$)")
+            and _decl(data, r"(^|;)int<lower=2>ncat(;|$)")
+            and _decl(data, r"(^|;)(int<lower=1,upper=ncat>y\[N\]|array\[N\]int<lower=1,upper=ncat>y)(;|$)")):
+        return "categorical"
+    return None
+
+
 def _split_priors(stmts):
     """Separate `alpha ~ normal(0, s)` / `beta ~ normal(0, s)` statements (s > 0) and `phi ~ gamma(a, b)` /
     `phi ~ exponential(r)` (a, b, r > 0; stored as 'phi': (a, b)) from the rest; `shape ~ ...` likewise, as
@@ -98,7 +131,7 @@ def program_info(model_code: str):
     code = _strip(model_code)
     b = _blocks(code)
     priors, rest = _split_priors(_stmts(b.get("model", "")))
-    fam = _recognise_blocks(b, sorted(rest))
+    fam = _recognise_blocks(b, sorted(rest)) or _recognise_categorical(b, rest)
     if fam == "student_t":
         lit = _STUDENT.match(rest[0]).group(1)
         if lit is not None:
@@ -116,14 +149,15 @@ def program_info(model_code: str):
             "variable or a literal, never a parameter) regression with flat or normal(0, s) "
             "priors on alpha and beta, and for the negative binomial a flat, gamma(a, b) or exponential(r) prior on "
             "phi, and gamma regression with the log link (gamma(shape, shape ./ exp(alpha + x * beta))) with a flat, "
-            "gamma(a, b) or exponential(r) prior on shape; see stark_amd/models/*.stan).  This Stan program is not one "
+            "gamma(a, b) or exponential(r) prior on shape, and softmax regression (categorical_logit with the last class "
+            "as reference and beta a column-major vector); see stark_amd/models/*.stan).  This Stan program is not one "
             "of them; pass "
-            "family='schools'|'linear'|'logistic'|'poisson'|'neg_binomial'|'student_t'|'gamma' if it is an equivalent program.")
+            "family='schools'|'linear'|'logistic'|'poisson'|'neg_binomial'|'student_t'|'gamma'|'categorical' if it is an equivalent program.")
     return fam, priors
 
 
 def recognise(model_code: str) -> str:
-    """Return 'schools', 'linear', 'logistic', 'poisson', 'neg_binomial', 'student_t' or 'gamma' for a supported Stan program."""
+    """Return 'schools', 'linear', 'logistic', 'poisson', 'neg_binomial', 'student_t', 'gamma' or 'categorical' for a supported Stan program."""
     return program_info(model_code)[0]
 
 
@@ -179,7 +213,7 @@ def load_program_info(file=None, model_code=None, family=None, priors=None, **_i
     family= (and priors={'alpha': s, 'beta': s}, for 'neg_binomial' also 'phi': (shape, rate), for 'gamma' also
     'shape': (shape, rate)) override recognition."""
     if family is not None:
-        if family not in ("schools", "linear", "logistic", "poisson", "neg_binomial", "student_t", "gamma"):
+        if family not in ("schools", "linear", "logistic", "poisson", "neg_binomial", "student_t", "gamma", "categorical"):
             raise ValueError(f"unknown family {family!r}")
         return family, dict(priors or {})
     if model_code is None:
@@ -226,6 +260,24 @@ def pack_data(family: str, data: dict, nu=None) -> dict:
         if not np.all(yf == np.round(yf)) or np.any((yf != 0) & (yf != 1)):
             raise ValueError("bernoulli_logit data: y must hold the integers 0 and 1")
         return {"x": x, "y": yf.astype(np.int32)}
+    if family == "categorical":
+        # int<lower=2> ncat; int<lower=1, upper=ncat> y[N]: pystan rejects anything else
+        if "ncat" not in data:
+            raise ValueError("categorical data: ncat is missing (int<lower=2> ncat in the data block)")
+        kf = float(np.asarray(data["ncat"], np.float64).reshape(()))
+        if kf != np.round(kf) or kf < 2:
+            raise ValueError(f"categorical data: ncat must be an integer >= 2, got {data['ncat']!r}")
+        ncat = int(kf)
+        y = np.asarray(data["y"]).reshape(-1)
+        if y.shape[0] != N:
+            raise ValueError("y must have N entries")
+        if y.dtype.kind not in "iuf":
+            raise ValueError("categorical_logit data: y must hold the integers 1 .. ncat")
+        yf = y.astype(np.float64)
+        if not np.all(yf == np.round(yf)) or np.any(yf < 1) or np.any(yf > ncat):
+            bad = int(np.flatnonzero(~((yf == np.round(yf)) & (yf >= 1) & (yf <= ncat)))[0])
+            raise ValueError(f"categorical_logit data: y must hold the integers 1 .. ncat = {ncat}, got y[{bad}] = {y[bad]!r}")
+        return {"x": x, "y": yf.astype(np.int32), "ncat": ncat}
     if family in ("poisson", "neg_binomial"):
         y = np.asarray(data["y"]).reshape(-1)
         if y.shape[0] != N:
@@ -263,6 +315,9 @@ def column_names(family: str, data: dict) -> list:
         return (["mu", "tau"] + [f"eta[{j}]" for j in range(1, J + 1)] + [f"theta[{j}]" for j in range(1, J + 1)]
                 + ["lp__"])
     K = int(data["K"])
+    if family == "categorical":   # alpha[1 .. G], beta[1 .. G K] (class g's coefficients are beta[(g - 1) K + 1 .. g K]), lp__
+        G = int(data["ncat"]) - 1
+        return [f"alpha[{g}]" for g in range(1, G + 1)] + [f"beta[{k}]" for k in range(1, G * K + 1)] + ["lp__"]
     cols = ["alpha"] + [f"beta[{k}]" for k in range(1, K + 1)]
     if family in ("linear", "student_t"):
         cols.append("sigma")

@@ -52,7 +52,7 @@ class FullDataSampler:
 
     def __init__(self, model: engine.Model, group=None, force_exchange: bool = False, **cfg):
         if model.family != engine.FAMILIES["logistic"]:
-            name = {v: k for k, v in engine.FAMILIES.items()}.get(model.family, model.family)
+            name = engine.FAMILY_NAMES.get(model.family, model.family)
             raise ValueError("full-data mode needs the logistic family (a log density that is a pure sum over rows)"
                              f", not the {name} family")
         if model.nshards != 1:

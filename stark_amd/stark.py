@@ -109,6 +109,10 @@ def _unconstrain(family, data, init_dict):
         eta = np.asarray(init_dict.get("eta", np.zeros(J)), np.float64).reshape(J)
         return np.concatenate([[float(init_dict.get("mu", 0.0)), np.log(float(init_dict.get("tau", 1.0)))], eta])
     K = int(data["K"])
+    if family == "categorical":   # alpha[ncat - 1], then beta[K (ncat - 1)] column-major: Stan's own order, nothing constrained
+        G = int(data["ncat"]) - 1
+        return np.concatenate([np.asarray(init_dict.get("alpha", np.zeros(G)), np.float64).reshape(G),
+                               np.asarray(init_dict.get("beta", np.zeros(G * K)), np.float64).reshape(G * K)])
     v = [float(init_dict.get("alpha", 0.0))] + list(np.asarray(init_dict.get("beta", np.zeros(K)), np.float64).reshape(K))
     if family in ("linear", "student_t"):
         v.append(np.log(float(init_dict.get("sigma", 1.0))))
@@ -120,7 +124,7 @@ def _unconstrain(family, data, init_dict):
 
 
 NO_ANALYSIS_FAMILY = "neg_binomial"   # samples and combines; the analysis sweeps do not cover it
-NO_ANALYSIS_FAMILIES = (NO_ANALYSIS_FAMILY, "student_t", "gamma")   # Student-t and gamma likewise
+NO_ANALYSIS_FAMILIES = (NO_ANALYSIS_FAMILY, "student_t", "gamma", "categorical")   # Student-t, gamma and categorical likewise
 
 
 def _refuse_analysis(family, what):
